@@ -95,7 +95,7 @@ class _Plan:
     # Opt-in plan cache (environment variable TBN_PLAN_CACHE=<directory>): the launch choices tuned by one process are
     # written there and adopted by later processes for the same problem and mode instead of tuning again (~10 s per
     # backbone and mode; and every run of a job then uses the SAME kernels).  Off by default: without the variable every
-    # process tunes on its own box, which is what bench.py measures.  A file only counts for the library version that wrote
+    # process tunes on its own box; bench.py points it at the committed plans (bench_plans.json).  A file only counts for the library version that wrote
     # it (tbn_version) and is validated field by field on import (tbn_backbone_plan_import).
     def _cache_file(self, cin, training):
         d = os.environ.get("TBN_PLAN_CACHE")

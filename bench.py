@@ -10,6 +10,11 @@ audio, batch 32 clips per GPU -- global batch 256 at 8 GPUs, i.e. weak scaling).
 A step = forward + loss + backward (+ RCCL gradient all-reduce for N>1) + clip_grad_norm(20) +
 SGD(momentum) update, exactly the reference loop body (core/tools/train.py:69-94), on synthetic
 inputs already resident in HBM.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else the line can
+carry -- the box identity and calibration bursts, the roofline from instrumented and timeline steps
+run after the timed loop, the CPU baseline, the multi-GPU probes -- needs --full.  --dump-outputs DIR
+writes what the last timed step returned (dump_outputs) for comparing two builds on the same inputs.
 """
 import argparse
 import ctypes as C
@@ -42,6 +47,11 @@ CONFIGS = {
             ov=["data.audio.audio_length=1.279"], batch=64, train=False, gflop=344.47),
 }
 PEAK_FP32_MFMA_TFLOPS = 157.3         # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
+DUMP_SAMPLE = 1 << 22                 # --dump-outputs: elements kept of a longer vector (16 MB of float32)
+# Launch plans of the benchmarked shapes (tuned per-layer kernel choices, tbn_backbone_plan_export).  The autotuner times
+# candidates on the device, so two processes pick different kernels whose different summation orders change the results
+# beyond rounding after a few training steps; every run of the benchmark uses these instead (pin_plans).
+PINNED_PLANS = os.path.join(ROOT, "bench_plans.json")
 
 
 def synthetic_batch(B, n, device, seed, modality=("RGB", "Flow", "Audio"), audio_w=256):
@@ -57,6 +67,57 @@ def synthetic_batch(B, n, device, seed, modality=("RGB", "Flow", "Audio"), audio
     tgt = {"class": {"verb": torch.randint(0, 125, (B,), device=device, generator=g),
                      "noun": torch.randint(0, 352, (B,), device=device, generator=g)}}
     return inp, tgt
+
+
+def pin_plans(path=PINNED_PLANS):
+    """Writes the committed launch plans into a fresh plan-cache directory and points TBN_PLAN_CACHE at it: the backbones
+    adopt a plan from there instead of tuning one (core/models/bn_inception.py), so every run launches the same kernels and
+    computes the same results.  A shape without a committed plan is tuned and stored there as before.  Returns the directory
+    and the names written, or None when the caller set TBN_PLAN_CACHE (plan experiments)."""
+    import atexit
+    import shutil
+    import tempfile
+    if os.environ.get("TBN_PLAN_CACHE"):
+        return None
+    with open(path) as f:
+        plans = json.load(f)["plans"]
+    d = tempfile.mkdtemp(prefix="tbn_plans_")
+    atexit.register(shutil.rmtree, d, True)
+    for name, blob in plans.items():
+        with open(os.path.join(d, name), "wb") as f:
+            f.write(bytes.fromhex(blob))
+    os.environ["TBN_PLAN_CACHE"] = d
+    return d, set(plans)
+
+
+def _sampled(tensors):
+    """`tensors` flattened into one float32 vector; beyond DUMP_SAMPLE elements a fixed seeded sample of it (sorted
+    positions), so that two builds run with the same arguments are compared at the same positions"""
+    flat = torch.cat([t.detach().reshape(-1).float() for t in tensors])
+    if flat.numel() <= DUMP_SAMPLE:
+        return flat
+    idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(path, loss, out, model, train, backward):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files under `path` -- the heads'
+    outputs (out_<key>), the loss, and for a training step the BN running statistics (buffers), for a full train step
+    also the updated parameters (params) and their gradients (grads).  The last three are sampled (_sampled)."""
+    import numpy as np
+    arrays = {"out_" + k: v for k, v in out.items()}
+    if train:
+        arrays["loss"] = loss.reshape(1)
+        arrays["buffers"] = _sampled([b for b in model.buffers() if b.is_floating_point()])
+    if backward:
+        params = [p for p in model.parameters() if p.requires_grad]
+        arrays["params"] = _sampled(params)
+        arrays["grads"] = _sampled([p.grad if p.grad is not None else torch.zeros_like(p) for p in params])
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20, {k: a.nbytes for k, a in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def collect_profile():
@@ -522,7 +583,15 @@ def main():
                     help="diagnostic: BN apply / BN-backward apply passes riding in sibling GEMM launches (default: the model's)")
     ap.add_argument("--eval-chunk", type=int, default=0,
                     help="config 5: frames per engine call of the eval forward (default: the backbone's, 256)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: rocm-smi state, box identity and calibration bursts "
+                         "(`box`), instrumented and timeline steps after the timed loop (`roofline`), the CPU baseline "
+                         "(`cpu_baseline`, config 4), and for N > 1 the all-reduce probe, bucket count, exposed all-reduce "
+                         "time and plan check")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one returned (heads' outputs, loss; for a train step "
+                         "also sampled parameters, gradients and BN running statistics) to DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--host-inputs", action="store_true",
                     help="diagnostic (never the headline): the batch starts in pinned HOST memory every step and is copied "
                          "over PCIe on a side stream, double-buffered against the previous step -- the PCIe-inclusive rate")
@@ -530,12 +599,13 @@ def main():
                     help="the audio leg starts from WAVEFORMS (B, n, 30695 samples = 1.279 s at 24 kHz, resident in HBM): the "
                          "log-power STFT kernel (reference dataset.py:483-495, CPU librosa there) runs inside the timed step")
     ap.add_argument("--profile-steps", type=int, default=3,
-                    help="instrumented single-stream steps run AFTER the timed loop (kernel timestamps on every conv-GEMM "
+                    help="--full: instrumented single-stream steps run AFTER the timed loop (kernel timestamps on every conv-GEMM "
                          "launch): `roofline` reports the median / min / max over them.  The timed region is the product "
                          "step only")
     ap.add_argument("--profile-every", type=int, default=0,
                     help="diagnostic (rocprofv3 / PMC passes): ALSO instrument every k-th step INSIDE the timed loop, so a "
-                         "short traced run contains instrumented steps; the line then says timed_region_instrumented")
+                         "short traced run contains instrumented steps; the line then says timed_region_instrumented "
+                         "(and with --full takes `roofline` from them)")
     ap.add_argument("--timeline", default=None, metavar="CSV",
                     help="diagnostic: after the timed loop run 4 more product steps with the library's kernel timeline on "
                          "(tbn_timeline_enable: begin / end of every launch on a common clock, no external tracer) and write "
@@ -545,7 +615,7 @@ def main():
                          "forward / backward call and print (stderr) when each ran on the GPU and how long the host took "
                          "to issue it -- the stagger between the modality streams")
     ap.add_argument("--timeline-steps", type=int, default=4,
-                    help="product steps run AFTER the timed loop under the library's kernel timeline: `roofline.frac` is the "
+                    help="--full: product steps run AFTER the timed loop under the library's kernel timeline: `roofline.frac` is the "
                          "conv stage of that schedule (0: skip; the line then leads with the one-stream conv stage)")
     ap.add_argument("--high-prio", default=None,
                     help="A/B: comma-separated modalities whose backbone stream gets the high HIP priority, or 'none' "
@@ -571,10 +641,11 @@ def main():
     os.dup2(2, 1)
     sys.stdout = sys.stderr
 
+    pinned = pin_plans()      # before the first forward: the priming step would tune
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    smi = query_rocm_smi() if rank == 0 else None      # before anything in this process touches the GPU
+    smi = query_rocm_smi() if rank == 0 and args.full else None      # before anything in this process touches the GPU
     assert torch.cuda.is_available(), "bench.py needs MI355X GPUs (no CPU fallback)"
     if os.environ.get("TBN_BENCH_BACKEND", "nccl") != "nccl":
         local_rank = local_rank % torch.cuda.device_count()      # rehearsal: ranks share the card(s) present
@@ -634,13 +705,13 @@ def main():
     def eval_step():
         with torch.no_grad():
             out = model(inp)
-        return out["verb"].float().sum() * 0 + 1.0
+        return out["verb"].float().sum() * 0 + 1.0, out
 
     def fwd_step():
         with torch.no_grad():
             out = model(inp)
             loss, _ = model.get_loss(criterion, tgt, out, 0)
-        return loss["total"].detach()      # no reference to the autograd graph survives the step
+        return loss["total"].detach(), out
 
     host_inp, copy_stream, staged = None, None, [None]
     if args.host_inputs:
@@ -655,7 +726,9 @@ def main():
             staged[0] = (bufs, ev)
         stage()
 
-    def step():
+    captured = {}      # step(capture=True): what the step returned, for --dump-outputs
+
+    def step(capture=False):
         if host_inp is not None:
             bufs, ev = staged[0]
             torch.cuda.current_stream().wait_event(ev)
@@ -666,18 +739,22 @@ def main():
         if wave is not None:          # waveform -> (B, n, 1, 256, 256) log-power spectrogram on the GPU, every step
             inp["Audio"] = spectrogram(wave).view(B, n, 1, 256, 256)
         if not C_["train"]:
-            return eval_step()
-        if args.forward_only:
-            return fwd_step()
-        opt.zero_grad(set_to_none=True)
-        out = model(inp)
-        loss, _ = model.get_loss(criterion, tgt, out, 0)
-        loss["total"].backward()              # N>1: gradient all-reduce is issued inside backward, waited at its end
-        opt.step(clip_grad=cfg.train.clip_grad, grads_consumed=True)   # clip_grad_norm_(20) + SGD(momentum) in three HIP launches (zero_grad precedes every backward)
-        return loss["total"].detach()      # no reference to the autograd graph survives the step
+            loss, out = eval_step()
+        elif args.forward_only:
+            loss, out = fwd_step()
+        else:
+            opt.zero_grad(set_to_none=True)
+            out = model(inp)
+            loss, _ = model.get_loss(criterion, tgt, out, 0)
+            loss["total"].backward()              # N>1: gradient all-reduce is issued inside backward, waited at its end
+            opt.step(clip_grad=cfg.train.clip_grad, grads_consumed=True)   # clip_grad_norm_(20) + SGD(momentum) in three HIP launches (zero_grad precedes every backward)
+            loss = loss["total"].detach()
+        if capture:
+            captured.update(loss=loss, out={k: v.detach() for k, v in out.items()})
+        return loss      # no reference to the autograd graph survives the step
 
     buckets_last_step = None
-    if world > 1 and hasattr(model, "time_sync"):
+    if world > 1 and args.full and hasattr(model, "time_sync"):
         model.time_sync = True     # HIP events around finish_gradient_sync: the all-reduce tail backward did not hide
     multi = not args.no_multi_stream
     core.multi_stream = multi
@@ -717,9 +794,9 @@ def main():
              # not one of the W warm-up steps, so a small --warmup cannot push the autotuner into the timed region
     L = lib()
     L.tbn_profile_reset()
-    box = box_identity(device, smi) if rank == 0 else None     # CPU / GPU names + a warm pure-MFMA burst: before the timed loop
+    box = box_identity(device, smi) if rank == 0 and args.full else None     # CPU / GPU names + a warm pure-MFMA burst: before the timed loop
     probe = None
-    if world > 1:
+    if world > 1 and args.full:
         # one-shot all-reduce probe on a tensor the size of a backbone's flat weight gradient (the largest collective of a
         # step, ~41 MB), before the timed loop: makes the first real multi-GPU run self-explaining (link bandwidth vs
         # exposed_allreduce_ms).  busbw = algbw * 2 (n - 1) / n (ring all-reduce convention).
@@ -753,9 +830,9 @@ def main():
     for _ in range(args.warmup):
         step()
     fence()
-    if world > 1 and hasattr(model, "exposed_sync_ms"):
+    if world > 1 and args.full and hasattr(model, "exposed_sync_ms"):
         model.exposed_sync_ms()     # drop the warm-up records
-    def profiled_step():
+    def profiled_step(capture=False):
         # kernel timestamps on every conv-GEMM launch; the backbones run on ONE stream (and the weight gradients on it
         # too) so a bracket times exactly one kernel -- in the product step they overlap
         core.multi_stream = False
@@ -763,7 +840,7 @@ def main():
             b_.use_aux_stream = False
             b_.use_branch_streams = False
         L.tbn_profile_enable(1)
-        out = step()
+        out = step(capture)
         L.tbn_profile_enable(0)
         core.multi_stream = multi
         for b_, a_, br_ in zip(bases, aux, branch):
@@ -774,17 +851,21 @@ def main():
     # one event per step boundary on the compute stream (the modality streams fork from and join it inside a step): the
     # per-step GPU times of the timed region, read AFTER the loop -- nothing inside the loop synchronises
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    last = args.steps - 1 if args.dump_outputs else -1
     t0 = time.perf_counter()
     for i in range(args.steps):
         marks[i].record()
         if args.profile_every > 0 and (i % args.profile_every == 0):
-            loss = profiled_step()      # diagnostic runs only (see --profile-every): the default timed region has none
+            loss = profiled_step(i == last)      # diagnostic runs only (see --profile-every): the default timed region has none
         else:
-            loss = step()
+            loss = step(i == last)
     marks[args.steps].record()
     fence()
     dt = time.perf_counter() - t0
-    if world > 1 and hasattr(model, "bucket_log"):
+    if args.dump_outputs and rank == 0:      # before any further step changes the model
+        dump_outputs(args.dump_outputs, captured["loss"], captured["out"], model, C_["train"],
+                     C_["train"] and not args.forward_only)
+    if world > 1 and args.full and hasattr(model, "bucket_log"):
         model.bucket_log.clear()
         step()                                  # one more (untimed) step: how many bucket collectives a step issues
         torch.cuda.synchronize()
@@ -792,34 +873,33 @@ def main():
     step_gpu_each = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
     step_gpu_ms = sorted(step_gpu_each)
     exposed_ms = None
-    if world > 1 and hasattr(model, "exposed_sync_ms"):
+    if world > 1 and args.full and hasattr(model, "exposed_sync_ms"):
         e = model.exposed_sync_ms()
         t = torch.tensor([e if e is not None else 0.0], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         exposed_ms = float(t.item())
     # instrumented steps AFTER the timed region (every rank runs them: the step holds collectives for N > 1); each one is
     # collected on its own so that the conv-stage figure is a median over samples, not one step
-    prof_samples = []
-    if args.profile_every > 0:
-        prof_samples.append(collect_profile() if rank == 0 else [])
-    for _ in range(max(0, args.profile_steps) if args.profile_every <= 0 else 0):
-        L.tbn_profile_reset()
-        profiled_step()
-        torch.cuda.synchronize()
-        prof_samples.append(collect_profile() if rank == 0 else [])
-    if world > 1:
-        fence()
-    sched = None
-    if args.timeline_steps > 0:
-        sched = timed_schedule_conv_stage(step, args.timeline_steps, B * flop_per_clip)
+    prof_samples, sched, plan_fps, plans_equal = [], None, None, None
+    if args.full:
+        if args.profile_every > 0:
+            prof_samples.append(collect_profile() if rank == 0 else [])
+        for _ in range(max(0, args.profile_steps) if args.profile_every <= 0 else 0):
+            L.tbn_profile_reset()
+            profiled_step()
+            torch.cuda.synchronize()
+            prof_samples.append(collect_profile() if rank == 0 else [])
         if world > 1:
             fence()
-    plan_fps = {m: "+".join(sorted(b_.plan_fingerprints().values())) for m, b_ in zip(modality, bases)}
-    plans_equal = None
-    if world > 1:
-        every_fp = [None] * world
-        dist.all_gather_object(every_fp, plan_fps)
-        plans_equal = all(f == every_fp[0] for f in every_fp)
+        if args.timeline_steps > 0:
+            sched = timed_schedule_conv_stage(step, args.timeline_steps, B * flop_per_clip)
+            if world > 1:
+                fence()
+        plan_fps = {m: "+".join(sorted(b_.plan_fingerprints().values())) for m, b_ in zip(modality, bases)}
+        if world > 1:
+            every_fp = [None] * world
+            dist.all_gather_object(every_fp, plan_fps)
+            plans_equal = all(f == every_fp[0] for f in every_fp)
     rank_ms = None
     if world > 1:
         t = torch.tensor([dt], device=device, dtype=torch.float64)
@@ -855,11 +935,14 @@ def main():
                 print("  %-22s host %6.2f -> %6.2f ms (%.2f)   GPU %6.2f -> %6.2f ms (%.2f)" %
                       (name[4:], (t0 - h0) * 1e3, (t1 - h0) * 1e3, (t1 - t0) * 1e3, ref.elapsed_time(e0),
                        ref.elapsed_time(e1), e0.elapsed_time(e1)), file=sys.stderr)
+    if pinned is None:
+        plans_used = "TBN_PLAN_CACHE=" + os.environ["TBN_PLAN_CACHE"]
+    else:
+        tuned = sorted(set(os.listdir(pinned[0])) - pinned[1])
+        plans_used = ("tuned in this run: " + ", ".join(tuned)) if tuned else "committed (bench_plans.json)"
     if rank == 0:
         clips = B * world * args.steps
         value = clips / dt
-        roofline = roofline_object(prof_samples, max(1, len(range(0, args.steps, args.profile_every))) if args.profile_every > 0 else 1,
-                                   value / world * flop_per_clip / 1e12 / PEAK_FP32_MFMA_TFLOPS, sched)
         line = {
             "metric": "clips/sec (3-seg RGB+Flow+Audio TBN fwd+bwd)" if args.config == 4 and not args.forward_only
             else f"clips/sec (config {args.config}{', forward only' if args.forward_only else ''})",
@@ -868,7 +951,7 @@ def main():
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": C_["name"] + (" [forward only]" if args.forward_only and C_["train"] else ""),
                        "batch_per_gpu": B, "global_batch": B * world, "segments": n,
-                       "parallelism": f"dp{world}" if world > 1 else "single",
+                       "parallelism": f"dp{world}" if world > 1 else "single", "launch_plans": plans_used,
                        "streams": {"modality_streams": bool(multi and len(modality) > 1),
                                    "weight_gradient_stream": [m for m, a_ in zip(modality, aux) if a_],
                                    "branch_streams": [m for m, b_ in zip(modality, branch) if b_],
@@ -877,7 +960,6 @@ def main():
                                    "early_weight_flip": bool(getattr(core, "flip_weights_early", False)) and multi and len(modality) > 1},
                        **({"inputs": "pinned host memory, PCIe copy every step (diagnostic)"} if args.host_inputs else {}),
                        **({"audio_input": "waveform (30695 samples), STFT kernel inside the timed step"} if args.stft_inputs else {})},
-            "roofline": roofline,
             # GPU time of each timed step (events at the step boundaries of rank 0's compute stream): a clock ramp or a
             # straggler step shows up here, not in the mean
             "step_gpu_ms": {"median": round(step_gpu_ms[len(step_gpu_ms) // 2], 3), "min": round(step_gpu_ms[0], 3),
@@ -887,26 +969,29 @@ def main():
         }
         if world > 1:
             line["multi_gpu"] = {"dist_world_size": dist.get_world_size(), "cuda_device_count": torch.cuda.device_count(),
-                                 # collectives issued from INSIDE the backbones' backward passes in the last step (two per
-                                 # backbone: inception_5a..5b, then 4a..4e; the prefix follows from the gradient hook)
-                                 "gradient_buckets_per_step": buckets_last_step,
-                                 "ms_per_step_rank_min": round(min(rank_ms), 3), "ms_per_step_rank_max": round(max(rank_ms), 3),
-                                 "allreduce_probe": probe}
-        if exposed_ms is not None:
-            # mean GPU time per step between the end of the last backbone's backward (entry of the gradient-sync
-            # callback on the compute stream) and the return of finish_gradient_sync, max over ranks
-            line["exposed_allreduce_ms"] = round(exposed_ms, 3)
-        # fingerprint of each backbone's tuned launch plan (tbn_backbone_plan_fingerprint): equal lines on two boxes with
-        # different numbers = a slow box; different fingerprints = a different plan.  N > 1: rank 0's plans are
-        # broadcast at first use (DataParallel / PlanSync), `plans_equal_across_ranks` confirms it
-        box["plans"] = plan_fps
-        if world > 1:
-            line["multi_gpu"]["plans_equal_across_ranks"] = plans_equal
-        line["box"] = box
+                                 "ms_per_step_rank_min": round(min(rank_ms), 3), "ms_per_step_rank_max": round(max(rank_ms), 3)}
+        if args.full:
+            line["roofline"] = roofline_object(
+                prof_samples, max(1, len(range(0, args.steps, args.profile_every))) if args.profile_every > 0 else 1,
+                value / world * flop_per_clip / 1e12 / PEAK_FP32_MFMA_TFLOPS, sched)
+            if world > 1:
+                # collectives issued from INSIDE the backbones' backward passes in the last step (two per
+                # backbone: inception_5a..5b, then 4a..4e; the prefix follows from the gradient hook)
+                line["multi_gpu"].update(gradient_buckets_per_step=buckets_last_step, allreduce_probe=probe,
+                                         plans_equal_across_ranks=plans_equal)
+            if exposed_ms is not None:
+                # mean GPU time per step between the end of the last backbone's backward (entry of the gradient-sync
+                # callback on the compute stream) and the return of finish_gradient_sync, max over ranks
+                line["exposed_allreduce_ms"] = round(exposed_ms, 3)
+            # fingerprint of each backbone's tuned launch plan (tbn_backbone_plan_fingerprint): equal lines on two boxes with
+            # different numbers = a slow box; different fingerprints = a different plan.  N > 1: rank 0's plans are
+            # broadcast at first use (DataParallel / PlanSync), `plans_equal_across_ranks` confirms it
+            box["plans"] = plan_fps
+            line["box"] = box
+            if world == 1 and not args.no_cpu_baseline and args.config == 4 and not args.forward_only:
+                line["cpu_baseline"] = cpu_baseline()
         if args.profile_every > 0:
             line["timed_region_instrumented"] = True      # diagnostic run: `value` includes single-stream instrumented steps
-        if world == 1 and not args.no_cpu_baseline and args.config == 4 and not args.forward_only:
-            line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), file=json_out, flush=True)
     if world > 1:
         dist.destroy_process_group()

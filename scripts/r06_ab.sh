@@ -18,7 +18,7 @@ set -o pipefail
 MODE=${1:?mode}; REPS=${2:-3}
 EXP=$PWD/scripts/ab/lib_exp.so
 line() { python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('%-34s %.3f ms/step  %.2f clips/s  e2e %.4f  conv one-stream %.4f  timed schedule %s' % (sys.argv[1], d['ms_per_step'], d['value'], r['end_to_end_frac'], r['all_conv_gemm']['frac'], (r.get('conv_stage_timed_schedule') or {}).get('frac')))" "$1"; }
-B="python bench.py --steps 40 --warmup 5 --no-cpu-baseline --profile-steps 1"
+B="python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --profile-steps 1"
 case $MODE in
   tune)
     for rep in $(seq $REPS); do
@@ -58,7 +58,7 @@ case $MODE in
     python scripts/step_timeline.py /tmp/tl_4.csv 1 bins | tee gpurun_out/r06_timeline_bins_config4.txt ;;
   batch)
     for b in 32 24 40 48 64 96 32; do
-      python bench.py --batch-per-gpu $b --steps 20 --warmup 5 --no-cpu-baseline --timeline-steps 2 2>/dev/null | python -c "
+      python bench.py --full --batch-per-gpu $b --steps 20 --warmup 5 --no-cpu-baseline --timeline-steps 2 2>/dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.read()); r = d['roofline']
 print('B=%3s  %8.2f clips/s  %7.3f ms/step  end to end %.4f  conv stage timed %.4f  one stream %.4f  dominant %.4f' % (sys.argv[1], d['value'], d['ms_per_step'], r['end_to_end_frac'], r['frac'], r['all_conv_gemm']['frac'], r['dominant']['frac']))" $b | tee -a gpurun_out/r06_batch_sweep.txt
@@ -74,9 +74,8 @@ print('B=%3s  %8.2f clips/s  %7.3f ms/step  end to end %.4f  conv stage timed %.
     bash scripts/refresh_profiles.sh r06 traffic > gpurun_out/r06_final_traffic.log 2>&1
     cp gpurun_out/r06_pmc_traffic.json gpurun_out/r06_pmc_traffic_top.txt profiles/
     for i in 1 2 3; do
-      timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r06_final_bench_driver_command_$i.json 2> /dev/null
-      head -c 160 gpurun_out/r06_final_bench_driver_command_$i.json; echo
+      timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full 2> /dev/null
     done
-    timeout -k 10 400 python bench.py > gpurun_out/r06_final_bench_default.json 2> /dev/null ;;
+    timeout -k 10 400 python bench.py --full 2> /dev/null ;;
   *) echo "unknown mode $MODE"; exit 2 ;;
 esac

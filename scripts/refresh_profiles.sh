@@ -14,17 +14,17 @@ if [ "$QUICK" = "traffic" ]; then ONLY_TRAFFIC=1; fi
 if [ "$QUICK" = "pmc" ]; then ONLY_PMC=1; QUICK=; fi
 if [ "$QUICK" = "bench" ]; then ONLY_BENCH=1; QUICK=; fi
 if [ -z "$ONLY_TRAFFIC" ] && [ -z "$ONLY_PMC" ]; then
-timeout -k 10 400 python bench.py --no-cpu-baseline > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
+timeout -k 10 400 python bench.py --full --no-cpu-baseline > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
 echo "default: $(head -c 200 $O/${TAG}_bench_default.json)"
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_driver_command.json 2> /dev/null
+timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${TAG}_bench_driver_command.json 2> /dev/null
 echo "driver command: $(head -c 200 $O/${TAG}_bench_driver_command.json)"
 if [ -z "$QUICK" ]; then
   for c in 2 3 5; do
-    timeout -k 10 300 python bench.py --config $c > $O/${TAG}_bench_config$c.json 2> /dev/null
+    timeout -k 10 300 python bench.py --full --config $c > $O/${TAG}_bench_config$c.json 2> /dev/null
   done
-  timeout -k 10 300 python bench.py --forward-only > $O/${TAG}_bench_config4_forward_only.json 2> /dev/null
-  timeout -k 10 300 python bench.py --stft-inputs --no-cpu-baseline > $O/${TAG}_bench_stft_inputs.json 2> /dev/null
-  timeout -k 10 300 python bench.py --config 3 --stft-inputs > $O/${TAG}_bench_config3_stft_inputs.json 2> /dev/null
+  timeout -k 10 300 python bench.py --full --forward-only > $O/${TAG}_bench_config4_forward_only.json 2> /dev/null
+  timeout -k 10 300 python bench.py --full --stft-inputs --no-cpu-baseline > $O/${TAG}_bench_stft_inputs.json 2> /dev/null
+  timeout -k 10 300 python bench.py --full --config 3 --stft-inputs > $O/${TAG}_bench_config3_stft_inputs.json 2> /dev/null
 fi
 timeout -k 10 120 python scripts/layer_profile.py 3 224 224 96 > $O/${TAG}_layer_profile_rgb_R96_single_stream.txt 2> /dev/null
 timeout -k 10 120 python scripts/layer_profile.py 10 224 224 96 > $O/${TAG}_layer_profile_flow_R96_single_stream.txt 2> /dev/null
@@ -39,11 +39,11 @@ timeout -k 10 200 python scripts/red_epilogue_cost.py 96 2> /dev/null | grep -v 
 cd /tmp && export TMPDIR=/tmp
 # rocprofv3 kernel trace of the bench command with HIP-event brackets on every step (same kernels, same averages)
 rm -rf /tmp/prof_$TAG
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG -o trace --output-format csv -- python3 $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --profile-every 1 --timeline-steps 0 > $ROOT/$O/${TAG}_bench_profile_every_1.json 2> $ROOT/$O/${TAG}_rocprof.err
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG -o trace --output-format csv -- python3 $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --profile-every 1 --timeline-steps 0 > $ROOT/$O/${TAG}_bench_profile_every_1.json 2> $ROOT/$O/${TAG}_rocprof.err
 cp "$(find /tmp/prof_$TAG -name '*kernel_stats.csv' | head -1)" $ROOT/$O/${TAG}_bench_profile_every_1.kernel_stats.csv
 # heads (PE / GroupNorm / MHA / fusion) + STFT: config 3 from waveforms
 rm -rf /tmp/prof_h_$TAG
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -d /tmp/prof_h_$TAG -o trace --output-format csv -- python3 $ROOT/bench.py --config 3 --stft-inputs --steps 10 --warmup 3 --no-cpu-baseline --profile-every 0 --timeline-steps 0 > $ROOT/$O/${TAG}_heads_bench_config3_stft.json 2> /dev/null
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d /tmp/prof_h_$TAG -o trace --output-format csv -- python3 $ROOT/bench.py --full --config 3 --stft-inputs --steps 10 --warmup 3 --no-cpu-baseline --profile-every 0 --timeline-steps 0 > $ROOT/$O/${TAG}_heads_bench_config3_stft.json 2> /dev/null
 cp "$(find /tmp/prof_h_$TAG -name '*kernel_stats.csv' | head -1)" $ROOT/$O/${TAG}_heads_config3_stft.kernel_stats.csv
 fi
 if [ -n "$ONLY_BENCH" ]; then cd $ROOT; echo done; exit 0; fi

@@ -127,14 +127,14 @@ def test_bench_n2_control_flow_rehearsal(launcher):
     then starts the ranks itself as a child process and relays the JSON line and the exit code -- round-5 verdict item 2a),
     with the two ranks sharing the one card over gloo (TBN_BENCH_BACKEND=gloo: RCCL needs a GPU per rank): the barrier /
     max-over-ranks timing / DataParallel path (gradient buckets included) must run and stdout must be exactly one JSON line
-    from rank 0."""
+    from rank 0.  --full: the line then also carries the roofline, bucket count and plan check asserted here."""
     import json
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(TBN_BENCH_BACKEND="gloo", OMP_NUM_THREADS="2")
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "2"]
+    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "2", "--full"]
     if launcher == "plain python":
         cmd = [sys.executable] + tail
     else:

@@ -991,6 +991,66 @@ def test_bench_roofline_is_a_median_over_post_loop_samples():
     assert cpu["hardware_threads"] >= 1 and (cpu["physical_cores"] is None or cpu["physical_cores"] <= cpu["hardware_threads"])
 
 
+def test_bench_pins_the_committed_launch_plans(tmp_path, monkeypatch):
+    """bench.py host logic (no GPU): the committed plans are written into a fresh plan-cache directory that TBN_PLAN_CACHE
+    points at, under the names core/models/bn_inception.py looks for with THIS library version, config 4's three backbones
+    among them; a TBN_PLAN_CACHE of the caller's own wins"""
+    import shutil
+    import bench
+    from attention_based_tbn_amd._lib import lib
+    monkeypatch.delenv("TBN_PLAN_CACHE", raising=False)
+    with open(bench.PINNED_PLANS) as f:
+        plans = json.load(f)["plans"]
+    d, names = bench.pin_plans()
+    try:
+        assert os.environ["TBN_PLAN_CACHE"] == d and names == set(plans) == set(os.listdir(d))
+        for n in names:
+            with open(os.path.join(d, n), "rb") as f:
+                assert f.read() == bytes.fromhex(plans[n]), n
+    finally:
+        shutil.rmtree(d)
+    shapes = set()
+    for n in names:
+        m = re.fullmatch(r"tbnplan_v(\d+)_(c\d+_f\d+_\d+x\d+_(?:train|eval))\.bin", n)
+        assert m and int(m.group(1)) == lib().tbn_version(), n
+        shapes.add(m.group(2))
+    assert {"c3_f96_224x224_train", "c10_f96_224x224_train", "c1_f96_256x256_train"} <= shapes, shapes
+    monkeypatch.setenv("TBN_PLAN_CACHE", str(tmp_path))
+    assert bench.pin_plans() is None and os.environ["TBN_PLAN_CACHE"] == str(tmp_path)
+
+
+def test_bench_dump_outputs_are_float32_and_sampled_at_fixed_positions(tmp_path, monkeypatch):
+    """bench.py --dump-outputs host logic (no GPU): one float32 .npy per returned array; parameters, gradients and BN
+    statistics beyond DUMP_SAMPLE elements are a sample taken at the same positions in every run, within 64 MB"""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(40, 30), torch.nn.BatchNorm1d(30), torch.nn.Linear(30, 5))
+    model[2].weight.requires_grad_(False)
+    out = model(torch.randn(8, 40))
+    loss = out.square().mean()
+    loss.backward()
+    out = {"verb": out[:, :3], "noun": out[:, 3:]}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), loss.detach(), out, model, True, True)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["buffers.npy", "grads.npy", "loss.npy", "out_noun.npy", "out_verb.npy", "params.npy"]
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype == np.float32 for a in got.values())
+    for k, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / (k + ".npy"))), k
+    assert got["out_verb"].shape == (8, 3) and got["loss"][0] == np.float32(loss.item())
+    assert got["buffers"].shape == (60,)                        # running mean + var: below the sample size, whole
+    trainable = [p for p in model.parameters() if p.requires_grad]
+    assert got["params"].shape == got["grads"].shape == (1000,) and sum(p.numel() for p in trainable) > 1000
+    flat = torch.cat([p.detach().reshape(-1) for p in trainable]).numpy()
+    gflat = torch.cat([p.grad.reshape(-1) for p in trainable]).numpy()
+    idx = torch.randint(flat.size, (1000,), generator=torch.Generator().manual_seed(0)).sort().values.numpy()
+    assert np.array_equal(got["params"], flat[idx]) and np.array_equal(got["grads"], gflat[idx])   # same positions in both
+    bench.dump_outputs(str(tmp_path / "eval"), None, out, model, False, False)
+    assert sorted(os.listdir(tmp_path / "eval")) == ["out_noun.npy", "out_verb.npy"]
+
+
 def test_pmc_traffic_prices_requests_with_the_calibration(tmp_path):
     """scripts/pmc_traffic.py --raw on synthetic rocprofv3 counter CSVs: bytes per request come from the calibration
     launches of known byte counts (128 here, as on the MI355X), the priming / warm-up steps are cut at the SKIP-th
