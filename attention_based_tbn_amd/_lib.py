@@ -57,6 +57,7 @@ class OptTensor(C.Structure):
 # name -> (restype, argtypes); every symbol declared in include/tbn_hip.h
 SIGNATURES = {
     "tbn_version": (c_i, []),
+    "tbn_capabilities": (c_i, []),
     "tbn_last_error": (C.c_char_p, []),
     "tbn_profile_enable": (c_i, [c_i]),
     "tbn_profile_reset": (c_i, []),

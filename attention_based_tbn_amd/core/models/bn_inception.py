@@ -314,6 +314,10 @@ class BNInception(nn.Module):
         # branch mode -- and bit-identical to the stand-alone passes
         self.use_riders = True
         self.stem_wgrad_last = False    # TBN_BACKBONE_STEM_WGRAD_LAST: see include/tbn_hip.h (bench.py --stem-wgrad-last)
+        # convolution math of the EVAL forward: "f32" (every conv on the fp32 MFMA) | "bf16x6" | "bf16x3" (the 3x3 / stride 1
+        # layers on the bf16 MFMA with the fp32 operands split into bf16 planes: include/tbn_hip.h TBN_BACKBONE_CONV_BF16X6 /
+        # _BF16X3).  Ignored in training mode; not part of state_dict
+        self._conv_math = "f32"
         self._last_flip = None          # weak reference to the last training forward's _Flip (flip_weights_early)
         self._out_slot = None       # set by TBNModel for one forward: where the pooled (frames, 1024) feature is to be written
         self.plan_sync = None       # data parallel: object with is_source() / check(key, device) / broadcast(blob, device)
@@ -466,8 +470,22 @@ class BNInception(nn.Module):
         f.done = True
         return True
 
+    CONV_MATH = {"f32": 0, "bf16x6": 8, "bf16x3": 16}   # -> TBN_BACKBONE_CONV_BF16X6 / TBN_BACKBONE_CONV_BF16X3
+
+    @property
+    def conv_math(self):
+        return self._conv_math
+
+    @conv_math.setter
+    def conv_math(self, value):
+        if value not in self.CONV_MATH:
+            raise ValueError("conv_math must be one of %s, got %r" % (", ".join(map(repr, self.CONV_MATH)), value))
+        self._conv_math = value
+
     def _engine_flags(self):
-        return (1 if self.use_riders else 0) | (2 if self.stem_wgrad_last else 0)   # TBN_BACKBONE_RIDERS | TBN_BACKBONE_STEM_WGRAD_LAST
+        # TBN_BACKBONE_RIDERS | TBN_BACKBONE_STEM_WGRAD_LAST | the eval forward's convolution math
+        return ((1 if self.use_riders else 0) | (2 if self.stem_wgrad_last else 0)
+                | (0 if self.training else self.CONV_MATH[self._conv_math]))
 
     def _side_stream_ptr(self):
         """the side stream that goes with the current stream (0: serial program; also while a graph is being captured --
@@ -515,7 +533,7 @@ class BNInception(nn.Module):
         if self.training:
             raise TbnHipError("features(): only available in eval mode; use forward() for training")
         prm = BackboneParams(ptr(self.flat_weight), ptr(self.flat_bias), ptr(gamma), ptr(beta),
-                             ptr(self.running_mean), ptr(self.running_var), 0.1, 1e-5)
+                             ptr(self.running_mean), ptr(self.running_var), 0.1, 1e-5, 0, self.CONV_MATH[self._conv_math])
         feat_ptr = C.c_void_p()
         call("tbn_backbone_forward", plan.handle, 0, ptr(x), C.byref(prm), ptr(ws), ws.numel(), C.byref(feat_ptr),
              stream_ptr())

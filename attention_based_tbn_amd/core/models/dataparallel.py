@@ -460,3 +460,11 @@ class DataParallel(nn.Module):
 
     def get_loss(self, criterion, target, preds, epoch=0):
         return self.module.get_loss(criterion, target, preds, epoch)
+
+    @property
+    def conv_math(self):
+        return self.module.conv_math
+
+    @conv_math.setter
+    def conv_math(self, value):
+        self.module.conv_math = value

@@ -193,6 +193,17 @@ class TBNModel(nn.Module):
             # reference: every BatchNorm2d child with index > 1, i.e. all but conv1_7x7_s2_bn
             base.set_bn_trainable(first=True, rest=False)
 
+    @property
+    def conv_math(self):
+        """convolution math of every backbone's EVAL forward: "f32" | "bf16x6" | "bf16x3" (BNInception.conv_math);
+        ignored in training mode, so a train / validate loop sets it once"""
+        return getattr(self, "Base_{}".format(self.modality[0])).conv_math
+
+    @conv_math.setter
+    def conv_math(self, value):
+        for m in self.modality:
+            getattr(self, "Base_{}".format(m)).conv_math = value
+
     def maybe_unused_parameter_prefixes(self):
         """parameters that may get no gradient in a step: with `data.audio.dropout > 0` the per-replica host draw of
         reference model.py:215-222 can drop the audio feature on one data-parallel rank and keep it on another --

@@ -272,6 +272,8 @@ extern "C" {
 
 int tbn_version(void) { return 102 | (TBN_EXPERIMENT ? 0x10000 : 0); }
 
+int tbn_capabilities(void) { return TBN_CAP_CONV_BF16X; }
+
 int tbn_diag_mfma_burst(float* sink, int workgroups, int iters, double* flops, void* stream) {
   TBN_REQUIRE(sink != nullptr && workgroups > 0 && workgroups <= 65536 && iters > 0, "diag_mfma_burst: bad argument");
   hipLaunchKernelGGL(mfma_burst_kernel, dim3(workgroups), dim3(256), 0, (hipStream_t)stream, sink, iters);
@@ -426,6 +428,10 @@ static int desc_to_convp(const tbn_conv_desc* d, float* workspace, hipStream_t s
     p.stat_partial = d->stat_partial;
     p.mode = d->epilogue;
   } else {
+    if (d->flags & (CONV_FLAG_BF16X6 | CONV_FLAG_BF16X3)) {
+      tbn_set_error("conv_launch: the bf16x kernels (flags 32 / 64) compute forward convolutions only, not dgrad = 1");
+      return TBN_ERR_UNSUPPORTED;
+    }
     TBN_REQUIRE(workspace != nullptr, "conv_launch: a data gradient needs the flipped-weight workspace");
     TBN_REQUIRE(d->epilogue == 0 && d->nred >= 0 && d->nred <= TBN_CONV_MAXSEG, "conv_launch: data gradient: epilogue 0, nred <= 4");
     TBN_TRY(tbn_launch_weight_flip_transpose(d->weight, workspace, d->cout, d->ksize * d->ksize, d->cin, st));

@@ -1,0 +1,287 @@
+// Split-bf16 3x3 / stride 1 / pad 1 forward convolution for gfx950: the fp32 product on v_mfma_f32_32x32x16_bf16.
+//
+// Replaces, under model.eval() / torch.no_grad() (reference core/tools/test.py:67-87), what the reference gets from cuDNN
+// through the 3x3 nn.Conv2d layers of core/models/bn_inception_audio.py:24-401 -- fp32 in, fp32 out, opt-in.
+//
+// An fp32 value is exactly hi + mid + lo with three bf16 planes (8 + 8 + 8 significand bits):
+//   hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid)      (round to nearest even; both subtractions are exact)
+// and a bf16 x bf16 product is exact in the fp32 accumulator of the MFMA.  With the planes numbered 0 / 1 / 2:
+//   bf16x6: the six plane products with i + j <= 2 -- a*b to about 2^-25 relative, below the fp32 accumulation's own rounding;
+//   bf16x3: the three with i + j <= 1               -- at most 2^-17 + 2^-17 + 2^-18 < 1.25 * 2^-16 relative per product.
+// One fp32 accumulator per output tile; inside a 16-channel K step the small products go first
+// (lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi).
+//
+// Geometry is the LDS-halo kernel's (conv_igemm.hip: conv_halo_body): the flat NHWC pixel range of a 128*MT-row output
+// tile widened by W + 1 pixels on both sides is staged ONCE per 32-channel chunk and read at nine row shifts; a lane whose
+// shift leaves the image reads a row of zeros.  THE SPLIT HAPPENS WHILE STAGING: global fp32 -> registers -> planes ->
+// LDS, for the input patch once per chunk and for the (32*NT) x 32 weight tile once per tap (double buffered), so the
+// tap loop holds ds_read_b128 fragment reads and MFMAs plus the staging of the NEXT weight tile, and no HBM buffer is
+// added.  bf16x6 stages three planes per operand (6 B per element), bf16x3 two (4 B).
+// LDS image: one row per pixel / output channel = [plane 0: 32 bf16 | plane 1 | (plane 2) | 16 B pad], i.e. a pitch of
+// 208 B (bf16x6) or 144 B (bf16x3) = 52 / 36 banks: the 16 lanes of a ds_read_b128 pass (consecutive rows, same column)
+// start on 16 distinct multiples of 4 banks -- conflict free, like the fp32 tiles' 36-float pitch.
+// Fragments (cdna_hip_programming.md section 3): lane l holds A[row l & 31][k = 8 (l >> 5) + j] and
+// B[k = 8 (l >> 5) + j][col l & 31], j = 0..7: one 16-B read at byte (plane * 64 + kstep * 32 + (l >> 5) * 16) of the
+// row.  C/D is laid out as the fp32 MFMA's, so the epilogue is the fp32 kernels' (tbn_conv_dev.h).
+// Tiles: MT in {1, 2} x NT in {1..4} as the LDS-halo kernel; the largest, <2,4> bf16x6 at W = 64, needs 134 KB of LDS.
+// Subnormals: the lo plane of an input below about 2^-110 is a bf16 subnormal and the guides do not say whether the
+// bf16 MFMA flushes subnormal A/B inputs; the absolute error that could cause is < 2^-126 per product.  A value that
+// rounds to a bf16 infinity (|x| > 3.39e38) gives NaN planes, where the fp32 kernel would return an infinity.
+#include <cstdio>
+#include <cstring>
+
+#include "tbn_common.h"
+#include "tbn_kernels.h"
+#include "tbn_conv_dev.h"
+
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// planes of four fp32 values -> 8 B each at dst + plane * 64
+template <int P>
+__device__ __forceinline__ void bf16x_split_store(char* dst, const float4 v4) {
+  f32x4 r = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+  for (int pl = 0; pl < P; ++pl) {
+    const bf16x4 b = __builtin_convertvector(r, bf16x4);   // round to nearest even (v_cvt_pk_bf16_f32)
+    *reinterpret_cast<bf16x4*>(dst + pl * 64) = b;
+    if (pl + 1 < P) r -= __builtin_convertvector(b, f32x4);   // exact
+  }
+}
+
+// NP = plane products (6 | 3); EPI 0 plain (+bias, optional ReLU / accumulate) | 2 eval-BN fold + ReLU
+template <int NP, int MT, int NT, int EPI>
+__global__ __launch_bounds__(256) void conv_bf16x_kernel(ConvP p) {
+  extern __shared__ __attribute__((aligned(16))) float dyn_lds[];
+  constexpr int P = NP == 6 ? 3 : 2;
+  constexpr int PITCH = P * 64 + 16;   // bytes per LDS row
+  constexpr int BM = 128 * MT, BN = 32 * NT;
+  constexpr int NJ = (BM + 2 * 64 + 2 + 31) / 32;   // float4 slots per thread for a halo of up to W = 64
+  const int bid = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nb = p.tiles_m * p.tiles_n;
+  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, idx = bid >> 3;   // the tiles of an activation row panel share an XCD
+  const int nid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+  const int tm = nid / p.tiles_n, tn = nid - tm * p.tiles_n;
+  const int m0 = tm * BM, n0 = tn * BN;
+  const int W = p.W, HR = BM + 2 * W + 2;   // halo rows; row HR is the zero row
+  char* As = reinterpret_cast<char*>(dyn_lds);
+  char* Bs0 = As + (HR + 1) * PITCH;
+
+  const i32x4 in_rsrc = make_rsrc(p.in, p.in_bytes);
+  const i32x4 wt_rsrc = make_rsrc(p.wt, p.wt_bytes);
+  const int c4 = tid & 7, r0 = tid >> 3;
+  const int lrow = lane & 31, lhalf = lane >> 5;
+
+  // per-lane LDS byte address of each tap's A fragment row (or the zero row)
+  unsigned fa_off[MT][9];
+#pragma unroll
+  for (int i = 0; i < MT; ++i) {
+    const int lr = wave * 32 * MT + i * 32 + lrow;
+    const int m = m0 + lr;
+    const uint32_t n = fdiv((uint32_t)m, p.div_ohw);
+    const uint32_t rem = (uint32_t)m - n * p.div_ohw.d;
+    const int y = (int)fdiv(rem, p.div_ow);
+    const int x = (int)rem - y * W;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      const int dy = t / 3 - 1, dx = t % 3 - 1;
+      const bool ok = (m < p.M) && ((unsigned)(y + dy) < (unsigned)p.H) && ((unsigned)(x + dx) < (unsigned)W);
+      const int row = ok ? lr + (W + 1) + dy * W + dx : HR;
+      fa_off[i][t] = (unsigned)(row * PITCH + lhalf * 16);
+    }
+  }
+  unsigned fb_off[NT];
+#pragma unroll
+  for (int j = 0; j < NT; ++j) fb_off[j] = (unsigned)((j * 32 + lrow) * PITCH + lhalf * 16);
+
+  // halo slot j of this thread: row (tid >> 3) + 32 j, channels 4 c4 .. 4 c4 + 3 of the chunk
+  const int pix0 = m0 - (W + 1) + r0;
+  float4 ha[NJ];
+  auto load_halo = [&](int c0) {
+    const unsigned soff = (unsigned)c0 * 4u;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int h = r0 + 32 * j, pix = pix0 + 32 * j;
+      const bool ok = (h < HR) && ((unsigned)pix < (unsigned)p.M);
+      ha[j] = buf_load4(in_rsrc, ok ? (unsigned)pix * (unsigned)p.in_ld * 4u + (unsigned)c4 * 16u : TBN_OOB, soff);
+    }
+  };
+  auto store_halo = [&]() {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+      if (r0 + 32 * j < HR) bf16x_split_store<P>(As + (r0 + 32 * j) * PITCH + c4 * 8, ha[j]);
+  };
+  float4 rb[NT];
+  unsigned b_voff[NT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i)
+    b_voff[i] = (unsigned)(n0 + r0 + 32 * i) * (unsigned)p.Krow * 4u + (unsigned)c4 * 16u;   // rows >= Cout: beyond wt_bytes
+  auto load_b = [&](int t, int c0) {
+    const unsigned koff = (unsigned)(t * p.Cin + c0) * 4u;
+#pragma unroll
+    for (int i = 0; i < NT; ++i) rb[i] = buf_load4(wt_rsrc, b_voff[i], koff);
+  };
+  auto store_b = [&](char* Bs) {
+#pragma unroll
+    for (int i = 0; i < NT; ++i) bf16x_split_store<P>(Bs + (r0 + 32 * i) * PITCH + c4 * 8, rb[i]);
+  };
+
+  f32x16 acc[MT][NT];
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+  // prologue: zero row, halo of chunk 0, B tile of (tap 0, chunk 0)
+  load_halo(0);
+  load_b(0, 0);
+  if (tid < PITCH / 4) reinterpret_cast<float*>(As + HR * PITCH)[tid] = 0.f;
+  store_halo();
+  store_b(Bs0);
+  __syncthreads();
+
+  const int nchunks = p.Cin >> 5;
+  int ks = 0;
+  for (int c = 0; c < nchunks; ++c) {
+    const bool next = c + 1 < nchunks;
+    if (next) load_halo((c + 1) * 32);   // waits in registers until every wave is past this chunk's last tap
+#pragma unroll
+    for (int t = 0; t < 9; ++t, ++ks) {
+      const bool more = next || t < 8;
+      if (more) load_b(t < 8 ? t + 1 : 0, t < 8 ? c * 32 : (c + 1) * 32);
+      const char* Bs = Bs0 + (ks & 1) * (BN * PITCH);
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {   // two K steps of 16 channels
+        bf16x8 fa[MT][P], fb[NT][P];
+#pragma unroll
+        for (int pl = 0; pl < P; ++pl) {
+#pragma unroll
+          for (int i = 0; i < MT; ++i) fa[i][pl] = *reinterpret_cast<const bf16x8*>(As + fa_off[i][t] + pl * 64 + s * 32);
+#pragma unroll
+          for (int j = 0; j < NT; ++j) fb[j][pl] = *reinterpret_cast<const bf16x8*>(Bs + fb_off[j] + pl * 64 + s * 32);
+        }
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+          for (int i = 0; i < MT; ++i) {
+            if (NP == 6) {
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][P - 1], fb[j][0], acc[i][j], 0, 0, 0);   // lo * hi
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][P - 1], acc[i][j], 0, 0, 0);   // hi * lo
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][1], acc[i][j], 0, 0, 0);       // mid * mid
+            }
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][0], acc[i][j], 0, 0, 0);         // mid * hi
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][1], acc[i][j], 0, 0, 0);         // hi * mid
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][0], acc[i][j], 0, 0, 0);         // hi * hi
+          }
+      }
+      // the other stage was last read in the previous tap: every wave is past that tap's barrier
+      if (more) store_b(Bs0 + ((ks + 1) & 1) * (BN * PITCH));
+      __syncthreads();
+    }
+    if (next) {   // every wave is past its last read of this chunk's halo (barrier above)
+      store_halo();
+      __syncthreads();
+    }
+  }
+  conv_epilogue<MT, NT, EPI, false>(p, acc, dyn_lds, tm, m0, n0);
+}
+
+// ---------------------------------------------------------------------------------------------- host side
+// LDS bytes of the split-bf16 kernel; 0 if the shape is not a 3x3 / stride 1 / pad 1 layer it handles
+size_t tbn_conv_bf16x_lds_bytes(const ConvP& p, int np, int mt, int nt) {
+  if (p.R != 3 || p.S != 3 || p.stride != 1 || p.pad != 1 || p.up != 1 || p.OH != p.H || p.OW != p.W || p.W > 64 ||
+      p.Cin % 32 != 0)
+    return 0;
+  const size_t pitch = (np == 6 ? 3 : 2) * 64 + 16;
+  return (size_t)(128 * mt + 2 * p.W + 3 + 2 * 32 * nt) * pitch;
+}
+
+// Tile heuristic: the cost model of tbn_conv_pick_tile with the MFMA cycles of this kernel -- per 32-channel K step
+// and 32 x 32 sub-tile 2 * np instructions of 32 cycles (fp32 kernel: 16 of 64) -- so the fixed per-step cost weighs
+// more and larger tiles win earlier.  The 350 / 4000 cycle constants are the fp32 kernel's; for this kernel the model is
+// NOT measured (the <2,3> / <2,4> tiles it prefers for large M run at 256+ VGPRs, one wave per SIMD).
+void tbn_conv_bf16x_pick_tile(int M, int Cout, int K, int np, int* mt_out, int* nt_out) {
+  double best = 1e300;
+  int bm = 1, bn = 1;
+  for (int mt = 1; mt <= 2; ++mt)
+    for (int nt = 1; nt <= 4; ++nt) {
+      const double blocks = (double)cdiv(M, 128 * mt) * cdiv(Cout, 32 * nt);
+      const double rounds = (double)((long)((blocks + 255) / 256));
+      const double per_block = (K / 32.0) * (mt * nt * 64.0 * np + 350.0) + 4000.0;
+      const double cost = rounds * per_block * (1.0 + 0.01 / (mt * nt));   // bigger tiles on ties (less L2 traffic)
+      if (cost < best) {
+        best = cost;
+        bm = mt;
+        bn = nt;
+      }
+    }
+  *mt_out = bm;
+  *nt_out = bn;
+}
+
+template <int NP, int MT, int NT, int EPI>
+static int launch_bf16x_e(const ConvP& p, int grid, size_t lds_bytes, hipStream_t st) {
+  static size_t allowed = 64 * 1024;   // per instantiation: raise the dynamic-LDS limit once when a shape needs it
+  if (lds_bytes > allowed) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16x_kernel<NP, MT, NT, EPI>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+      tbn_set_error("conv_bf16x: cannot raise the dynamic LDS limit");
+      return TBN_ERR_LAUNCH;
+    }
+    allowed = 160 * 1024;
+  }
+  TBN_LAUNCH((conv_bf16x_kernel<NP, MT, NT, EPI>), dim3(grid), dim3(256), lds_bytes, st, p);
+  return TBN_OK;
+}
+template <int MT, int NT>
+static int launch_bf16x(const ConvP& p, int np, int grid, size_t lds_bytes, hipStream_t st) {
+  if (np == 6)
+    return p.mode == CONV_EPI_EVAL ? launch_bf16x_e<6, MT, NT, 2>(p, grid, lds_bytes, st)
+                                   : launch_bf16x_e<6, MT, NT, 0>(p, grid, lds_bytes, st);
+  return p.mode == CONV_EPI_EVAL ? launch_bf16x_e<3, MT, NT, 2>(p, grid, lds_bytes, st)
+                                 : launch_bf16x_e<3, MT, NT, 0>(p, grid, lds_bytes, st);
+}
+
+#define TBN_BF16X_REFUSE(cond, code, ...) \
+  do {                                    \
+    if (cond) {                           \
+      tbn_set_error(__VA_ARGS__);         \
+      return code;                        \
+    }                                     \
+  } while (0)
+
+// `p` prepared by the caller (derived geometry filled, a single GEMM); mt, nt <= 0: heuristic tile
+int tbn_launch_conv_bf16x(ConvP& p, int rowmode, int mt, int nt, double alg_bytes, hipStream_t st, const RiderP* rider) {
+  const int both = CONV_FLAG_BF16X6 | CONV_FLAG_BF16X3;
+  TBN_BF16X_REFUSE((p.flags & both) == both, TBN_ERR_ARG, "conv: bf16x6 and bf16x3 (flags 32 | 64) are exclusive");
+  const int np = (p.flags & CONV_FLAG_BF16X6) ? 6 : 3;
+  TBN_BF16X_REFUSE(p.flags & (CONV_FLAG_HALO | CONV_FLAG_DMA | CONV_FLAG_SK4), TBN_ERR_ARG,
+                   "conv: the bf16x%d flag selects its own kernel: not with variant flags 4 / 8 / 16", np);
+  TBN_BF16X_REFUSE(p.mode == CONV_EPI_STATS || p.nred > 0 || rider != nullptr, TBN_ERR_UNSUPPORTED,
+                   "conv: the bf16x%d kernel has no training-statistics / reduce epilogue and hosts no rider (eval forward only)", np);
+  TBN_BF16X_REFUSE(rowmode || tbn_conv_bf16x_lds_bytes(p, np, 1, 1) == 0, TBN_ERR_UNSUPPORTED,
+                   "conv: the bf16x%d kernel handles 3x3 / stride 1 / pad 1 layers on maps at most 64 wide (got %dx%d stride %d pad %d, width %d)",
+                   np, p.R, p.S, p.stride, p.pad, p.W);
+  if (mt <= 0 || nt <= 0) tbn_conv_bf16x_pick_tile(p.M, p.Cout, p.K, np, &mt, &nt);
+  TBN_BF16X_REFUSE(mt > 2 || nt > 4, TBN_ERR_UNSUPPORTED, "conv: unsupported bf16x%d tile %dx%d", np, mt, nt);
+  const size_t lds_bytes = tbn_conv_bf16x_lds_bytes(p, np, mt, nt);
+  TBN_BF16X_REFUSE(lds_bytes > 160 * 1024, TBN_ERR_UNSUPPORTED, "conv: bf16x%d tile %dx%d needs %zu B of LDS", np, mt, nt, lds_bytes);
+  p.tiles_m = cdiv(p.M, 128 * mt);
+  p.tiles_n = cdiv(p.Cout, 32 * nt);
+  const int grid = p.tiles_m * p.tiles_n;
+  char nm[64];
+  snprintf(nm, sizeof(nm), "conv_bf16x%d_kernel<%d, %d, %d>", np, mt, nt, p.mode == CONV_EPI_EVAL ? 2 : 0);
+  tbn_prof_begin(nm, p.alg_flops, st, alg_bytes);
+  int rc = TBN_ERR_UNSUPPORTED;
+#define TBN_XCASE(MTv, NTv) \
+  if (mt == MTv && nt == NTv) rc = launch_bf16x<MTv, NTv>(p, np, grid, lds_bytes, st);
+  TBN_XCASE(1, 1) TBN_XCASE(1, 2) TBN_XCASE(1, 3) TBN_XCASE(1, 4) TBN_XCASE(2, 1) TBN_XCASE(2, 2) TBN_XCASE(2, 3) TBN_XCASE(2, 4)
+#undef TBN_XCASE
+  tbn_prof_end(st);
+  if (rc != TBN_OK) return rc;
+  TBN_CHECK_LAUNCH("conv_bf16x");
+  return TBN_OK;
+}

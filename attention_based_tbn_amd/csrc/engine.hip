@@ -1230,6 +1230,8 @@ int tbn_backbone_forward(const tbn_backbone_plan* P, int training, const float* 
   TBN_REQUIRE(P && x_nchw && prm && workspace && features_out, "backbone_forward: null argument");
   TBN_REQUIRE(workspace_bytes >= tbn_backbone_workspace_bytes(P, training), "backbone_forward: workspace too small");
   TBN_REQUIRE(((uintptr_t)workspace & 255) == 0, "backbone_forward: workspace must be 256-B aligned");
+  TBN_REQUIRE((prm->flags & (TBN_BACKBONE_CONV_BF16X6 | TBN_BACKBONE_CONV_BF16X3)) != (TBN_BACKBONE_CONV_BF16X6 | TBN_BACKBONE_CONV_BF16X3),
+              "backbone_forward: TBN_BACKBONE_CONV_BF16X6 and _BF16X3 (bf16x math modes) are exclusive");
   float* ws = (float*)workspace;
   const int R = P->frames;
   const int tr = training ? 1 : 0;   // index of the forward launch choices (Conv::ft)
@@ -1290,6 +1292,15 @@ int tbn_backbone_forward(const tbn_backbone_plan* P, int training, const float* 
       }
     }
   };
+  // TBN_BACKBONE_CONV_BF16X6 / _BF16X3 (eval forward only): every 3x3 / stride 1 / pad 1 layer on a map at most 64 wide goes
+  // through the split-bf16 kernel as a single launch with the eval epilogue; its tile is the layer's tuned LDS-halo tile
+  // where the plan holds one (same geometry), else that kernel's size heuristic.  The plan is not touched.
+  const int bf16x_flag = training ? 0
+                                  : ((prm->flags & TBN_BACKBONE_CONV_BF16X6) ? CONV_FLAG_BF16X6
+                                                                             : ((prm->flags & TBN_BACKBONE_CONV_BF16X3) ? CONV_FLAG_BF16X3 : 0));
+  auto bf16x_layer = [&](const Conv& c) {
+    return bf16x_flag != 0 && !c.stem && c.k == 3 && c.stride == 1 && c.pad == 1 && c.inW <= 64 && c.cin % 32 == 0;
+  };
   const hipStream_t st_main = st;
   // riders: one-chain training program only; off while the profiler brackets the conv launches (a rider's time would be
   // charged to its host GEMM)
@@ -1310,13 +1321,19 @@ int tbn_backbone_forward(const tbn_backbone_plan* P, int training, const float* 
     if (o.kind == OP_CONV) {
       const Conv& c = P->convs[o.idx];
       const Conv::FwdTune& T = c.ft[tr];
-      if (!br && c.pair_prev >= 0 && P->convs[c.pair_prev].ft[tr].pair) continue;   // ran with its sibling
+      if (!br && c.pair_prev >= 0 && P->convs[c.pair_prev].ft[tr].pair &&
+          !(bf16x_layer(c) || bf16x_layer(P->convs[c.pair_prev])))
+        continue;   // ran with its sibling
       const RiderP* rd = (pend_host == o.idx) ? &pend_rider : nullptr;
       if (rd != nullptr) {
         pend_host = -1;
         ++PM->rider_launches[0];
       }
-      if (!br && c.pair_next >= 0 && T.pair) {
+      const bool bx = bf16x_layer(c);
+      // a sibling pair with a split-bf16 member is issued as its two single launches (as branch mode does)
+      const bool pair_bx = bx || (c.pair_next >= 0 && bf16x_layer(P->convs[c.pair_next])) ||
+                           (c.pair_prev >= 0 && bf16x_layer(P->convs[c.pair_prev]));
+      if (!br && !pair_bx && c.pair_next >= 0 && T.pair) {
         const Conv& c2 = P->convs[c.pair_next];
         ConvP pa, pb;
         fwd_params(c, pa);
@@ -1351,6 +1368,12 @@ int tbn_backbone_forward(const tbn_backbone_plan* P, int training, const float* 
           p.seg[i].col_begin = q.col0;
           if (q.pooled) p.raw_seg1 = i + 1;
         }
+      }
+      if (bx) {
+        p.flags |= bf16x_flag;
+        p.halo = 0;
+        TBN_TRY(tbn_launch_conv(p, 0, T.halo == 1 ? T.mt : 0, T.halo == 1 ? T.nt : 0, st, nullptr));
+        continue;
       }
       TBN_TRY(tbn_launch_conv(p, c.stem, T.mt, T.nt, st, rd));
     } else if (o.kind == OP_PREPOOL) {

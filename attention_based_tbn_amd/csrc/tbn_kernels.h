@@ -9,7 +9,9 @@ enum {
   CONV_FLAG_RELU = 2,
   CONV_FLAG_HALO = 4,   // host only: use the LDS-halo kernel
   CONV_FLAG_DMA = 8,    // host only: use the LDS-DMA staging kernel
-  CONV_FLAG_SK4 = 16    // host only: 32-row tiles whose four waves split K (small-M launches)
+  CONV_FLAG_SK4 = 16,   // host only: 32-row tiles whose four waves split K (small-M launches)
+  CONV_FLAG_BF16X6 = 32,   // host only: split-bf16 kernel (conv_bf16x.hip), six plane products
+  CONV_FLAG_BF16X3 = 64    // host only: the same with three plane products
 };
 
 // BN-backward reduce fused into a data-gradient epilogue (the launch that writes the FINAL value of dz): for the output
@@ -160,6 +162,11 @@ int tbn_launch_conv(ConvP p, int rowmode, int mt, int nt, hipStream_t st, const 
 int tbn_launch_conv_pair(ConvP a, ConvP b, int variant, int mt, int nt, hipStream_t st, const RiderP* rider = nullptr);
 int tbn_conv_red_rows(int N, int OH, int OW, int up, int tile_rows);   // tile_rows = M rows per workgroup tile (128 * mt; 32 * mt for the split-K tile kernel)
 size_t tbn_conv_halo_lds_bytes(const ConvP& p, int mt, int nt);   // 0: shape not handled by the LDS-halo kernel
+// conv_bf16x.hip: 3x3 / stride 1 / pad 1 forward on the bf16 MFMA (np = 6 | 3 plane products); tbn_launch_conv routes a
+// launch whose flags carry CONV_FLAG_BF16X6 / _BF16X3 there and refuses what that kernel does not cover
+size_t tbn_conv_bf16x_lds_bytes(const ConvP& p, int np, int mt, int nt);   // 0: shape not handled
+void tbn_conv_bf16x_pick_tile(int M, int Cout, int K, int np, int* mt, int* nt);
+int tbn_launch_conv_bf16x(ConvP& p, int rowmode, int mt, int nt, double alg_bytes, hipStream_t st, const RiderP* rider);
 void tbn_wgrad_plan(int M, int Cout, int Cin, int taps, int* mt, int* nt, int* splits, int* rows_per_split);
 size_t tbn_wgrad_workspace_floats(int M, int Cout, int Cin, int taps);
 int tbn_launch_wgrad(WgradP p, int rowmode, float* dw, float* workspace, hipStream_t st);

@@ -30,6 +30,13 @@ extern "C" {
 /* library version in the low 16 bits; bit 16 (0x10000) is set by a -DTBN_EXPERIMENT=1 build, the only build that reads
  * A/B environment knobs (the shipped library reads no environment variable at all) */
 int tbn_version(void);
+/* Feature bits of this build, for callers that bind the C-ABI directly: flag bits a library does not know are ignored by
+ * its launchers, so ask before relying on one.  TBN_CAP_CONV_BF16X: the split-bf16 convolution math (flags 32 / 64 of
+ * tbn_conv2d_fwd / tbn_conv_desc, TBN_BACKBONE_CONV_BF16X6 / _BF16X3) is honoured.  The low 16 bits of tbn_version() name
+ * the plan-cache format (TBN_PLAN_CACHE file names, the committed bench plans) and do not move with added features; a
+ * library without this symbol has none of them.  Replaces nothing in the reference. */
+#define TBN_CAP_CONV_BF16X 1
+int tbn_capabilities(void);
 const char* tbn_last_error(void);
 
 /* measurement aid (bench.py roofline): while enabled, every conv-GEMM launch (forward / data-grad /
@@ -103,6 +110,18 @@ typedef struct {
                                             workspace are current (tbn_backbone_flip_weights ran on this workspace, on the same
                                             stream, after the matching forward and the weights have not changed since): the pass
                                             does not launch the flip itself */
+#define TBN_BACKBONE_CONV_BF16X6 8       /* tbn_backbone_forward(training = 0) only: split-bf16 convolution math.  Every conv of the
+                                            plan that is 3x3 / stride 1 / pad 1 with cin a multiple of 32 on a map at most 64 wide (in this
+                                            graph: every 3x3 / stride 1 layer, cin 64 ... 192) runs on the bf16 MFMA with
+                                            six plane products (tbn_conv2d_fwd flag 32: fp32 in / out, error below the fp32
+                                            accumulation's own) and the eval epilogue, as a single launch with the layer's tuned
+                                            LDS-halo tile or a size heuristic; every other layer, and every layer when training = 1,
+                                            runs exactly as without the flag.  The plan blob, its size and fingerprint and the
+                                            workspace size do not depend on it; tbn_backbone_autotune / _backward ignore it.
+                                            replaces: the 3x3 nn.Conv2d forwards of core/models/bn_inception_audio.py:24-401 under
+                                            model.eval() / torch.no_grad() (core/tools/test.py:67-87) */
+#define TBN_BACKBONE_CONV_BF16X3 16      /* the same with three plane products (flag 64: relative error < 1.25 * 2^-16 per product);
+                                            exclusive with TBN_BACKBONE_CONV_BF16X6 (both: TBN_ERR_ARG) */
 
 typedef struct {
   float* dweight;             /* same layout as weight; fully overwritten */
@@ -219,7 +238,14 @@ int tbn_backbone_flip_weights(const tbn_backbone_plan* plan, const tbn_backbone_
  * flags also selects the kernel variant (test / tuning aid; 0 = generic): 4 = LDS-halo (3x3 / stride 1 / pad 1 only),
  * 8 = LDS-DMA staging, 16 = 32-row tiles whose four waves split K (statistics partial rows are then per 32*mt output
  * rows, tiles mt, nt in {1,2}).  Without a variant flag, epilogue-0 / -2 launches of at most 128 tiles and k*k*cin >= 256
- * (the head Linear layers, M = 96 rows) take the split-K tile kernel by themselves; every variant is deterministic. */
+ * (the head Linear layers, M = 96 rows) take the split-K tile kernel by themselves; every variant is deterministic.
+ * Split-bf16 math (opt-in; replaces the same nn.Conv2d forward under model.eval() / torch.no_grad(), reference
+ * core/tools/test.py:67-87): flag 32 = bf16x6, 64 = bf16x3.  fp32 operands are split into three / two bf16 planes while they
+ * are staged into LDS and the six (i + j <= 2) / three (i + j <= 1) plane products run on v_mfma_f32_32x32x16_bf16 into one
+ * fp32 accumulator: bf16x6 reproduces a * b to about 2^-25 relative, bf16x3 to < 1.25 * 2^-16.  3x3 / stride 1 / pad 1, map
+ * width <= 64, epilogue 0 or 2, tiles mt in {1,2} x nt in {1..4} only: any other geometry, epilogue 1, a data gradient, a
+ * pair launch, both bits, or a combination with 4 / 8 / 16 fails with TBN_ERR_UNSUPPORTED / TBN_ERR_ARG and a message naming
+ * bf16x -- never a silent fp32 launch.  The profiler keys these launches as conv_bf16x6_kernel<..> / conv_bf16x3_kernel<..>. */
 int tbn_conv2d_fwd(const float* in, int in_ld, const float* weight, const float* bias, float* out, int out_ld,
                    int n, int h, int w, int cin, int cout, int ksize, int stride, int pad, int epilogue, int flags,
                    const float* scale, const float* shift, float* stat_partial, void* stream);
@@ -257,7 +283,8 @@ typedef struct {
   int n, h, w, cin, cout, ksize, stride, pad;   /* geometry of the FORWARD convolution */
   int dgrad;              /* 0: forward, 1: data gradient of that convolution (workspace: cout*k*k*cin floats) */
   int epilogue;           /* forward: 0 / 1 / 2 as tbn_conv2d_fwd; data gradient: 0 */
-  int flags;              /* 1 accumulate, 2 ReLU; kernel variant 4 LDS-halo, 8 LDS-DMA, 16 split-K tile (0 generic) */
+  int flags;              /* 1 accumulate, 2 ReLU; kernel variant 4 LDS-halo, 8 LDS-DMA, 16 split-K tile (0 generic);
+                             32 bf16x6 / 64 bf16x3 split-bf16 math (forward, epilogue 0 / 2; see tbn_conv2d_fwd) */
   int stages;             /* generic kernel: LDS stages 1 / 2 (0 = default) */
   const float* scale;     /* epilogue 2 */
   const float* shift;
