@@ -25,7 +25,8 @@ class ConvInfo(C.Structure):
 
 class BackboneParams(C.Structure):
     _fields_ = [("weight", c_fp), ("bias", c_fp), ("gamma", c_fp), ("beta", c_fp), ("running_mean", c_fp),
-                ("running_var", c_fp), ("momentum", c_f), ("eps", c_f), ("side_stream", c_fp), ("flags", c_i)]
+                ("running_var", c_fp), ("momentum", c_f), ("eps", c_f), ("side_stream", c_fp), ("flags", c_i),
+                ("weight_planes", c_fp)]
 
 
 BUCKET_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.c_size_t)   # tbn_backbone_grads.bucket_cb(user, first_float, num_floats)
@@ -47,7 +48,7 @@ class ConvDesc(C.Structure):
                 ("n", c_i), ("h", c_i), ("w", c_i), ("cin", c_i), ("cout", c_i), ("ksize", c_i), ("stride", c_i),
                 ("pad", c_i), ("dgrad", c_i), ("epilogue", c_i), ("flags", c_i), ("stages", c_i), ("scale", c_fp),
                 ("shift", c_fp), ("stat_partial", c_fp), ("nred", c_i), ("red", ConvRed * 4), ("red_stats", c_fp),
-                ("red_stats_stride", c_i)]
+                ("red_stats_stride", c_i), ("out2", c_fp), ("out2_ld", c_i), ("out2_col_begin", c_i), ("out2_raw", c_i)]
 
 
 class OptTensor(C.Structure):
@@ -87,12 +88,16 @@ SIGNATURES = {
     "tbn_backbone_plan_fingerprint": (C.c_ulonglong, [C.c_void_p]),
     "tbn_backbone_forward": (c_i, [C.c_void_p, c_i, c_fp, C.POINTER(BackboneParams), c_fp, c_sz,
                                    C.POINTER(C.c_void_p), c_fp]),
+    "tbn_backbone_weight_planes_bytes": (c_sz, [C.c_void_p, c_i]),
+    "tbn_backbone_split_weights": (c_i, [C.c_void_p, c_fp, c_i, c_fp, c_fp]),
     "tbn_backbone_autotune": (c_i, [C.c_void_p, c_i, C.POINTER(BackboneParams), c_fp, c_sz, c_fp]),
     "tbn_backbone_backward": (c_i, [C.c_void_p, c_fp, C.POINTER(BackboneParams), C.POINTER(BackboneGrads), c_fp,
                                     c_sz, c_fp]),
     "tbn_backbone_flip_weights": (c_i, [C.c_void_p, C.POINTER(BackboneParams), c_fp, c_sz, c_fp]),
     "tbn_conv2d_fwd": (c_i, [c_fp, c_i, c_fp, c_fp, c_fp, c_i] + [c_i] * 10 + [c_fp, c_fp, c_fp, c_fp]),
     "tbn_conv2d_stat_tiles": (c_i, [c_i] * 8),
+    "tbn_conv_weight_planes_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "tbn_conv_split_weights": (c_i, [c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp]),
     "tbn_conv2d_fwd_tile": (c_i, [c_fp, c_i, c_fp, c_fp, c_fp, c_i] + [c_i] * 10 + [c_fp, c_i, c_i, c_fp]),
     "tbn_conv2d_dgrad": (c_i, [c_fp, c_i, c_fp, c_fp, c_i] + [c_i] * 9 + [c_fp, c_fp]),
     "tbn_conv_partial_rows": (c_i, [C.POINTER(ConvDesc), c_i, c_i]),

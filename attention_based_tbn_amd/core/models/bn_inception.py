@@ -167,6 +167,8 @@ class _BackboneFn(torch.autograd.Function):
         beta = torch.cat([b0, b1]) if b1.numel() else b0
         prm = BackboneParams(ptr(weight), ptr(bias), ptr(gamma), ptr(beta), ptr(module.running_mean),
                              ptr(module.running_var), 0.1, 1e-5, module._side_stream_ptr(), module._engine_flags())
+        if module._planes_on():
+            prm.weight_planes = ptr(module._weight_planes(plan))
         feat_ptr = C.c_void_p()
         st = stream_ptr()
         sync = module.plan_sync
@@ -318,6 +320,12 @@ class BNInception(nn.Module):
         # layers on the bf16 MFMA with the fp32 operands split into bf16 planes: include/tbn_hip.h TBN_BACKBONE_CONV_BF16X6 /
         # _BF16X3).  Ignored in training mode; not part of state_dict
         self._conv_math = "f32"
+        # which layers the bf16x modes cover: "3x3" (the 3x3 / stride 1 layers, weights split inside the kernel) | "all" (also
+        # every 1x1 / stride 1 GEMM, weights pre-split ONCE into bf16 planes this module owns: TBN_BACKBONE_CONV_BF16X_ALL).
+        # Ignored in training mode and with conv_math "f32"; not part of state_dict
+        self._conv_math_layers = "3x3"
+        self._planes = None             # uint8 tensor of weight planes ("all" only) and what it was split from:
+        self._planes_key = None         # (flat_weight.data_ptr(), flat_weight._version, conv_math)
         self._last_flip = None          # weak reference to the last training forward's _Flip (flip_weights_early)
         self._out_slot = None       # set by TBNModel for one forward: where the pooled (frames, 1024) feature is to be written
         self.plan_sync = None       # data parallel: object with is_source() / check(key, device) / broadcast(blob, device)
@@ -363,6 +371,7 @@ class BNInception(nn.Module):
                 nn.init.kaiming_uniform_(w, a=5 ** 0.5)
                 bound = 1.0 / (L["cin"] * L["k"] * L["k"]) ** 0.5
                 self.flat_bias[L["c_off"]:L["c_off"] + L["cout"]].uniform_(-bound, bound)
+            torch.autograd.graph.increment_version(self.flat_weight)   # conv_weight() views write through `.data`
 
     def conv_weight(self, name):
         """OIHW view (channels_last memory) of one conv's weights inside the flat buffer"""
@@ -427,6 +436,9 @@ class BNInception(nn.Module):
                                       f"from checkpoint, the shape in current model is {tuple(dst.shape)}.")
                     continue
                 dst.copy_(src)
+            # the copies went through `.data` views: tell every cache keyed on the parameter's `_version` (the weight planes
+            # of conv_math_layers "all") that the flat weights changed
+            torch.autograd.graph.increment_version(self.flat_weight)
         if strict:
             child_prefixes = tuple(prefix + n + "." for n, _ in self.named_children())
             for key in state_dict:
@@ -481,11 +493,51 @@ class BNInception(nn.Module):
         if value not in self.CONV_MATH:
             raise ValueError("conv_math must be one of %s, got %r" % (", ".join(map(repr, self.CONV_MATH)), value))
         self._conv_math = value
+        if value == "f32":
+            self._planes = self._planes_key = None
+
+    CONV_MATH_LAYERS = ("3x3", "all")
+
+    @property
+    def conv_math_layers(self):
+        return self._conv_math_layers
+
+    @conv_math_layers.setter
+    def conv_math_layers(self, value):
+        if value not in self.CONV_MATH_LAYERS:
+            raise ValueError("conv_math_layers must be one of %s, got %r"
+                             % (", ".join(map(repr, self.CONV_MATH_LAYERS)), value))
+        self._conv_math_layers = value
+        if value != "all":
+            self._planes = self._planes_key = None
+
+    def _planes_on(self):
+        """the eval forward runs from pre-split weight planes (conv_math_layers "all" beside a bf16x math mode)"""
+        return not self.training and self._conv_math != "f32" and self._conv_math_layers == "all"
+
+    def _weight_planes(self, plan):
+        """the bf16 planes of flat_weight for the current math mode, split again (one HBM-bound launch on the current
+        stream) when the weights changed in place (`_version`), moved (`data_ptr`) or the mode changed; inside a stream
+        capture always, so that every replay of the graph splits the weights it then reads"""
+        w = self.flat_weight
+        np_ = 6 if self._conv_math == "bf16x6" else 3
+        key = (w.data_ptr(), w._version, self._conv_math)
+        nbytes = lib().tbn_backbone_weight_planes_bytes(plan.handle, np_)
+        if self._planes is None or self._planes.numel() != nbytes or self._planes.device != w.device:
+            self._planes, self._planes_key = torch.empty(nbytes, dtype=torch.uint8, device=w.device), None
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self._planes_key != key or capturing:
+            call("tbn_backbone_split_weights", plan.handle, ptr(w), np_, ptr(self._planes), stream_ptr())
+            # a captured split is only recorded, not executed: the key stays as it was, so that an eager forward before the
+            # first replay splits for itself instead of reading planes nobody has written
+            if not capturing:
+                self._planes_key = key
+        return self._planes
 
     def _engine_flags(self):
-        # TBN_BACKBONE_RIDERS | TBN_BACKBONE_STEM_WGRAD_LAST | the eval forward's convolution math
+        # TBN_BACKBONE_RIDERS | TBN_BACKBONE_STEM_WGRAD_LAST | the eval forward's convolution math (| _CONV_BF16X_ALL)
         return ((1 if self.use_riders else 0) | (2 if self.stem_wgrad_last else 0)
-                | (0 if self.training else self.CONV_MATH[self._conv_math]))
+                | (0 if self.training else self.CONV_MATH[self._conv_math]) | (32 if self._planes_on() else 0))
 
     def _side_stream_ptr(self):
         """the side stream that goes with the current stream (0: serial program; also while a graph is being captured --
@@ -533,7 +585,10 @@ class BNInception(nn.Module):
         if self.training:
             raise TbnHipError("features(): only available in eval mode; use forward() for training")
         prm = BackboneParams(ptr(self.flat_weight), ptr(self.flat_bias), ptr(gamma), ptr(beta),
-                             ptr(self.running_mean), ptr(self.running_var), 0.1, 1e-5, 0, self.CONV_MATH[self._conv_math])
+                             ptr(self.running_mean), ptr(self.running_var), 0.1, 1e-5, 0,
+                             self.CONV_MATH[self._conv_math] | (32 if self._planes_on() else 0))
+        if self._planes_on():
+            prm.weight_planes = ptr(self._weight_planes(plan))
         feat_ptr = C.c_void_p()
         call("tbn_backbone_forward", plan.handle, 0, ptr(x), C.byref(prm), ptr(ws), ws.numel(), C.byref(feat_ptr),
              stream_ptr())

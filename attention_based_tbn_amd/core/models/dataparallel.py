@@ -468,3 +468,11 @@ class DataParallel(nn.Module):
     @conv_math.setter
     def conv_math(self, value):
         self.module.conv_math = value
+
+    @property
+    def conv_math_layers(self):
+        return self.module.conv_math_layers
+
+    @conv_math_layers.setter
+    def conv_math_layers(self, value):
+        self.module.conv_math_layers = value

@@ -204,6 +204,16 @@ class TBNModel(nn.Module):
         for m in self.modality:
             getattr(self, "Base_{}".format(m)).conv_math = value
 
+    @property
+    def conv_math_layers(self):
+        """layers the bf16x math modes cover in every backbone's EVAL forward: "3x3" | "all" (BNInception.conv_math_layers)"""
+        return getattr(self, "Base_{}".format(self.modality[0])).conv_math_layers
+
+    @conv_math_layers.setter
+    def conv_math_layers(self, value):
+        for m in self.modality:   # (the first backbone validates before any is changed)
+            getattr(self, "Base_{}".format(m)).conv_math_layers = value
+
     def maybe_unused_parameter_prefixes(self):
         """parameters that may get no gradient in a step: with `data.audio.dropout > 0` the per-replica host draw of
         reference model.py:215-222 can drop the audio feature on one data-parallel rank and keep it on another --

@@ -272,7 +272,7 @@ extern "C" {
 
 int tbn_version(void) { return 102 | (TBN_EXPERIMENT ? 0x10000 : 0); }
 
-int tbn_capabilities(void) { return TBN_CAP_CONV_BF16X; }
+int tbn_capabilities(void) { return TBN_CAP_CONV_BF16X | TBN_CAP_CONV_BF16X_PLANES; }
 
 int tbn_diag_mfma_burst(float* sink, int workgroups, int iters, double* flops, void* stream) {
   TBN_REQUIRE(sink != nullptr && workgroups > 0 && workgroups <= 65536 && iters > 0, "diag_mfma_burst: bad argument");
@@ -428,7 +428,7 @@ static int desc_to_convp(const tbn_conv_desc* d, float* workspace, hipStream_t s
     p.stat_partial = d->stat_partial;
     p.mode = d->epilogue;
   } else {
-    if (d->flags & (CONV_FLAG_BF16X6 | CONV_FLAG_BF16X3)) {
+    if (d->flags & (CONV_FLAG_BF16X6 | CONV_FLAG_BF16X3 | CONV_FLAG_BF16X_PLANES)) {
       tbn_set_error("conv_launch: the bf16x kernels (flags 32 / 64) compute forward convolutions only, not dgrad = 1");
       return TBN_ERR_UNSUPPORTED;
     }
@@ -467,13 +467,44 @@ static int desc_to_convp(const tbn_conv_desc* d, float* workspace, hipStream_t s
       p.red[i].c_off = d->red[i].stat_offset;
     }
   }
-  p.flags = d->flags;
+  p.flags = d->flags & ~CONV_FLAG_DESC_OUT2;
   p.stages = d->stages;
   p.nseg = 1;
   p.seg[0].ptr = d->out;
   p.seg[0].ld = d->out_ld;
   p.seg[0].col_begin = 0;
+  // the out2* fields were appended to the struct: they are only read under flag 256, which a caller built against the
+  // shorter struct never sets
+  if (d->flags & CONV_FLAG_DESC_OUT2) {   // forward: the columns from out2_col_begin on go to a second destination
+    TBN_REQUIRE(d->out2 != nullptr && !d->dgrad && d->epilogue != CONV_EPI_STATS && d->out2_col_begin > 0 && d->out2_col_begin < d->cout,
+                "conv_launch: a second output segment belongs to a forward launch with epilogue 0 / 2 and starts inside (0, cout)");
+    p.nseg = 2;
+    p.seg[1].ptr = d->out2;
+    p.seg[1].ld = d->out2_ld;
+    p.seg[1].col_begin = d->out2_col_begin;
+    if (d->out2_raw && d->epilogue == CONV_EPI_EVAL) p.raw_seg1 = 2;
+  }
   return TBN_OK;
+}
+
+size_t tbn_conv_weight_planes_bytes(int cout, int ksize, int cin, int np) {
+  if (cout <= 0 || ksize <= 0 || cin <= 0 || cin % 32 != 0 || (np != 6 && np != 3)) return 0;
+  return tbn_bf16x_planes_bytes((size_t)cout * ksize * ksize * cin, np);
+}
+
+int tbn_conv_split_weights(const float* weight, int cout, int ksize, int cin, int np, void* planes, void* stream) {
+  TBN_REQUIRE(weight && planes, "conv_split_weights: null pointer");
+  TBN_REQUIRE(cout > 0 && ksize > 0 && cin > 0 && cin % 32 == 0 && (np == 6 || np == 3),
+              "conv_split_weights: bf16x weight planes need cin a multiple of 32 and np 6 | 3 (got cin %d, np %d)", cin, np);
+  TBN_REQUIRE((((uintptr_t)weight | (uintptr_t)planes) & 15) == 0, "conv_split_weights: pointers must be 16-B aligned");
+  static thread_local SplitTab tab;
+  tab.n = 1;
+  tab.w_off[0] = 0;
+  tab.p_off[0] = 0;
+  tab.floats[0] = (size_t)cout * ksize * ksize * cin;
+  tab.blk0[0] = 0;
+  tab.blk0[1] = (int)((tab.floats[0] + 1023) / 1024);
+  return tbn_launch_bf16x_split(weight, planes, tab, np, (hipStream_t)stream);
 }
 
 int tbn_conv_partial_rows(const tbn_conv_desc* d, int mt, int pair) {

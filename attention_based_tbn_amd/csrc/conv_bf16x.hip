@@ -27,6 +27,15 @@
 // Subnormals: the lo plane of an input below about 2^-110 is a bf16 subnormal and the guides do not say whether the
 // bf16 MFMA flushes subnormal A/B inputs; the absolute error that could cause is < 2^-126 per product.  A value that
 // rounds to a bf16 infinity (|x| > 3.39e38) gives NaN planes, where the fp32 kernel would return an infinity.
+//
+// PRE-SPLIT WEIGHT PLANES (CONV_FLAG_BF16X_PLANES, eval mode: the weights are constants).  bf16x_split_planes_kernel writes
+// the planes of a whole [Cout][taps][Cin] weight tensor ONCE, as one record per (cout row, tap, 32-channel chunk) =
+// [hi 32 | mid 32 | (lo 32)] bf16 -- the LDS row image above minus its pad, record index = (float index of the chunk) / 32.
+// With PL = true the 3x3 kernel copies its B tile from those records with 16-B loads (same values in the same LDS image,
+// same MFMA order: bit-identical results) and the tap loop loses the weight split's VALU work.
+// conv_bf16x_pw_kernel is the pointwise (1x1 / stride 1 / pad 0) kernel on planes: a plain [M x Cin] . [Cin x Cout] GEMM over
+// the NHWC rows, no map-width limit; the activation tile is still split while it is staged, now once per 32-channel chunk
+// and N tile with no nine-tap reuse behind it, so wide N tiles are what amortises it.
 #include <cstdio>
 #include <cstring>
 
@@ -50,7 +59,8 @@ __device__ __forceinline__ void bf16x_split_store(char* dst, const float4 v4) {
 }
 
 // NP = plane products (6 | 3); EPI 0 plain (+bias, optional ReLU / accumulate) | 2 eval-BN fold + ReLU
-template <int NP, int MT, int NT, int EPI>
+// PL: p.wt holds pre-split weight planes (records, see the head of the file) instead of fp32 weights
+template <int NP, int MT, int NT, int EPI, bool PL = false>
 __global__ __launch_bounds__(256) void conv_bf16x_kernel(ConvP p) {
   extern __shared__ __attribute__((aligned(16))) float dyn_lds[];
   constexpr int P = NP == 6 ? 3 : 2;
@@ -112,19 +122,38 @@ __global__ __launch_bounds__(256) void conv_bf16x_kernel(ConvP p) {
     for (int j = 0; j < NJ; ++j)
       if (r0 + 32 * j < HR) bf16x_split_store<P>(As + (r0 + 32 * j) * PITCH + c4 * 8, ha[j]);
   };
-  float4 rb[NT];
-  unsigned b_voff[NT];
+  // B tile: NT float4 of fp32 weights per thread, or (PL) the 16-B pieces of the tile's plane records: piece q of the
+  // tile = piece q % (4 P) of row q / (4 P), copied to the same place of the LDS row
+  constexpr int NB = PL ? (NT * P + 1) / 2 : NT;
+  float4 rb[NB];
+  unsigned b_voff[NB], b_lds[NB];
 #pragma unroll
-  for (int i = 0; i < NT; ++i)
-    b_voff[i] = (unsigned)(n0 + r0 + 32 * i) * (unsigned)p.Krow * 4u + (unsigned)c4 * 16u;   // rows >= Cout: beyond wt_bytes
+  for (int i = 0; i < NB; ++i) {
+    if (PL) {
+      const int q = tid + 256 * i, row = q / (4 * P), pc = q - row * (4 * P);
+      const bool ok = q < BN * 4 * P;
+      // rows >= Cout: beyond wt_bytes
+      b_voff[i] = ok ? (unsigned)(n0 + row) * (unsigned)(p.Krow >> 5) * (unsigned)(P * 64) + (unsigned)pc * 16u : TBN_OOB;
+      b_lds[i] = ok ? (unsigned)(row * PITCH + pc * 16) : 0xffffffffu;
+    } else {
+      b_voff[i] = (unsigned)(n0 + r0 + 32 * i) * (unsigned)p.Krow * 4u + (unsigned)c4 * 16u;   // rows >= Cout: beyond wt_bytes
+      b_lds[i] = (unsigned)((r0 + 32 * i) * PITCH + c4 * 8);
+    }
+  }
   auto load_b = [&](int t, int c0) {
-    const unsigned koff = (unsigned)(t * p.Cin + c0) * 4u;
+    const unsigned koff = PL ? (unsigned)((t * p.Cin + c0) >> 5) * (unsigned)(P * 64) : (unsigned)(t * p.Cin + c0) * 4u;
 #pragma unroll
-    for (int i = 0; i < NT; ++i) rb[i] = buf_load4(wt_rsrc, b_voff[i], koff);
+    for (int i = 0; i < NB; ++i) rb[i] = buf_load4(wt_rsrc, b_voff[i], koff);
   };
   auto store_b = [&](char* Bs) {
 #pragma unroll
-    for (int i = 0; i < NT; ++i) bf16x_split_store<P>(Bs + (r0 + 32 * i) * PITCH + c4 * 8, rb[i]);
+    for (int i = 0; i < NB; ++i) {
+      if (PL) {
+        if (b_lds[i] != 0xffffffffu) *reinterpret_cast<float4*>(Bs + b_lds[i]) = rb[i];
+      } else {
+        bf16x_split_store<P>(Bs + b_lds[i], rb[i]);
+      }
+    }
   };
 
   f32x16 acc[MT][NT];
@@ -189,6 +218,130 @@ __global__ __launch_bounds__(256) void conv_bf16x_kernel(ConvP p) {
   conv_epilogue<MT, NT, EPI, false>(p, acc, dyn_lds, tm, m0, n0);
 }
 
+
+// Pointwise (1x1 / stride 1 / pad 0) split-bf16 GEMM on pre-split weight planes: out[m][n] = sum_c in[m][c] * w[n][c] over
+// the flat NHWC rows m.  Per 32-channel chunk the (128 MT) x 32 activation tile is loaded as fp32, split into planes and
+// staged (four float4 per thread and M sub-tile), the (32 NT) x 32 weight tile is copied from its plane records; both are
+// double buffered, one barrier per chunk.  Fragment layout, product order and epilogue are the 3x3 kernel's.
+template <int NP, int MT, int NT, int EPI>
+__global__ __launch_bounds__(256) void conv_bf16x_pw_kernel(ConvP p) {
+  extern __shared__ __attribute__((aligned(16))) float dyn_lds[];
+  constexpr int P = NP == 6 ? 3 : 2;
+  constexpr int PITCH = P * 64 + 16;
+  constexpr int BM = 128 * MT, BN = 32 * NT;
+  constexpr int NA = 4 * MT;                 // float4 of the activation tile per thread
+  constexpr int NB = (NT * P + 1) / 2;       // 16-B pieces of the weight tile per thread
+  constexpr int STAGE = (BM + BN) * PITCH;   // bytes of one LDS stage: A rows, then B rows
+  const int bid = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nb = p.tiles_m * p.tiles_n;
+  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, idx = bid >> 3;   // the tiles of an activation row panel share an XCD
+  const int nid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+  const int tm = nid / p.tiles_n, tn = nid - tm * p.tiles_n;
+  const int m0 = tm * BM, n0 = tn * BN;
+  char* lds = reinterpret_cast<char*>(dyn_lds);
+
+  const i32x4 in_rsrc = make_rsrc(p.in, p.in_bytes);
+  const i32x4 wt_rsrc = make_rsrc(p.wt, p.wt_bytes);
+  const int c4 = tid & 7, r0 = tid >> 3;
+  const int lrow = lane & 31, lhalf = lane >> 5;
+
+  unsigned fa_off[MT], fb_off[NT];
+#pragma unroll
+  for (int i = 0; i < MT; ++i) fa_off[i] = (unsigned)((wave * 32 * MT + i * 32 + lrow) * PITCH + lhalf * 16);
+#pragma unroll
+  for (int j = 0; j < NT; ++j) fb_off[j] = (unsigned)((BM + j * 32 + lrow) * PITCH + lhalf * 16);
+
+  float4 ra[NA];
+  unsigned a_voff[NA];
+#pragma unroll
+  for (int j = 0; j < NA; ++j) {
+    const int m = m0 + r0 + 32 * j;   // rows >= M read zeros
+    a_voff[j] = m < p.M ? (unsigned)m * (unsigned)p.in_ld * 4u + (unsigned)c4 * 16u : TBN_OOB;
+  }
+  float4 rb[NB];
+  unsigned b_voff[NB], b_lds[NB];
+  const unsigned nchunks = (unsigned)p.Cin >> 5;
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    const int q = tid + 256 * i, row = q / (4 * P), pc = q - row * (4 * P);
+    const bool ok = q < BN * 4 * P;
+    b_voff[i] = ok ? (unsigned)(n0 + row) * nchunks * (unsigned)(P * 64) + (unsigned)pc * 16u : TBN_OOB;   // rows >= Cout: beyond wt_bytes
+    b_lds[i] = ok ? (unsigned)((BM + row) * PITCH + pc * 16) : 0xffffffffu;
+  }
+  auto load_ab = [&](int c) {
+#pragma unroll
+    for (int j = 0; j < NA; ++j) ra[j] = buf_load4(in_rsrc, a_voff[j], (unsigned)c * 128u);
+#pragma unroll
+    for (int i = 0; i < NB; ++i) rb[i] = buf_load4(wt_rsrc, b_voff[i], (unsigned)c * (unsigned)(P * 64));
+  };
+  auto store_ab = [&](char* S) {
+#pragma unroll
+    for (int j = 0; j < NA; ++j) bf16x_split_store<P>(S + (r0 + 32 * j) * PITCH + c4 * 8, ra[j]);
+#pragma unroll
+    for (int i = 0; i < NB; ++i)
+      if (b_lds[i] != 0xffffffffu) *reinterpret_cast<float4*>(S + b_lds[i]) = rb[i];
+  };
+
+  f32x16 acc[MT][NT];
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+  load_ab(0);
+  store_ab(lds);
+  __syncthreads();
+  for (int c = 0; c < (int)nchunks; ++c) {
+    const bool next = c + 1 < (int)nchunks;
+    if (next) load_ab(c + 1);
+    const char* S = lds + (c & 1) * STAGE;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {   // two K steps of 16 channels
+      bf16x8 fa[MT][P], fb[NT][P];
+#pragma unroll
+      for (int pl = 0; pl < P; ++pl) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i) fa[i][pl] = *reinterpret_cast<const bf16x8*>(S + fa_off[i] + pl * 64 + s * 32);
+#pragma unroll
+        for (int j = 0; j < NT; ++j) fb[j][pl] = *reinterpret_cast<const bf16x8*>(S + fb_off[j] + pl * 64 + s * 32);
+      }
+#pragma unroll
+      for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int i = 0; i < MT; ++i) {
+          if (NP == 6) {
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][P - 1], fb[j][0], acc[i][j], 0, 0, 0);   // lo * hi
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][P - 1], acc[i][j], 0, 0, 0);   // hi * lo
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][1], acc[i][j], 0, 0, 0);       // mid * mid
+          }
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][0], acc[i][j], 0, 0, 0);         // mid * hi
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][1], acc[i][j], 0, 0, 0);         // hi * mid
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][0], acc[i][j], 0, 0, 0);         // hi * hi
+        }
+    }
+    // the other stage was last read in the previous chunk: every wave is past that chunk's barrier
+    if (next) store_ab(lds + ((c + 1) & 1) * STAGE);
+    __syncthreads();
+  }
+  conv_epilogue<MT, NT, EPI, false>(p, acc, dyn_lds, tm, m0, n0);
+}
+
+// Weight planes of up to 64 weight tensors in one launch: a workgroup splits 1024 consecutive floats (32 records) of one
+// tensor; thread = one float4 = 8 B of each plane of its record.
+template <int P>
+__global__ __launch_bounds__(256) void bf16x_split_planes_kernel(const float* __restrict__ w, char* __restrict__ planes,
+                                                                 SplitTab tab) {
+  int l = 0;
+  while (l + 1 < tab.n && (int)blockIdx.x >= tab.blk0[l + 1]) ++l;
+  const size_t f = ((size_t)((int)blockIdx.x - tab.blk0[l]) * 256 + threadIdx.x) * 4;   // float index inside the tensor
+  if (f >= tab.floats[l]) return;
+  const float4 v = *reinterpret_cast<const float4*>(w + tab.w_off[l] + f);
+  bf16x_split_store<P>(planes + tab.p_off[l] + (f >> 5) * (size_t)(P * 64) + ((f & 31) >> 2) * 8, v);
+}
+
 // ---------------------------------------------------------------------------------------------- host side
 // LDS bytes of the split-bf16 kernel; 0 if the shape is not a 3x3 / stride 1 / pad 1 layer it handles
 size_t tbn_conv_bf16x_lds_bytes(const ConvP& p, int np, int mt, int nt) {
@@ -222,27 +375,82 @@ void tbn_conv_bf16x_pick_tile(int M, int Cout, int K, int np, int* mt_out, int* 
   *nt_out = bn;
 }
 
-template <int NP, int MT, int NT, int EPI>
+// KIND 0: 3x3, weights split while staging | 1: 3x3 from weight planes | 2: pointwise from weight planes
+template <int NP, int MT, int NT, int EPI, int KIND>
 static int launch_bf16x_e(const ConvP& p, int grid, size_t lds_bytes, hipStream_t st) {
   static size_t allowed = 64 * 1024;   // per instantiation: raise the dynamic-LDS limit once when a shape needs it
+  const void* fn = KIND == 2 ? reinterpret_cast<const void*>(&conv_bf16x_pw_kernel<NP, MT, NT, EPI>)
+                             : reinterpret_cast<const void*>(&conv_bf16x_kernel<NP, MT, NT, EPI, KIND == 1>);
   if (lds_bytes > allowed) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16x_kernel<NP, MT, NT, EPI>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
       tbn_set_error("conv_bf16x: cannot raise the dynamic LDS limit");
       return TBN_ERR_LAUNCH;
     }
     allowed = 160 * 1024;
   }
-  TBN_LAUNCH((conv_bf16x_kernel<NP, MT, NT, EPI>), dim3(grid), dim3(256), lds_bytes, st, p);
+  if (KIND == 2)
+    TBN_LAUNCH((conv_bf16x_pw_kernel<NP, MT, NT, EPI>), dim3(grid), dim3(256), lds_bytes, st, p);
+  else
+    TBN_LAUNCH((conv_bf16x_kernel<NP, MT, NT, EPI, KIND == 1>), dim3(grid), dim3(256), lds_bytes, st, p);
   return TBN_OK;
 }
-template <int MT, int NT>
-static int launch_bf16x(const ConvP& p, int np, int grid, size_t lds_bytes, hipStream_t st) {
+template <int MT, int NT, int KIND>
+static int launch_bf16x_k(const ConvP& p, int np, int grid, size_t lds_bytes, hipStream_t st) {
   if (np == 6)
-    return p.mode == CONV_EPI_EVAL ? launch_bf16x_e<6, MT, NT, 2>(p, grid, lds_bytes, st)
-                                   : launch_bf16x_e<6, MT, NT, 0>(p, grid, lds_bytes, st);
-  return p.mode == CONV_EPI_EVAL ? launch_bf16x_e<3, MT, NT, 2>(p, grid, lds_bytes, st)
-                                 : launch_bf16x_e<3, MT, NT, 0>(p, grid, lds_bytes, st);
+    return p.mode == CONV_EPI_EVAL ? launch_bf16x_e<6, MT, NT, 2, KIND>(p, grid, lds_bytes, st)
+                                   : launch_bf16x_e<6, MT, NT, 0, KIND>(p, grid, lds_bytes, st);
+  return p.mode == CONV_EPI_EVAL ? launch_bf16x_e<3, MT, NT, 2, KIND>(p, grid, lds_bytes, st)
+                                 : launch_bf16x_e<3, MT, NT, 0, KIND>(p, grid, lds_bytes, st);
+}
+template <int MT, int NT>
+static int launch_bf16x(const ConvP& p, int np, int kind, int grid, size_t lds_bytes, hipStream_t st) {
+  if (kind == 2) return launch_bf16x_k<MT, NT, 2>(p, np, grid, lds_bytes, st);
+  if (kind == 1) return launch_bf16x_k<MT, NT, 1>(p, np, grid, lds_bytes, st);
+  return launch_bf16x_k<MT, NT, 0>(p, np, grid, lds_bytes, st);
+}
+
+// LDS bytes of the pointwise kernel (two stages of A + B rows); 0 if the shape is not a 1x1 / stride 1 / pad 0 layer
+size_t tbn_conv_bf16x_pw_lds_bytes(const ConvP& p, int np, int mt, int nt) {
+  if (p.R != 1 || p.S != 1 || p.stride != 1 || p.pad != 0 || p.up != 1 || p.OH != p.H || p.OW != p.W || p.Cin % 32 != 0)
+    return 0;
+  const size_t pitch = (np == 6 ? 3 : 2) * 64 + 16;
+  return (size_t)2 * (128 * mt + 32 * nt) * pitch;
+}
+
+// Tile heuristic of the pointwise kernel: the model above plus the activation split.  A 1x1 has no nine-tap reuse of the
+// split activation tile: every N tile of a row panel splits it again (per chunk and 128 rows: 4 float4 x (2 np / 3 + ...)
+// VALU instructions per thread on the port the MFMA shares, priced at 150 cycles per M sub-tile), so the split is only
+// amortised over the N tile -- the merged 1x1 groups are 192 - 832 columns wide and the model therefore prefers WIDE NT
+// (fewer N tiles = fewer splits of the same rows) over tall MT.  Not measured, like the 3x3 model.
+void tbn_conv_bf16x_pw_pick_tile(int M, int Cout, int K, int np, int* mt_out, int* nt_out) {
+  double best = 1e300;
+  int bm = 1, bn = 1;
+  for (int mt = 1; mt <= 2; ++mt)
+    for (int nt = 1; nt <= 4; ++nt) {
+      const double blocks = (double)cdiv(M, 128 * mt) * cdiv(Cout, 32 * nt);
+      const double rounds = (double)((long)((blocks + 255) / 256));
+      const double per_block = (K / 32.0) * (mt * nt * 64.0 * np + mt * 150.0 + 350.0) + 4000.0;
+      const double cost = rounds * per_block * (1.0 + 0.01 / (mt * nt)) * (1.0 + 0.005 / nt);   // ties: bigger, then wider
+      if (cost < best) {
+        best = cost;
+        bm = mt;
+        bn = nt;
+      }
+    }
+  *mt_out = bm;
+  *nt_out = bn;
+}
+
+size_t tbn_bf16x_planes_bytes(size_t floats, int np) { return floats * (np == 6 ? 6 : 4); }
+
+int tbn_launch_bf16x_split(const float* w, void* planes, const SplitTab& tab, int np, hipStream_t st) {
+  if (tab.n <= 0) return TBN_OK;
+  if (np == 6)
+    TBN_KLAUNCH((bf16x_split_planes_kernel<3>), dim3(tab.blk0[tab.n]), dim3(256), 0, st, w, (char*)planes, tab);
+  else
+    TBN_KLAUNCH((bf16x_split_planes_kernel<2>), dim3(tab.blk0[tab.n]), dim3(256), 0, st, w, (char*)planes, tab);
+  TBN_CHECK_LAUNCH("bf16x_split_planes");
+  return TBN_OK;
 }
 
 #define TBN_BF16X_REFUSE(cond, code, ...) \
@@ -262,22 +470,43 @@ int tbn_launch_conv_bf16x(ConvP& p, int rowmode, int mt, int nt, double alg_byte
                    "conv: the bf16x%d flag selects its own kernel: not with variant flags 4 / 8 / 16", np);
   TBN_BF16X_REFUSE(p.mode == CONV_EPI_STATS || p.nred > 0 || rider != nullptr, TBN_ERR_UNSUPPORTED,
                    "conv: the bf16x%d kernel has no training-statistics / reduce epilogue and hosts no rider (eval forward only)", np);
-  TBN_BF16X_REFUSE(rowmode || tbn_conv_bf16x_lds_bytes(p, np, 1, 1) == 0, TBN_ERR_UNSUPPORTED,
-                   "conv: the bf16x%d kernel handles 3x3 / stride 1 / pad 1 layers on maps at most 64 wide (got %dx%d stride %d pad %d, width %d)",
-                   np, p.R, p.S, p.stride, p.pad, p.W);
-  if (mt <= 0 || nt <= 0) tbn_conv_bf16x_pick_tile(p.M, p.Cout, p.K, np, &mt, &nt);
+  const bool planes = (p.flags & CONV_FLAG_BF16X_PLANES) != 0;
+  // weights split while staging: the 3x3 kernel only; on pre-split planes (flag 128) also the pointwise kernel
+  const bool pw = planes && !rowmode && tbn_conv_bf16x_pw_lds_bytes(p, np, 1, 1) != 0;
+  if (!planes)
+    TBN_BF16X_REFUSE(rowmode || tbn_conv_bf16x_lds_bytes(p, np, 1, 1) == 0, TBN_ERR_UNSUPPORTED,
+                     "conv: the bf16x%d kernel handles 3x3 / stride 1 / pad 1 layers on maps at most 64 wide (got %dx%d stride %d pad %d, width %d)",
+                     np, p.R, p.S, p.stride, p.pad, p.W);
+  else
+    TBN_BF16X_REFUSE(!pw && (rowmode || tbn_conv_bf16x_lds_bytes(p, np, 1, 1) == 0), TBN_ERR_UNSUPPORTED,
+                     "conv: the bf16x%d kernels on weight planes (flag 128) handle 3x3 / stride 1 / pad 1 layers on maps at most 64 wide and 1x1 / stride 1 / pad 0 layers, cin a multiple of 32 (got %dx%d stride %d pad %d, width %d, cin %d)",
+                     np, p.R, p.S, p.stride, p.pad, p.W, p.Cin);
+  const int kind = pw ? 2 : (planes ? 1 : 0);
+  if (mt <= 0 || nt <= 0) {
+    if (pw)
+      tbn_conv_bf16x_pw_pick_tile(p.M, p.Cout, p.K, np, &mt, &nt);
+    else
+      tbn_conv_bf16x_pick_tile(p.M, p.Cout, p.K, np, &mt, &nt);
+  }
   TBN_BF16X_REFUSE(mt > 2 || nt > 4, TBN_ERR_UNSUPPORTED, "conv: unsupported bf16x%d tile %dx%d", np, mt, nt);
-  const size_t lds_bytes = tbn_conv_bf16x_lds_bytes(p, np, mt, nt);
+  const size_t lds_bytes = pw ? tbn_conv_bf16x_pw_lds_bytes(p, np, mt, nt) : tbn_conv_bf16x_lds_bytes(p, np, mt, nt);
+  if (planes) {   // p.wt points at the plane records of this weight tensor: extent for the hardware range check
+    const size_t pb = tbn_bf16x_planes_bytes((size_t)p.Cout * p.Krow, np);
+    TBN_BF16X_REFUSE(pb >= (1ull << 31), TBN_ERR_UNSUPPORTED, "conv: bf16x%d weight planes of %zu B >= 2 GiB", np, pb);
+    p.wt_bytes = (unsigned)pb;
+  }
   TBN_BF16X_REFUSE(lds_bytes > 160 * 1024, TBN_ERR_UNSUPPORTED, "conv: bf16x%d tile %dx%d needs %zu B of LDS", np, mt, nt, lds_bytes);
   p.tiles_m = cdiv(p.M, 128 * mt);
   p.tiles_n = cdiv(p.Cout, 32 * nt);
   const int grid = p.tiles_m * p.tiles_n;
   char nm[64];
-  snprintf(nm, sizeof(nm), "conv_bf16x%d_kernel<%d, %d, %d>", np, mt, nt, p.mode == CONV_EPI_EVAL ? 2 : 0);
+  // conv_bf16x6_kernel: weights split while staging | conv_bf16x6_planes_kernel: 3x3 from planes | conv_bf16x6_pw_kernel: pointwise
+  snprintf(nm, sizeof(nm), "conv_bf16x%d%s_kernel<%d, %d, %d>", np, kind == 2 ? "_pw" : (kind == 1 ? "_planes" : ""), mt, nt,
+           p.mode == CONV_EPI_EVAL ? 2 : 0);
   tbn_prof_begin(nm, p.alg_flops, st, alg_bytes);
   int rc = TBN_ERR_UNSUPPORTED;
 #define TBN_XCASE(MTv, NTv) \
-  if (mt == MTv && nt == NTv) rc = launch_bf16x<MTv, NTv>(p, np, grid, lds_bytes, st);
+  if (mt == MTv && nt == NTv) rc = launch_bf16x<MTv, NTv>(p, np, kind, grid, lds_bytes, st);
   TBN_XCASE(1, 1) TBN_XCASE(1, 2) TBN_XCASE(1, 3) TBN_XCASE(1, 4) TBN_XCASE(2, 1) TBN_XCASE(2, 2) TBN_XCASE(2, 3) TBN_XCASE(2, 4)
 #undef TBN_XCASE
   tbn_prof_end(st);

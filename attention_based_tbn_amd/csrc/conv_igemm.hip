@@ -1536,11 +1536,22 @@ static int conv_prepare(ConvP& p, int rowmode, int* single) {
 }
 
 int tbn_launch_conv(ConvP p, int rowmode, int mt, int nt, hipStream_t st, const RiderP* rider) {
+  if (p.flags & CONV_FLAG_BF16X_PLANES) {   // refused here, in bf16x terms, before the generic checks see the launch
+    if ((p.flags & (CONV_FLAG_BF16X6 | CONV_FLAG_BF16X3)) == 0) {
+      tbn_set_error("conv: flag 128 (pre-split bf16x weight planes) is only valid with a bf16x math flag (32 / 64)");
+      return TBN_ERR_ARG;
+    }
+    if (rowmode || p.Cin % 32 != 0 || p.stride != 1) {
+      tbn_set_error("conv: the bf16x kernels on weight planes (flag 128) need stride 1 and cin a multiple of 32 (got stride %d, cin %d)",
+                    p.stride, p.Cin);
+      return TBN_ERR_UNSUPPORTED;
+    }
+  }
   int single = 0;
   const int prc = conv_prepare(p, rowmode, &single);
   if (prc != TBN_OK) return prc;
   if (single) return launch_conv_tiles(p, rowmode, mt, nt, st, rider);
-  if (p.flags & (CONV_FLAG_BF16X6 | CONV_FLAG_BF16X3)) {
+  if (p.flags & (CONV_FLAG_BF16X6 | CONV_FLAG_BF16X3 | CONV_FLAG_BF16X_PLANES)) {
     tbn_set_error("conv: the bf16x kernels (flags 32 / 64) do not compute strided data gradients");
     return TBN_ERR_UNSUPPORTED;
   }
@@ -1747,8 +1758,8 @@ static int launch_pair(const ConvPair& q, const RiderP& rd, int blocks, int vari
 int tbn_launch_conv_pair(ConvP a, ConvP b, int variant, int mt, int nt, hipStream_t st, const RiderP* rider) {
   static thread_local ConvPair q;
   static thread_local RiderP rd;
-  if ((a.flags | b.flags) & (CONV_FLAG_BF16X6 | CONV_FLAG_BF16X3)) {
-    tbn_set_error("conv_pair: the bf16x kernels (flags 32 / 64) are single launches");
+  if ((a.flags | b.flags) & (CONV_FLAG_BF16X6 | CONV_FLAG_BF16X3 | CONV_FLAG_BF16X_PLANES)) {
+    tbn_set_error("conv_pair: the bf16x kernels (flags 32 / 64, weight planes 128) are single launches");
     return TBN_ERR_UNSUPPORTED;
   }
   if (rider != nullptr)

@@ -1223,6 +1223,54 @@ struct SideJoin {
 
 extern "C" {
 
+// bf16 weight planes of the backbone (TBN_BACKBONE_CONV_BF16X_ALL): every GEMM with k in {1, 3}, stride 1 and cin a multiple
+// of 32 owns a run of records (conv_bf16x.hip) in plan order; off[i] = byte offset of conv i's records, -1 = none
+// The predicate looks at the layer only, not at the map it runs on, on purpose: the layout is then a function of the graph
+// and np alone, so ONE plane buffer serves every plan of a backbone (any frame count and input size; the Python host keeps
+// one per module).  The price: a conv2_3x3 on a map wider than 64 stays on the fp32 kernel and its planes (110592 weights,
+// 0.65 MB of ~40 MB at np 6) are written and never read.
+static bool planes_conv(const Conv& c) {
+  return !c.stem && c.stride == 1 && c.cin % 32 == 0 && ((c.k == 1 && c.pad == 0) || (c.k == 3 && c.pad == 1));
+}
+static size_t planes_layout(const tbn_backbone_plan* P, int np, std::vector<long long>* off) {
+  size_t total = 0;
+  if (off) off->assign(P->convs.size(), -1);
+  for (size_t i = 0; i < P->convs.size(); ++i) {
+    const Conv& c = P->convs[i];
+    if (!planes_conv(c)) continue;
+    if (off) (*off)[i] = (long long)total;
+    total += tbn_bf16x_planes_bytes((size_t)c.cout * c.k * c.k * c.cin, np);
+  }
+  return total;
+}
+
+size_t tbn_backbone_weight_planes_bytes(const tbn_backbone_plan* P, int np) {
+  if (!P || (np != 6 && np != 3)) return 0;
+  return planes_layout(P, np, nullptr);
+}
+
+int tbn_backbone_split_weights(const tbn_backbone_plan* P, const float* weight, int np, void* planes, void* stream) {
+  TBN_REQUIRE(P && weight && planes, "backbone_split_weights: null argument");
+  TBN_REQUIRE(np == 6 || np == 3, "backbone_split_weights: np must be 6 (bf16x6) or 3 (bf16x3), got %d", np);
+  TBN_REQUIRE((((uintptr_t)weight | (uintptr_t)planes) & 15) == 0, "backbone_split_weights: pointers must be 16-B aligned");
+  std::vector<long long> off;
+  planes_layout(P, np, &off);
+  static thread_local SplitTab tab;
+  tab.n = 0;
+  tab.blk0[0] = 0;
+  for (size_t i = 0; i < P->convs.size(); ++i) {
+    if (off[i] < 0) continue;
+    const Conv& c = P->convs[i];
+    TBN_REQUIRE(tab.n < 64, "backbone_split_weights: more than 64 weight tensors");
+    tab.w_off[tab.n] = c.w_off;
+    tab.p_off[tab.n] = (size_t)off[i];
+    tab.floats[tab.n] = (size_t)c.cout * c.k * c.k * c.cin;
+    tab.blk0[tab.n + 1] = tab.blk0[tab.n] + (int)((tab.floats[tab.n] + 1023) / 1024);
+    ++tab.n;
+  }
+  return tbn_launch_bf16x_split(weight, planes, tab, np, (hipStream_t)stream);
+}
+
 int tbn_backbone_forward(const tbn_backbone_plan* P, int training, const float* x_nchw,
                          const tbn_backbone_params* prm, void* workspace, size_t workspace_bytes,
                          float** features_out, void* stream) {
@@ -1232,6 +1280,16 @@ int tbn_backbone_forward(const tbn_backbone_plan* P, int training, const float* 
   TBN_REQUIRE(((uintptr_t)workspace & 255) == 0, "backbone_forward: workspace must be 256-B aligned");
   TBN_REQUIRE((prm->flags & (TBN_BACKBONE_CONV_BF16X6 | TBN_BACKBONE_CONV_BF16X3)) != (TBN_BACKBONE_CONV_BF16X6 | TBN_BACKBONE_CONV_BF16X3),
               "backbone_forward: TBN_BACKBONE_CONV_BF16X6 and _BF16X3 (bf16x math modes) are exclusive");
+  // TBN_BACKBONE_CONV_BF16X_ALL: honoured in eval mode beside one of the math flags only
+  const bool bf16x_all = !training && (prm->flags & TBN_BACKBONE_CONV_BF16X_ALL) != 0 &&
+                         (prm->flags & (TBN_BACKBONE_CONV_BF16X6 | TBN_BACKBONE_CONV_BF16X3)) != 0;
+  if (bf16x_all) {
+    if (prm->weight_planes == nullptr) {
+      tbn_set_error("backbone_forward: TBN_BACKBONE_CONV_BF16X_ALL (bf16x weight planes) needs tbn_backbone_params.weight_planes");
+      return TBN_ERR_ARG;
+    }
+    TBN_REQUIRE(((uintptr_t)prm->weight_planes & 15) == 0, "backbone_forward: bf16x weight_planes must be 16-B aligned");
+  }
   float* ws = (float*)workspace;
   const int R = P->frames;
   const int tr = training ? 1 : 0;   // index of the forward launch choices (Conv::ft)
@@ -1301,6 +1359,14 @@ int tbn_backbone_forward(const tbn_backbone_plan* P, int training, const float* 
   auto bf16x_layer = [&](const Conv& c) {
     return bf16x_flag != 0 && !c.stem && c.k == 3 && c.stride == 1 && c.pad == 1 && c.inW <= 64 && c.cin % 32 == 0;
   };
+  // TBN_BACKBONE_CONV_BF16X_ALL: those layers read their weight tiles from the caller's pre-split planes, and every
+  // 1x1 / stride 1 GEMM (merged sibling groups with a pooled part included) goes through the pointwise split-bf16 kernel
+  // with that kernel's size heuristic -- the plan holds no tile for it
+  auto bf16x_pw_layer = [&](const Conv& c) {
+    return bf16x_all && !c.stem && c.k == 1 && c.stride == 1 && c.pad == 0 && c.cin % 32 == 0;
+  };
+  std::vector<long long> planes_off;
+  if (bf16x_all) planes_layout(P, (bf16x_flag & CONV_FLAG_BF16X6) ? 6 : 3, &planes_off);
   const hipStream_t st_main = st;
   // riders: one-chain training program only; off while the profiler brackets the conv launches (a rider's time would be
   // charged to its host GEMM)
@@ -1369,10 +1435,15 @@ int tbn_backbone_forward(const tbn_backbone_plan* P, int training, const float* 
           if (q.pooled) p.raw_seg1 = i + 1;
         }
       }
-      if (bx) {
+      if (bx || bf16x_pw_layer(c)) {
         p.flags |= bf16x_flag;
         p.halo = 0;
-        TBN_TRY(tbn_launch_conv(p, 0, T.halo == 1 ? T.mt : 0, T.halo == 1 ? T.nt : 0, st, nullptr));
+        if (bf16x_all) {
+          p.flags |= CONV_FLAG_BF16X_PLANES;
+          p.wt = reinterpret_cast<const float*>(static_cast<const char*>(prm->weight_planes) + planes_off[o.idx]);
+        }
+        const bool tuned = bx && T.halo == 1;
+        TBN_TRY(tbn_launch_conv(p, 0, tuned ? T.mt : 0, tuned ? T.nt : 0, st, nullptr));
         continue;
       }
       TBN_TRY(tbn_launch_conv(p, c.stem, T.mt, T.nt, st, rd));

@@ -11,7 +11,9 @@ enum {
   CONV_FLAG_DMA = 8,    // host only: use the LDS-DMA staging kernel
   CONV_FLAG_SK4 = 16,   // host only: 32-row tiles whose four waves split K (small-M launches)
   CONV_FLAG_BF16X6 = 32,   // host only: split-bf16 kernel (conv_bf16x.hip), six plane products
-  CONV_FLAG_BF16X3 = 64    // host only: the same with three plane products
+  CONV_FLAG_BF16X3 = 64,   // host only: the same with three plane products
+  CONV_FLAG_BF16X_PLANES = 128,  // host only, with 32 / 64: ConvP::wt points at pre-split bf16 weight planes (conv_bf16x.hip)
+  CONV_FLAG_DESC_OUT2 = 256      // tbn_conv_desc only (consumed by the C-ABI, never reaches a launcher): its out2* fields are set
 };
 
 // BN-backward reduce fused into a data-gradient epilogue (the launch that writes the FINAL value of dz): for the output
@@ -167,6 +169,19 @@ size_t tbn_conv_halo_lds_bytes(const ConvP& p, int mt, int nt);   // 0: shape no
 size_t tbn_conv_bf16x_lds_bytes(const ConvP& p, int np, int mt, int nt);   // 0: shape not handled
 void tbn_conv_bf16x_pick_tile(int M, int Cout, int K, int np, int* mt, int* nt);
 int tbn_launch_conv_bf16x(ConvP& p, int rowmode, int mt, int nt, double alg_bytes, hipStream_t st, const RiderP* rider);
+// with CONV_FLAG_BF16X_PLANES: the pointwise (1x1 / stride 1 / pad 0) kernel on weight planes
+size_t tbn_conv_bf16x_pw_lds_bytes(const ConvP& p, int np, int mt, int nt);   // 0: shape not handled
+void tbn_conv_bf16x_pw_pick_tile(int M, int Cout, int K, int np, int* mt, int* nt);
+// weight planes (layout: include/tbn_hip.h): up to 64 weight tensors of one flat fp32 array split in ONE launch
+struct SplitTab {
+  int n;
+  size_t w_off[64];    // float offset of the tensor inside the fp32 array
+  size_t p_off[64];    // byte offset of its records inside the plane buffer
+  size_t floats[64];   // cout * taps * cin (cin a multiple of 32)
+  int blk0[65];        // first workgroup of each tensor (1024 floats per workgroup); blk0[n] = grid size
+};
+size_t tbn_bf16x_planes_bytes(size_t floats, int np);
+int tbn_launch_bf16x_split(const float* w, void* planes, const SplitTab& tab, int np, hipStream_t st);
 void tbn_wgrad_plan(int M, int Cout, int Cin, int taps, int* mt, int* nt, int* splits, int* rows_per_split);
 size_t tbn_wgrad_workspace_floats(int M, int Cout, int Cin, int taps);
 int tbn_launch_wgrad(WgradP p, int rowmode, float* dw, float* workspace, hipStream_t st);

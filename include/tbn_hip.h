@@ -36,6 +36,9 @@ int tbn_version(void);
  * the plan-cache format (TBN_PLAN_CACHE file names, the committed bench plans) and do not move with added features; a
  * library without this symbol has none of them.  Replaces nothing in the reference. */
 #define TBN_CAP_CONV_BF16X 1
+/* bit 2: pre-split bf16 weight planes are honoured -- conv flag 128 with the pointwise (1x1) split-bf16 kernel,
+ * tbn_conv_split_weights / tbn_backbone_split_weights, TBN_BACKBONE_CONV_BF16X_ALL and tbn_backbone_params.weight_planes */
+#define TBN_CAP_CONV_BF16X_PLANES 2
 int tbn_capabilities(void);
 const char* tbn_last_error(void);
 
@@ -100,6 +103,9 @@ typedef struct {
                                  concat, :485-493).  Same device code as the stand-alone passes: results are bit-identical with the
                                  flag off (tests/test_riders_gpu.py).  Ignored in branch mode and while the opt-in profiler brackets
                                  the conv launches. */
+  const void* weight_planes;  /* TBN_BACKBONE_CONV_BF16X_ALL only (never read without that flag, so callers built against the
+                                 shorter struct keep working): the bf16 planes of the flat weights,
+                                 tbn_backbone_weight_planes_bytes() bytes filled by tbn_backbone_split_weights() with the same np */
 } tbn_backbone_params;
 #define TBN_BACKBONE_RIDERS 1
 #define TBN_BACKBONE_STEM_WGRAD_LAST 2   /* one-chain backward without aux stream: the weight gradients of conv2_3x3 and
@@ -122,6 +128,16 @@ typedef struct {
                                             model.eval() / torch.no_grad() (core/tools/test.py:67-87) */
 #define TBN_BACKBONE_CONV_BF16X3 16      /* the same with three plane products (flag 64: relative error < 1.25 * 2^-16 per product);
                                             exclusive with TBN_BACKBONE_CONV_BF16X6 (both: TBN_ERR_ARG) */
+#define TBN_BACKBONE_CONV_BF16X_ALL 32   /* with _BF16X6 or _BF16X3 and training = 0 (ignored otherwise): the weights come from
+                                            tbn_backbone_params.weight_planes (NULL: TBN_ERR_ARG) -- pre-split once instead of per
+                                            tap and tile inside the kernels -- and the mode also covers every 1x1 / stride 1 GEMM
+                                            (cin a multiple of 32: all of them, the merged sibling groups with their pooled
+                                            pool_proj part and conv2_3x3_reduce included) through the pointwise split-bf16 kernel
+                                            (conv flag 128), as single launches with the eval epilogue.  The stem, the four
+                                            stride-2 3x3 layers and a conv2_3x3 on a map wider than 64 stay on the fp32 MFMA.
+                                            Plan blob, fingerprint, autotune and workspace size do not depend on it.
+                                            replaces: the 1x1 and 3x3 nn.Conv2d forwards of core/models/bn_inception_audio.py:24-401
+                                            under model.eval() / torch.no_grad() (core/tools/test.py:67-87) */
 
 typedef struct {
   float* dweight;             /* same layout as weight; fully overwritten */
@@ -208,6 +224,15 @@ unsigned long long tbn_backbone_plan_fingerprint(const tbn_backbone_plan* plan);
 int tbn_backbone_forward(const tbn_backbone_plan* plan, int training, const float* x_nchw,
                          const tbn_backbone_params* params, void* workspace, size_t workspace_bytes,
                          float** features_out, void* stream);
+/* Weight planes for TBN_BACKBONE_CONV_BF16X_ALL (np = 6 | 3 plane products, i.e. three | two planes): one HBM-bound launch
+ * that splits, in the layout of tbn_conv_split_weights, the weights of every GEMM of the plan with ksize 1 or 3, stride 1 and
+ * cin a multiple of 32 -- a merged multi-part 1x1 GEMM as ONE tensor of its parts' rows in the engine's own part order, which
+ * is their order in the flat weight array.  The buffer is the caller's (16-B aligned; size and layout depend on the graph and
+ * np only -- 0 for another np -- never on frames or input size, so one buffer serves every plan of a backbone; a 3x3 layer
+ * that a wide map keeps on the fp32 kernel still has its planes written); split again whenever the weights change.  tbn_backbone_workspace_bytes is unaffected.
+ * replaces: nothing in the reference (cuDNN reads the fp32 nn.Conv2d weights of bn_inception_audio.py:24-401 directly). */
+size_t tbn_backbone_weight_planes_bytes(const tbn_backbone_plan* plan, int np);
+int tbn_backbone_split_weights(const tbn_backbone_plan* plan, const float* weight, int np, void* planes, void* stream);
 /* optional one-time tuning of the per-layer GEMM tiles on the real shapes (times each candidate with
  * hipEvents).  The ONLY entry point that synchronises the stream; clobbers the activations held in
  * `workspace`, so call it between steps (e.g. right after the first forward of a new plan). */
@@ -245,11 +270,29 @@ int tbn_backbone_flip_weights(const tbn_backbone_plan* plan, const tbn_backbone_
  * fp32 accumulator: bf16x6 reproduces a * b to about 2^-25 relative, bf16x3 to < 1.25 * 2^-16.  3x3 / stride 1 / pad 1, map
  * width <= 64, epilogue 0 or 2, tiles mt in {1,2} x nt in {1..4} only: any other geometry, epilogue 1, a data gradient, a
  * pair launch, both bits, or a combination with 4 / 8 / 16 fails with TBN_ERR_UNSUPPORTED / TBN_ERR_ARG and a message naming
- * bf16x -- never a silent fp32 launch.  The profiler keys these launches as conv_bf16x6_kernel<..> / conv_bf16x3_kernel<..>. */
+ * bf16x -- never a silent fp32 launch.  The profiler keys these launches as conv_bf16x6_kernel<..> / conv_bf16x3_kernel<..>.
+ * Flag 128 (only with 32 or 64; alone: TBN_ERR_ARG): `weight` points at PRE-SPLIT bf16 weight planes written by
+ * tbn_conv_split_weights with the matching np, not at fp32 weights.  3x3 / stride 1 / pad 1 (same limits): the same kernel with
+ * its weight tile copied from the planes, bit-identical to the launch without 128 at the same tile (profiler key
+ * conv_bf16x6_planes_kernel<..>).  1x1 / stride 1 / pad 0 with cin a multiple of 32: the pointwise split-bf16 kernel, a plain
+ * [pixels x cin] . [cin x cout] GEMM with no map-width limit, the activation tile split while staged, epilogue 0 / 2, tiles
+ * mt in {1,2} x nt in {1..4} (conv_bf16x6_pw_kernel<..>).  Everything else with 128 -- stride != 1, cin not a multiple of
+ * 32, epilogue 1, a data gradient, a pair launch, a combination with 4 / 8 / 16 -- is refused with a message naming bf16x. */
 int tbn_conv2d_fwd(const float* in, int in_ld, const float* weight, const float* bias, float* out, int out_ld,
                    int n, int h, int w, int cin, int cout, int ksize, int stride, int pad, int epilogue, int flags,
                    const float* scale, const float* shift, float* stat_partial, void* stream);
 int tbn_conv2d_stat_tiles(int n, int h, int w, int cin, int cout, int ksize, int stride, int pad);
+/* bf16 weight planes of ONE conv weight tensor [cout][ksize][ksize][cin] (cin a multiple of 32) for conv flag 128; np = 6
+ * writes three planes (bf16x6), np = 3 two (bf16x3):  hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid), round to
+ * nearest even -- the values the split-bf16 kernels compute while staging fp32 weights.
+ * LAYOUT: one record per (cout row, tap, 32-channel chunk), record index = (row * ksize * ksize + tap) * (cin / 32) + chunk,
+ * i.e. (float index of the chunk's first weight) / 32; a record is [hi 32 | mid 32 | (lo 32)] bf16 = 192 B (np 6) / 128 B
+ * (np 3), element c of a plane = channel 32 * chunk + c.  That is the kernels' LDS row image minus its 16-B pad, so a weight
+ * tile row reaches LDS as 12 / 8 plain 16-byte copies.  Bytes: cout * ksize^2 * cin * 6 (np 6) / * 4 (np 3); the query returns
+ * 0 for arguments the split refuses.  `planes` is caller-owned and 16-B aligned.
+ * replaces: nothing in the reference (its nn.Conv2d weights, bn_inception_audio.py:24-401, go to cuDNN as fp32). */
+size_t tbn_conv_weight_planes_bytes(int cout, int ksize, int cin, int np);
+int tbn_conv_split_weights(const float* weight, int cout, int ksize, int cin, int np, void* planes, void* stream);
 /* tuning / test aid: as tbn_conv2d_fwd (epilogue 0 or 1) with an explicit tile: the workgroup computes
  * (128*mt) x (32*nt) outputs, mt in {1,2}, nt in {1..4}; (0,0) = built-in heuristic */
 int tbn_conv2d_fwd_tile(const float* in, int in_ld, const float* weight, const float* bias, float* out, int out_ld,
@@ -284,7 +327,9 @@ typedef struct {
   int dgrad;              /* 0: forward, 1: data gradient of that convolution (workspace: cout*k*k*cin floats) */
   int epilogue;           /* forward: 0 / 1 / 2 as tbn_conv2d_fwd; data gradient: 0 */
   int flags;              /* 1 accumulate, 2 ReLU; kernel variant 4 LDS-halo, 8 LDS-DMA, 16 split-K tile (0 generic);
-                             32 bf16x6 / 64 bf16x3 split-bf16 math (forward, epilogue 0 / 2; see tbn_conv2d_fwd) */
+                             32 bf16x6 / 64 bf16x3 split-bf16 math (forward, epilogue 0 / 2; see tbn_conv2d_fwd); 128 with
+                             32 / 64: `weight` points at pre-split weight planes (tbn_conv_split_weights); 256: the out2*
+                             fields at the end of this struct are set (a second output destination) */
   int stages;             /* generic kernel: LDS stages 1 / 2 (0 = default) */
   const float* scale;     /* epilogue 2 */
   const float* shift;
@@ -293,6 +338,15 @@ typedef struct {
   tbn_conv_red red[4];
   const float* red_stats; /* mean | rstd | scale | shift, each red_stats_stride floats */
   int red_stats_stride;
+  /* the four fields below were appended to the struct and are read ONLY when flags carries 256, so that a caller compiled
+     against the shorter struct (which cannot set that bit knowingly) never has them read past its object */
+  float* out2;            /* flags & 256; forward, epilogue 0 / 2: output columns >= out2_col_begin (a
+                             multiple of 32, inside (0, cout)) go to out2 (pitch out2_ld, its column 0 = column out2_col_begin),
+                             as the engine's merged 1x1 groups write their parts to different buffers */
+  int out2_ld;
+  int out2_col_begin;
+  int out2_raw;           /* epilogue 2: 1 = out2 receives the bare accumulator (no scale / shift / ReLU), what the engine does
+                             for a pool_proj part whose average pool follows the conv */
 } tbn_conv_desc;
 /* rows of stat_partial / red[i].partial that a launch with M tile `mt` writes (pair = 1: issued by tbn_conv_launch_pair) */
 int tbn_conv_partial_rows(const tbn_conv_desc* d, int mt, int pair);
