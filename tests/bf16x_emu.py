@@ -49,3 +49,34 @@ def cancel_problem(n, h, w, cin, cout, seed=3):
     taps = F.conv2d(torch.ones(1, 1, h, w, dtype=torch.float64), torch.ones(1, 1, 3, 3, dtype=torch.float64), padding=1)
     want = c.double().view(1, -1, 1, 1) * (7 * 2.0 ** -20) * (cin // 2) * taps
     return x, wt, want.expand(n, cout, h, w).contiguous()
+
+
+# plane-product census: hi / mid / lo of the baseline are all populated, each perturbation moves exactly one plane
+X0 = 1 + 2.0 ** -9 + 2.0 ** -19
+D = [2.0 ** -3, 3 * 2.0 ** -11, 3 * 2.0 ** -21]
+PAIRS = [(i, j) for i in range(3) for j in range(3)]
+
+
+def kept(i, j, nprod):
+    """does bf16x6 (nprod 6) / bf16x3 (nprod 3) compute the product of plane i of x with plane j of w"""
+    return i + j <= (2 if nprod == 6 else 1)
+
+
+def isolate_problem(i, j, n, h, w, cin, cout, k, seed=3):
+    """inputs on which every plane product cancels exactly except (plane i of x) * (plane j of w): cancel_problem with a
+    period-4 channel pattern.  With c4 = channel % 4: x_c = X0 + e * D[i], e = [1, 1, 0, 0][c4], at every pixel;
+    w_oc = r_o * s * (X0 + f * D[j]), f = [1, 0, 1, 0][c4], s = [+1, -1, -1, +1][c4], at every tap; r_o = 2^randint(-3, 3).
+    Over four channels sum s = sum s e = sum s f = 0 and sum s e f = 1, so plane product (p, q) sums to
+    r_o (x_p(1) - x_p(0)) (w_q(1) - w_q(0)): zero unless (p, q) == (i, j), where it is r_o D[i] D[j].
+    k = 1 (pad 0) | 3 (pad 1).  Returns x (NCHW), wt (OIHW), the exact output (fp64, NCHW)."""
+    assert k in (1, 3) and cin % 4 == 0
+    e = torch.tensor([1.0, 1.0, 0.0, 0.0]).repeat(cin // 4)
+    f = torch.tensor([1.0, 0.0, 1.0, 0.0]).repeat(cin // 4)
+    s = torch.tensor([1.0, -1.0, -1.0, 1.0]).repeat(cin // 4)
+    x = (X0 + e * D[i]).float().view(1, cin, 1, 1).expand(n, cin, h, w).contiguous()
+    r = 2.0 ** torch.randint(-3, 3, (cout,), generator=torch.Generator().manual_seed(seed)).float()
+    wt = (r.view(-1, 1) * (s * (X0 + f * D[j])).float().view(1, -1)).view(cout, cin, 1, 1).expand(cout, cin, k, k).contiguous()
+    ones = torch.ones(1, 1, h, w, dtype=torch.float64)
+    taps = F.conv2d(ones, torch.ones(1, 1, k, k, dtype=torch.float64), padding=k // 2)
+    want = r.double().view(1, -1, 1, 1) * (D[i] * D[j] * (cin // 4)) * taps
+    return x, wt, want.expand(n, cout, h, w).contiguous()
