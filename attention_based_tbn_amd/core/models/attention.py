@@ -97,13 +97,14 @@ class MultiheadedAttention(nn.Module):
     def forward(self, query, key, value):
         """reference layout: query (L, R, E), key / value (T, R, E) -> ((L, R, E), (R, L, T)) like
         torch.nn.MultiheadAttention (reference attention.py:48-57).  The TBN's own call -- ONE query per sample, key is value
-        (model.py:231-237) -- runs on the wavefront-reduction kernel; any other call shape takes the general path: the three
-        projections and the output projection on the HIP GEMM, the (tiny) score / softmax / weighted-sum core as batched
-        torch-ROCm ops."""
-        if key is value and query.shape[0] == 1:
+        (model.py:231-237) -- runs on the wavefront-reduction kernel when that kernel takes the shape (tbn_mha_q1_fwd: at most
+        32 keys, head_dim a multiple of 4); any other call takes the general path: the three projections and the output
+        projection on the HIP GEMM, the (tiny) score / softmax / weighted-sum core as batched torch-ROCm ops."""
+        a = self.attention_layer
+        if (key is value and query.shape[0] == 1 and 1 <= key.shape[0] <= 32
+                and (a.embed_dim // a.num_heads) % 4 == 0):
             out, w = self.attend(query[0], key.transpose(0, 1).contiguous())
             return out.unsqueeze(0), w.unsqueeze(1)
-        a = self.attention_layer
         E, H = a.embed_dim, a.num_heads
         L, R, _ = query.shape
         T = key.shape[0]
@@ -112,14 +113,15 @@ class MultiheadedAttention(nn.Module):
         q = ops.linear(query.reshape(L * R, E), a.in_proj_weight[:E], a.in_proj_bias[:E]) * (float(d) ** -0.5)
         k = ops.linear(key.reshape(T * R, E), a.in_proj_weight[E:2 * E], a.in_proj_bias[E:2 * E])
         v = ops.linear(value.reshape(T * R, E), a.in_proj_weight[2 * E:], a.in_proj_bias[2 * E:])
-        q = q.view(L, R * H, d).transpose(0, 1)              # (R H, L, d): torch's head layout
-        k = k.view(T, R * H, d).transpose(0, 1)
-        v = v.view(T, R * H, d).transpose(0, 1)
+        # reshape, not view: ops.linear returns a column slice of its padded output when E is no multiple of 32
+        q = q.reshape(L, R * H, d).transpose(0, 1)           # (R H, L, d): torch's head layout
+        k = k.reshape(T, R * H, d).transpose(0, 1)
+        v = v.reshape(T, R * H, d).transpose(0, 1)
         p = torch.softmax(torch.bmm(q, k.transpose(1, 2)), dim=-1)      # (R H, L, T)
         if self.training and a.dropout > 0:
             p = F.dropout(p, p=a.dropout)
         ctx = torch.bmm(p, v).transpose(0, 1).reshape(L * R, E)
-        out = ops.linear(ctx, a.out_proj.weight, a.out_proj.bias).view(L, R, E)
+        out = ops.linear(ctx, a.out_proj.weight, a.out_proj.bias).reshape(L, R, E)
         return out, p.view(R, H, L, T).mean(dim=1)
 
 

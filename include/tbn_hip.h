@@ -417,7 +417,11 @@ int tbn_spatial_mean_bwd(const float* dout, int dout_ld, float* din, int din_ld,
  * padded to out_ld. pe is (pe_dim, t) row-major. */
 int tbn_pe_concat_fwd(const float* feat, int feat_ld, const float* pe, float* out, int out_ld, int r, int t, int c,
                       int pe_dim, void* stream);
-/* nn.GroupNorm(groups, c) over (r, t, c) rows (model.py:62-67 pe.2) */
+/* nn.GroupNorm(groups, c) over (r, t, c) rows (model.py:62-67 pe.2).  c % groups == 0 and the channels per group
+ * c / groups must be 4 * 2^k with k in 0..6 (4, 8, 16, ... 256: a group is a power-of-two run of float4 lanes inside one
+ * wave); any c, t >= 1.  Anything else: TBN_ERR_ARG with a message naming groupnorm.  save_mean / save_rstd (r * groups
+ * each) are the group mean and 1 / sqrt(var + eps), var = mean of the squared deviations FROM that mean (computed in a pass
+ * of its own after the mean, so a large common offset of x costs no accuracy). */
 int tbn_groupnorm_fwd(const float* x, float* y, const float* gamma, const float* beta, float* save_mean,
                       float* save_rstd, int r, int t, int c, int groups, float eps, void* stream);
 /* dgamma_part / dbeta_part: (r, c) per-sample partials, reduce with tbn_colsum */
@@ -430,7 +434,11 @@ int tbn_colsum(const float* x, int x_ld, float* out, int rows, int cols, void* s
  * kv (r,t,2e) = [k | v] projections.  drop_mask (r,heads,t) holds 0 or 1/(1-p), NULL in eval.
  * Outputs: ctx (r,e) (input of out_proj); probs, 2*r*heads*t floats = pre-dropout softmax (saved
  * for backward) followed by the post-dropout weights; avg_w (r,t) head-mean of the post-dropout
- * weights (what nn.MultiheadAttention returns). */
+ * weights (what nn.MultiheadAttention returns).
+ * Limits (forward and backward): 1 <= t <= 32 keys (the scores of a (sample, head) live in registers), e % heads == 0 and
+ * head_dim = e / heads a multiple of 4 (any size: lanes walk it 256 floats at a time); anything else returns TBN_ERR_ARG
+ * with a message naming mha_q1 -- core/models/attention.py sends such calls down its general path instead.
+ * tbn_mha_q1_bwd: davg_w may be NULL (no gradient through the returned weights); dctx may not. */
 int tbn_mha_q1_fwd(const float* q, const float* kv, const float* drop_mask, float* ctx, float* probs, float* avg_w,
                    int r, int t, int e, int heads, float scale, void* stream);
 int tbn_mha_q1_bwd(const float* dctx, const float* davg_w, const float* q, const float* kv, const float* probs,
