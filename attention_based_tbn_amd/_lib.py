@@ -147,6 +147,8 @@ SIGNATURES = {
     "tbn_opt_sgd_step": (c_i, [C.POINTER(OptTensor), c_i, c_f, c_f, c_f, c_fp, c_fp]),
     "tbn_topk_correct": (c_i, [c_fp, c_i, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp]),
     "tbn_frames_to_tensor": (c_i, [c_fp] + [c_i] * 16 + [c_fp, c_fp, c_i, c_i, c_fp, c_fp]),
+    "tbn_frames_to_tensor_crops": (c_i, [c_fp] + [c_i] * 10 + [C.POINTER(c_i), C.POINTER(c_i)] + [c_i] * 5 +
+                                   [c_fp, c_fp, c_i, c_i, c_fp, c_fp]),
 }
 
 _lib = None

@@ -39,6 +39,8 @@ int tbn_version(void);
 /* bit 2: pre-split bf16 weight planes are honoured -- conv flag 128 with the pointwise (1x1) split-bf16 kernel,
  * tbn_conv_split_weights / tbn_backbone_split_weights, TBN_BACKBONE_CONV_BF16X_ALL and tbn_backbone_params.weight_planes */
 #define TBN_CAP_CONV_BF16X_PLANES 2
+/* bit 3: tbn_frames_to_tensor_crops (several crop windows, optionally paired with their mirror images, in one launch) */
+#define TBN_CAP_FRAMES_CROPS 4
 int tbn_capabilities(void);
 const char* tbn_last_error(void);
 
@@ -522,6 +524,25 @@ int tbn_frames_to_tensor(const unsigned char* frames, int n_img, int height, int
                          int box_y, int box_w, int box_h, int resized_w, int resized_h, int crop_x, int crop_y,
                          int out_w, int out_h, int flip, int stack, const float* mean, const float* std_dev,
                          int n_stat, int div255, float* out, void* stream);
+/* The same pass with FixedCrop (reference core/dataset/transform.py:106-179, the multi-crop test-time augmentation) in
+ * place of the single window, followed by Stack (transform.py:415-461).  crop_x / crop_y: HOST arrays of n_crops window
+ * origins inside the resized box, copied into the launch arguments; 1 <= n_crops <= TBN_FRAMES_MAX_CROPS, a design
+ * limit (the reference has five locations).  mirror: 0 = windows as given, 1 = every window mirrored (the `flip` of
+ * tbn_frames_to_tensor), 2 = every window followed by its mirror image (horizontal_flip=True), 3 = every window's
+ * mirror image followed by the window (what horizontal_flip=True makes of frames that were flipped beforehand).
+ * Order = the reference's: FixedCrop emits a flat list, entry j = (window * n_img + image) * F + f with F = 2 for
+ * mirror >= 2 (f = 1: the second of the pair) and F = 1 otherwise; Stack makes `stack` CONSECUTIVE entries the channels
+ * of one sample, so output sample s, stack slot u holds entry j = s * stack + u.  With stack > 1 and a mirror pair
+ * (Flow) a sample therefore alternates plain and mirrored images of neighbouring frames -- the reference's behaviour,
+ * reproduced as is.  out: (n_img * n_crops * F / stack, channels * stack, out_h, out_w) fp32.  Refused before any
+ * launch: n_img * n_crops * F not a multiple of stack, a window outside the resized box, n_crops outside
+ * 1..TBN_FRAMES_MAX_CROPS, and whatever tbn_frames_to_tensor refuses.  Ask tbn_capabilities() & TBN_CAP_FRAMES_CROPS. */
+#define TBN_FRAMES_MAX_CROPS 16
+int tbn_frames_to_tensor_crops(const unsigned char* frames, int n_img, int height, int width, int channels, int box_x,
+                               int box_y, int box_w, int box_h, int resized_w, int resized_h, const int* crop_x,
+                               const int* crop_y, int n_crops, int out_w, int out_h, int mirror, int stack,
+                               const float* mean, const float* std_dev, int n_stat, int div255, float* out,
+                               void* stream);
 
 #ifdef __cplusplus
 }
