@@ -128,6 +128,11 @@ SIGNATURES = {
     "tbn_colsum": (c_i, [c_fp, c_i, c_fp, c_i, c_i, c_fp]),
     "tbn_mha_q1_fwd": (c_i, [c_fp] * 6 + [c_i] * 4 + [c_f, c_fp]),
     "tbn_mha_q1_bwd": (c_i, [c_fp] * 8 + [c_i] * 4 + [c_f, c_fp]),
+    "tbn_mha_fwd": (c_i, [c_fp, c_i, c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_i, c_fp, c_fp] + [c_i] * 5 + [c_f, c_fp]),
+    "tbn_mha_bwd": (c_i, [c_fp, c_i, c_fp, c_fp, c_i, c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_fp, c_i, c_fp,
+                          c_i] + [c_i] * 5 + [c_f, c_fp]),
+    "tbn_attn_weights_fwd": (c_i, [c_fp, c_i, c_fp, c_f, c_i, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp]),
+    "tbn_attn_weights_bwd": (c_i, [c_fp, c_fp, c_fp, c_f, c_fp, c_i, c_i, c_i, c_fp]),
     "tbn_weighted_sum_fwd": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp]),
     "tbn_weighted_sum_bwd": (c_i, [c_fp, c_i, c_fp, c_fp, c_i, c_i, c_i, c_fp]),
     "tbn_segment_mean_fwd": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp]),

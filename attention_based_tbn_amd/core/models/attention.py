@@ -11,7 +11,6 @@ import math
 import numpy as np
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from ... import ops
 
@@ -76,7 +75,8 @@ class _MHAParams(nn.Module):
 
 class MultiheadedAttention(nn.Module):
     """torch.nn.MultiheadAttention(embed_dim, heads, dropout, bias=True) restricted to what the TBN
-    uses: ONE query per sample, key == value (reference model.py:231-237)."""
+    uses: ONE query per sample, key == value (reference model.py:231-237); `forward` takes every other shape through the
+    general attention core."""
 
     def __init__(self, embed_dim, num_heads, dropout=0.0):
         super().__init__()
@@ -99,7 +99,10 @@ class MultiheadedAttention(nn.Module):
         torch.nn.MultiheadAttention (reference attention.py:48-57).  The TBN's own call -- ONE query per sample, key is value
         (model.py:231-237) -- runs on the wavefront-reduction kernel when that kernel takes the shape (tbn_mha_q1_fwd: at most
         32 keys, head_dim a multiple of 4); any other call takes the general path: the three projections and the output
-        projection on the HIP GEMM, the (tiny) score / softmax / weighted-sum core as batched torch-ROCm ops."""
+        projection on the HIP GEMM, scores / softmax / dropout / weighted sum on the general attention core (ops.mha_core,
+        tbn_mha_fwd: any number of queries, up to 1024 keys, any head_dim).  In training the dropout mask of the general
+        path is drawn as on the one-query path, from ONE uniform tensor of shape (R, heads, L, T) (ops.dropout_mask):
+        the same distribution as torch's functional dropout, other draws for a given seed."""
         a = self.attention_layer
         if (key is value and query.shape[0] == 1 and 1 <= key.shape[0] <= 32
                 and (a.embed_dim // a.num_heads) % 4 == 0):
@@ -109,20 +112,21 @@ class MultiheadedAttention(nn.Module):
         L, R, _ = query.shape
         T = key.shape[0]
         assert key.shape[1] == R and value.shape[:2] == key.shape[:2] and query.shape[2] == E
-        d = E // H
-        q = ops.linear(query.reshape(L * R, E), a.in_proj_weight[:E], a.in_proj_bias[:E]) * (float(d) ** -0.5)
+        # ops.linear returns a column slice of its padded output when E is no multiple of 32: the core takes row pitches
+        q = ops.linear(query.reshape(L * R, E), a.in_proj_weight[:E], a.in_proj_bias[:E])
         k = ops.linear(key.reshape(T * R, E), a.in_proj_weight[E:2 * E], a.in_proj_bias[E:2 * E])
         v = ops.linear(value.reshape(T * R, E), a.in_proj_weight[2 * E:], a.in_proj_bias[2 * E:])
-        # reshape, not view: ops.linear returns a column slice of its padded output when E is no multiple of 32
-        q = q.reshape(L, R * H, d).transpose(0, 1)           # (R H, L, d): torch's head layout
-        k = k.reshape(T, R * H, d).transpose(0, 1)
-        v = v.reshape(T, R * H, d).transpose(0, 1)
-        p = torch.softmax(torch.bmm(q, k.transpose(1, 2)), dim=-1)      # (R H, L, T)
-        if self.training and a.dropout > 0:
-            p = F.dropout(p, p=a.dropout)
-        ctx = torch.bmm(p, v).transpose(0, 1).reshape(L * R, E)
+        mask = ops.dropout_mask((R, H, L, T), a.dropout, self.training, query.device)
+        ctx, w = ops.mha_core(q, k, v, mask, H, L, T, R)
         out = ops.linear(ctx, a.out_proj.weight, a.out_proj.bias).reshape(L, R, E)
-        return out, p.view(R, H, L, T).mean(dim=1)
+        return out, w
+
+
+def _exp_noise(logits):
+    """the Exp(1) draw of torch's gumbel_softmax, made exactly as torch makes it (torch/nn/functional.py), so a seed
+    consumes the RNG stream as it did when these modules called that function; -log and the rest run in
+    ops.attn_weights"""
+    return torch.empty_like(logits, memory_format=torch.legacy_contiguous_format).exponential_()
 
 
 class UniModalAttention(nn.Module):
@@ -139,9 +143,9 @@ class UniModalAttention(nn.Module):
         """vis (R, C); seq (R, T, C) native layout"""
         logits = self._logits(vis)
         if self.training and self.use_gumbel:
-            w = F.gumbel_softmax(logits, tau=self.temperature, hard=self.one_hot)
+            w = ops.attn_weights(logits, _exp_noise(logits), self.temperature, self.one_hot)
         else:
-            w = F.softmax(logits, dim=1)
+            w = ops.attn_weights(logits)
         return ops.weighted_sum(seq, w), w
 
     def forward(self, input1, input2):
@@ -165,10 +169,9 @@ class PrototypeAttention(nn.Module):
         h = ops.linear(vis, self.seq[0].weight, self.seq[0].bias, relu=True)
         logits = ops.linear(h, self.seq[2].weight, self.seq[2].bias)
         if self.training and self.use_gumbel:
-            m = F.gumbel_softmax(logits, tau=self.temperature, hard=True)
+            w = ops.attn_weights(logits, _exp_noise(logits), self.temperature, True, self.prototype_wts)
         else:
-            m = F.softmax(logits, dim=1)
-        w = torch.matmul(m, self.prototype_wts)
+            w = ops.attn_weights(logits, protos=self.prototype_wts)
         return ops.weighted_sum(seq, w), w
 
     def forward(self, input1, input2):

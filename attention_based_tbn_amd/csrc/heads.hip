@@ -1,8 +1,10 @@
 // Mid-level fusion heads for gfx950: positional-encoding concat, GroupNorm, the L_q = 1
 // multi-head attention core (one 64-lane wave per (sample, head): dot products and the softmax
-// are wavefront reductions), fixed-attention weighted sum, temporal-consensus mean.
+// are wavefront reductions), the general attention core (any number of queries, up to 1024 keys, scores in LDS), the
+// attention-weight softmax of the learnt variants (gumbel noise, straight-through one-hot, prototype mix),
+// fixed-attention weighted sum, temporal-consensus mean.
 //
-// Reference: core/models/attention.py:8-57, core/models/model.py:62-67,178-203,224-237.
+// Reference: core/models/attention.py:8-145, core/models/model.py:62-67,178-203,224-237.
 // All tensors are row-major with channels fastest: audio sequence (r, t, c), features (r, c).
 #include "tbn_common.h"
 #include "../../include/tbn_hip.h"
@@ -300,6 +302,239 @@ __global__ __launch_bounds__(256) void mha_q1_bwd_kernel(const float* __restrict
   }
 }
 
+// ---------------------------------------------------------------- MHA core, general shape
+// One wave (a 64-thread workgroup) per (sample, head, query).  A lane owns the keys lane, lane + 64, ... for everything
+// that is per key (scores, softmax, score gradients) and the head dims lane, lane + 64, ... for everything that is per
+// dim (context, dq); the per-key values cross from one ownership to the other through LDS.  Plain float loads only: rows
+// may start at any float (column slices of padded buffers) and head_dim may be odd.
+#define MHA_MAXT 1024
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+
+__global__ __launch_bounds__(64) void mha_fwd_kernel(const float* __restrict__ q, int q_ld, const float* __restrict__ k,
+                                                     int k_ld, const float* __restrict__ v, int v_ld,
+                                                     const float* __restrict__ drop, float* __restrict__ ctx, int ctx_ld,
+                                                     float* __restrict__ probs, float* __restrict__ pdrop_out, int L,
+                                                     int T, int R, int E, int heads, float scale) {
+  __shared__ float sc[MHA_MAXT];
+  const int lane = threadIdx.x;
+  const int wid = blockIdx.x;  // (r, h, i), i fastest: the row order of probs
+  const int i = wid % L, rh = wid / L;
+  const int h = rh % heads, r = rh / heads;
+  const int d = E / heads;
+  const float* qrow = q + ((size_t)i * R + r) * q_ld + h * d;
+  float mx = -INFINITY;
+  for (int t = lane; t < T; t += 64) {
+    const float* krow = k + ((size_t)t * R + r) * k_ld + h * d;
+    float s = 0.f;
+    for (int j = 0; j < d; ++j) s = fmaf(qrow[j], krow[j], s);
+    s *= scale;
+    sc[t] = s;
+    mx = fmaxf(mx, s);
+  }
+  mx = wave_max(mx);
+  float den = 0.f;
+  for (int t = lane; t < T; t += 64) {
+    const float e = expf(sc[t] - mx);
+    sc[t] = e;
+    den += e;
+  }
+  const float inv = 1.f / wave_sum(den);
+  const size_t po = (size_t)wid * T;
+  for (int t = lane; t < T; t += 64) {
+    const float p = sc[t] * inv;
+    const float pd = drop ? p * drop[po + t] : p;
+    probs[po + t] = p;
+    pdrop_out[po + t] = pd;
+    sc[t] = pd;
+  }
+  __syncthreads();
+  float* crow = ctx + ((size_t)i * R + r) * ctx_ld + h * d;
+  for (int j = lane; j < d; j += 64) {
+    const float* vcol = v + (size_t)r * v_ld + h * d + j;
+    float acc = 0.f;
+    for (int t = 0; t < T; ++t) acc = fmaf(sc[t], vcol[(size_t)t * R * v_ld], acc);
+    crow[j] = acc;
+  }
+}
+
+// avg_w[r][i][t] = mean_h pdrop[r][h][i][t]
+__global__ __launch_bounds__(256) void mha_head_mean_kernel(const float* __restrict__ pd, float* __restrict__ avg, int R,
+                                                            int LT, int heads) {
+  const size_t n = (size_t)R * LT;
+  for (size_t o = (size_t)blockIdx.x * 256 + threadIdx.x; o < n; o += (size_t)gridDim.x * 256) {
+    const size_t r = o / LT, it = o - r * LT;
+    float s = 0.f;
+    for (int h = 0; h < heads; ++h) s += pd[(r * heads + h) * LT + it];
+    avg[o] = s / (float)heads;
+  }
+}
+
+// first backward launch, same mapping as the forward: the score gradients ds (r,heads,l,t) and dq
+__global__ __launch_bounds__(64) void mha_bwd_scores_kernel(const float* __restrict__ dctx, int dctx_ld,
+                                                            const float* __restrict__ davg, const float* __restrict__ k,
+                                                            int k_ld, const float* __restrict__ v, int v_ld,
+                                                            const float* __restrict__ probs,
+                                                            const float* __restrict__ drop, float* __restrict__ dscores,
+                                                            float* __restrict__ dq, int dq_ld, int L, int T, int R, int E,
+                                                            int heads, float scale) {
+  __shared__ float ds[MHA_MAXT];
+  const int lane = threadIdx.x;
+  const int wid = blockIdx.x;
+  const int i = wid % L, rh = wid / L;
+  const int h = rh % heads, r = rh / heads;
+  const int d = E / heads;
+  const float* dcrow = dctx + ((size_t)i * R + r) * dctx_ld + h * d;
+  const size_t po = (size_t)wid * T;
+  float dot = 0.f;
+  for (int t = lane; t < T; t += 64) {
+    const float* vrow = v + ((size_t)t * R + r) * v_ld + h * d;
+    float g = 0.f;  // gradient wrt the post-dropout weight: dctx_h . v[t] (+ the head-mean's share)
+    for (int j = 0; j < d; ++j) g = fmaf(dcrow[j], vrow[j], g);
+    if (davg) g += davg[((size_t)r * L + i) * T + t] / (float)heads;
+    if (drop) g *= drop[po + t];  // gradient wrt the pre-dropout softmax output
+    ds[t] = g;
+    dot += probs[po + t] * g;
+  }
+  dot = wave_sum(dot);
+  for (int t = lane; t < T; t += 64) {
+    const float s = scale * probs[po + t] * (ds[t] - dot);
+    ds[t] = s;
+    dscores[po + t] = s;
+  }
+  __syncthreads();
+  float* dqrow = dq + ((size_t)i * R + r) * dq_ld + h * d;
+  for (int j = lane; j < d; j += 64) {
+    const float* kcol = k + (size_t)r * k_ld + h * d + j;
+    float acc = 0.f;
+    for (int t = 0; t < T; ++t) acc = fmaf(ds[t], kcol[(size_t)t * R * k_ld], acc);
+    dqrow[j] = acc;
+  }
+}
+
+// second backward launch: one thread per (key, head dim) of a (sample, head) sums over the queries in query order --
+// dk[t] = sum_i ds[i][t] * q[i], dv[t] = sum_i pdrop[i][t] * dctx[i]
+__global__ __launch_bounds__(256) void mha_bwd_kv_kernel(const float* __restrict__ dctx, int dctx_ld,
+                                                         const float* __restrict__ q, int q_ld,
+                                                         const float* __restrict__ dscores,
+                                                         const float* __restrict__ pdrop, float* __restrict__ dk,
+                                                         int dk_ld, float* __restrict__ dv, int dv_ld, int L, int T, int R,
+                                                         int E, int heads) {
+  const int rh = blockIdx.x;
+  const int h = rh % heads, r = rh / heads;
+  const int d = E / heads;
+  const size_t n = (size_t)T * d;
+  for (size_t o = (size_t)blockIdx.y * 256 + threadIdx.x; o < n; o += (size_t)gridDim.y * 256) {
+    const int t = (int)(o / d), j = (int)(o - (size_t)t * d);
+    float ak = 0.f, av = 0.f;
+    for (int i = 0; i < L; ++i) {
+      const size_t po = ((size_t)rh * L + i) * T + t;
+      const size_t row = (size_t)i * R + r;
+      ak = fmaf(dscores[po], q[row * q_ld + h * d + j], ak);
+      av = fmaf(pdrop[po], dctx[row * dctx_ld + h * d + j], av);
+    }
+    const size_t krow = (size_t)t * R + r;
+    dk[krow * dk_ld + h * d + j] = ak;
+    dv[krow * dv_ld + h * d + j] = av;
+  }
+}
+
+// ---------------------------------------------------------------- attention-weight softmax (+ gumbel, + prototypes)
+// One wave (a 64-thread workgroup) per row; the row's k values live in LDS.
+#define AW_MAXK 1024
+
+__global__ __launch_bounds__(64) void attn_weights_fwd_kernel(const float* __restrict__ logits, int ld,
+                                                              const float* __restrict__ noise, float tau, int hard,
+                                                              const float* __restrict__ protos, float* __restrict__ soft,
+                                                              float* __restrict__ w, int K, int T) {
+  __shared__ float m[AW_MAXK];
+  const int lane = threadIdx.x;
+  const size_t r = blockIdx.x;
+  float mx = -INFINITY;
+  for (int c = lane; c < K; c += 64) {
+    float z = logits[r * ld + c];
+    if (noise) z += -logf(noise[r * K + c]);
+    z /= tau;
+    m[c] = z;
+    mx = fmaxf(mx, z);
+  }
+  mx = wave_max(mx);
+  float den = 0.f;
+  for (int c = lane; c < K; c += 64) {
+    const float e = expf(m[c] - mx);
+    m[c] = e;
+    den += e;
+  }
+  const float inv = 1.f / wave_sum(den);
+  float best = -INFINITY;
+  int arg = K;
+  for (int c = lane; c < K; c += 64) {
+    const float s = m[c] * inv;
+    m[c] = s;
+    soft[r * K + c] = s;
+    if (s > best) {  // ascending c: the first index keeps a tie
+      best = s;
+      arg = c;
+    }
+  }
+  if (hard) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ob = __shfl_xor(best, o);
+      const int oa = __shfl_xor(arg, o);
+      if (ob > best || (ob == best && oa < arg)) {
+        best = ob;
+        arg = oa;
+      }
+    }
+    for (int c = lane; c < K; c += 64) {
+      const float s = m[c];
+      m[c] = ((c == arg ? 1.f : 0.f) - s) + s;
+    }
+  }
+  if (!protos) {
+    for (int c = lane; c < K; c += 64) w[r * K + c] = m[c];
+    return;
+  }
+  __syncthreads();
+  for (int j = lane; j < T; j += 64) {
+    float acc = 0.f;
+    for (int c = 0; c < K; ++c) acc = fmaf(m[c], protos[(size_t)c * T + j], acc);
+    w[r * T + j] = acc;
+  }
+}
+
+__global__ __launch_bounds__(64) void attn_weights_bwd_kernel(const float* __restrict__ dw, const float* __restrict__ soft,
+                                                              const float* __restrict__ protos, float tau,
+                                                              float* __restrict__ dlogits, int K, int T) {
+  __shared__ float g[AW_MAXK];   // the row of dw
+  __shared__ float dm[AW_MAXK];
+  const int lane = threadIdx.x;
+  const size_t r = blockIdx.x;
+  const int W = protos ? T : K;
+  for (int j = lane; j < W; j += 64) g[j] = dw[r * W + j];
+  __syncthreads();
+  float dot = 0.f;
+  for (int c = lane; c < K; c += 64) {
+    float a;
+    if (protos) {
+      a = 0.f;
+      const float* prow = protos + (size_t)c * T;
+      for (int j = 0; j < T; ++j) a = fmaf(g[j], prow[j], a);
+    } else {
+      a = g[c];
+    }
+    dm[c] = a;
+    dot += a * soft[r * K + c];
+  }
+  dot = wave_sum(dot);
+  for (int c = lane; c < K; c += 64) dlogits[r * K + c] = soft[r * K + c] * (dm[c] - dot) / tau;
+}
+
 // ---------------------------------------------------------------- fixed attention, consensus, masks
 __global__ __launch_bounds__(256) void weighted_sum_fwd_kernel(const float* __restrict__ feat,
                                                                const float* __restrict__ w, float* __restrict__ out,
@@ -569,6 +804,73 @@ int tbn_mha_q1_bwd(const float* dctx, const float* davg_w, const float* q, const
     TBN_KLAUNCH((mha_q1_bwd_kernel<32>), dim3(blocks), dim3(256), 0, st, dctx, davg_w, q, kv, probs, drop_mask,
                        dq, dkv, r, t, e, heads, scale);
   TBN_CHECK_LAUNCH("mha_q1_bwd");
+  return TBN_OK;
+}
+
+static int mha_ok(int l, int t, int r, int e, int heads) {
+  return l >= 1 && t >= 1 && t <= MHA_MAXT && r >= 1 && heads >= 1 && e >= heads && e % heads == 0 &&
+         (long long)r * heads * l * t < (1ll << 31);
+}
+#define MHA_LIMITS "mha: need L >= 1, 1 <= T <= 1024, R >= 1, heads >= 1, E %% heads == 0 and R*heads*L*T < 2^31"
+
+int tbn_mha_fwd(const float* q, int q_ld, const float* k, int k_ld, const float* v, int v_ld, const float* drop_mask,
+                float* ctx, int ctx_ld, float* probs, float* avg_w, int l, int t, int r, int e, int heads, float scale,
+                void* stream) {
+  TBN_REQUIRE(q && k && v && ctx && probs && avg_w, "mha: null argument (only drop_mask may be NULL)");
+  TBN_REQUIRE(mha_ok(l, t, r, e, heads), MHA_LIMITS " (L = %d, T = %d, R = %d, E = %d, heads = %d)", l, t, r, e, heads);
+  TBN_REQUIRE(q_ld >= e && k_ld >= e && v_ld >= e && ctx_ld >= e, "mha: a leading dimension is smaller than E = %d", e);
+  hipStream_t st = (hipStream_t)stream;
+  float* pdrop = probs + (size_t)r * heads * l * t;
+  TBN_KLAUNCH(mha_fwd_kernel, dim3(r * heads * l), dim3(64), 0, st, q, q_ld, k, k_ld, v, v_ld, drop_mask, ctx, ctx_ld,
+              probs, pdrop, l, t, r, e, heads, scale);
+  TBN_CHECK_LAUNCH("mha_fwd");
+  TBN_KLAUNCH(mha_head_mean_kernel, dim3(ew_grid((size_t)r * l * t)), dim3(256), 0, st, pdrop, avg_w, r, l * t, heads);
+  TBN_CHECK_LAUNCH("mha_head_mean");
+  return TBN_OK;
+}
+
+int tbn_mha_bwd(const float* dctx, int dctx_ld, const float* davg_w, const float* q, int q_ld, const float* k, int k_ld,
+                const float* v, int v_ld, const float* probs, const float* drop_mask, float* dscores, float* dq, int dq_ld,
+                float* dk, int dk_ld, float* dv, int dv_ld, int l, int t, int r, int e, int heads, float scale,
+                void* stream) {
+  TBN_REQUIRE(dctx && q && k && v && probs && dscores && dq && dk && dv,
+              "mha: null argument (only davg_w and drop_mask may be NULL)");
+  TBN_REQUIRE(mha_ok(l, t, r, e, heads), MHA_LIMITS " (L = %d, T = %d, R = %d, E = %d, heads = %d)", l, t, r, e, heads);
+  TBN_REQUIRE(dctx_ld >= e && q_ld >= e && k_ld >= e && v_ld >= e && dq_ld >= e && dk_ld >= e && dv_ld >= e,
+              "mha: a leading dimension is smaller than E = %d", e);
+  hipStream_t st = (hipStream_t)stream;
+  const float* pdrop = probs + (size_t)r * heads * l * t;
+  TBN_KLAUNCH(mha_bwd_scores_kernel, dim3(r * heads * l), dim3(64), 0, st, dctx, dctx_ld, davg_w, k, k_ld, v, v_ld, probs,
+              drop_mask, dscores, dq, dq_ld, l, t, r, e, heads, scale);
+  TBN_CHECK_LAUNCH("mha_bwd_scores");
+  const size_t per = (size_t)t * (e / heads);
+  const int ny = (int)((per + 255) / 256 > 1024 ? 1024 : (per + 255) / 256);
+  TBN_KLAUNCH(mha_bwd_kv_kernel, dim3(r * heads, ny), dim3(256), 0, st, dctx, dctx_ld, q, q_ld, dscores, pdrop, dk, dk_ld,
+              dv, dv_ld, l, t, r, e, heads);
+  TBN_CHECK_LAUNCH("mha_bwd_kv");
+  return TBN_OK;
+}
+
+#define AW_LIMITS "attn_weights: need r >= 1, 1 <= k <= 1024, 1 <= t <= 1024 with prototypes, tau > 0"
+
+int tbn_attn_weights_fwd(const float* logits, int logits_ld, const float* noise, float tau, int hard, const float* protos,
+                         float* soft, float* w, int r, int k, int t, void* stream) {
+  TBN_REQUIRE(logits && soft && w, "attn_weights: null argument (only noise and protos may be NULL)");
+  TBN_REQUIRE(r >= 1 && k >= 1 && k <= AW_MAXK && (!protos || (t >= 1 && t <= AW_MAXK)) && tau > 0.f && logits_ld >= k,
+              AW_LIMITS " (r = %d, k = %d, t = %d, tau = %g, ld = %d)", r, k, t, (double)tau, logits_ld);
+  TBN_KLAUNCH(attn_weights_fwd_kernel, dim3(r), dim3(64), 0, (hipStream_t)stream, logits, logits_ld, noise, tau, hard,
+              protos, soft, w, k, t);
+  TBN_CHECK_LAUNCH("attn_weights_fwd");
+  return TBN_OK;
+}
+
+int tbn_attn_weights_bwd(const float* dw, const float* soft, const float* protos, float tau, float* dlogits, int r, int k,
+                         int t, void* stream) {
+  TBN_REQUIRE(dw && soft && dlogits, "attn_weights: null argument (only protos may be NULL)");
+  TBN_REQUIRE(r >= 1 && k >= 1 && k <= AW_MAXK && (!protos || (t >= 1 && t <= AW_MAXK)) && tau > 0.f,
+              AW_LIMITS " (r = %d, k = %d, t = %d, tau = %g)", r, k, t, (double)tau);
+  TBN_KLAUNCH(attn_weights_bwd_kernel, dim3(r), dim3(64), 0, (hipStream_t)stream, dw, soft, protos, tau, dlogits, k, t);
+  TBN_CHECK_LAUNCH("attn_weights_bwd");
   return TBN_OK;
 }
 

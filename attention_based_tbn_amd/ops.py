@@ -212,6 +212,116 @@ def mha_q1(q, kv, drop_mask, heads):
     return _MHAq1Fn.apply(q, kv, drop_mask, heads)
 
 
+def _rows(t):
+    """a float32 (rows, cols) matrix as the kernels take it: unit column stride, any row pitch (a column slice of a
+    padded GEMM output stays where it is)"""
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.dim() != 2 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t
+
+
+def _ld(t):
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+class _MHACoreFn(torch.autograd.Function):
+    """general attention core: q (L*R, E) rows i*R + r, k / v (T*R, E) rows t*R + r, drop_mask (R, H, L, T) or None
+    -> ctx (L*R, E), avg weights (R, L, T)   [reference attention.py:48-57]"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, drop_mask, heads, L, T, R):
+        _need_cuda(q, "mha_core")
+        _need_cuda(k, "mha_core")
+        _need_cuda(v, "mha_core")
+        q, k, v = _rows(q), _rows(k), _rows(v)
+        E = q.shape[1]
+        if q.shape[0] != L * R or k.shape != (T * R, E) or v.shape != (T * R, E):
+            raise TbnHipError(f"mha_core: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not match "
+                              f"L = {L}, T = {T}, R = {R}")
+        if drop_mask is not None:
+            if tuple(drop_mask.shape) != (R, heads, L, T):
+                raise TbnHipError(f"mha_core: drop_mask {tuple(drop_mask.shape)} is not (R, heads, L, T)")
+            drop_mask = _f32c(drop_mask)
+        scale = float(max(E // heads, 1)) ** -0.5
+        out = torch.empty(L * R, E, device=q.device, dtype=torch.float32)
+        probs = torch.empty(2, R, heads, L, T, device=q.device, dtype=torch.float32)
+        avg = torch.empty(R, L, T, device=q.device, dtype=torch.float32)
+        call("tbn_mha_fwd", ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(drop_mask), ptr(out), E, ptr(probs),
+             ptr(avg), L, T, R, E, heads, scale, stream_ptr())
+        ctx.dims, ctx.scale = (heads, L, T, R, E), scale
+        ctx.save_for_backward(q, k, v, probs, drop_mask)
+        return out, avg
+
+    @staticmethod
+    def backward(ctx, dctx, davg):
+        q, k, v, probs, drop = ctx.saved_tensors
+        heads, L, T, R, E = ctx.dims
+        dctx = _rows(dctx) if dctx is not None else torch.zeros(L * R, E, device=q.device, dtype=torch.float32)
+        davg = _f32c(davg) if davg is not None else None
+        dq = torch.empty(L * R, E, device=q.device, dtype=torch.float32)
+        dk = torch.empty(T * R, E, device=q.device, dtype=torch.float32)
+        dv = torch.empty_like(dk)
+        ds = torch.empty(R * heads * L * T, device=q.device, dtype=torch.float32)
+        call("tbn_mha_bwd", ptr(dctx), _ld(dctx), ptr(davg), ptr(q), _ld(q), ptr(k), _ld(k), ptr(v), _ld(v), ptr(probs),
+             ptr(drop), ptr(ds), ptr(dq), E, ptr(dk), E, ptr(dv), E, L, T, R, E, heads, ctx.scale, stream_ptr())
+        return dq, dk, dv, None, None, None, None, None
+
+
+def mha_core(q, k, v, drop_mask, heads, L, T, R):
+    """torch.nn.MultiheadAttention between the input projections and out_proj, for any number of queries L, up to 1024
+    keys T and any head_dim (tbn_mha_fwd / tbn_mha_bwd); q arrives unscaled.  Returns (ctx (L*R, E), avg_w (R, L, T))."""
+    return _MHACoreFn.apply(q, k, v, drop_mask, heads, L, T, R)
+
+
+class _AttnWeightsFn(torch.autograd.Function):
+    """softmax / gumbel-softmax attention weights, optionally mixed through the prototype matrix, one launch per direction
+    [reference attention.py:60-91, :94-145]"""
+
+    @staticmethod
+    def forward(ctx, logits, noise, tau, hard, protos):
+        _need_cuda(logits, "attn_weights")
+        logits = _rows(logits)
+        R, K = logits.shape
+        if noise is not None:
+            _need_cuda(noise, "attn_weights")
+            if tuple(noise.shape) != (R, K):
+                raise TbnHipError(f"attn_weights: noise {tuple(noise.shape)} does not match logits {(R, K)}")
+            noise = _f32c(noise)
+        T = 0
+        if protos is not None:
+            _need_cuda(protos, "attn_weights")
+            if protos.dim() != 2 or protos.shape[0] != K:
+                raise TbnHipError(f"attn_weights: protos {tuple(protos.shape)} does not have k = {K} rows")
+            protos = _f32c(protos)
+            T = protos.shape[1]
+        soft = torch.empty(R, K, device=logits.device, dtype=torch.float32)
+        w = torch.empty(R, T if protos is not None else K, device=logits.device, dtype=torch.float32)
+        call("tbn_attn_weights_fwd", ptr(logits), _ld(logits), ptr(noise), float(tau), int(bool(hard)), ptr(protos),
+             ptr(soft), ptr(w), R, K, T, stream_ptr())
+        ctx.tau = float(tau)
+        ctx.save_for_backward(soft, protos)
+        return w
+
+    @staticmethod
+    def backward(ctx, dw):
+        soft, protos = ctx.saved_tensors
+        R, K = soft.shape
+        dw = _f32c(dw)
+        dlogits = torch.empty_like(soft)
+        call("tbn_attn_weights_bwd", ptr(dw), ptr(soft), ptr(protos), ctx.tau, ptr(dlogits), R, K,
+             protos.shape[1] if protos is not None else 0, stream_ptr())
+        return dlogits, None, None, None, None
+
+
+def attn_weights(logits, noise=None, tau=1.0, hard=False, protos=None):
+    """w = m @ protos (or m), m = softmax((logits - log(noise)) / tau), with hard=True its straight-through one-hot
+    (F.gumbel_softmax's value and gradient rule); `noise` are Exp(1) samples or None for the plain softmax.  `protos`
+    (k, t) is a buffer and gets no gradient."""
+    return _AttnWeightsFn.apply(logits, noise, tau, hard, protos)
+
+
 class _WeightedSumFn(torch.autograd.Function):
     """fixed attention: out[r] = sum_t feat[r,t] * w[r,t]   [reference model.py:224-228]"""
 

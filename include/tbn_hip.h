@@ -41,6 +41,9 @@ int tbn_version(void);
 #define TBN_CAP_CONV_BF16X_PLANES 2
 /* bit 3: tbn_frames_to_tensor_crops (several crop windows, optionally paired with their mirror images, in one launch) */
 #define TBN_CAP_FRAMES_CROPS 4
+/* bit 4: the general attention core (tbn_mha_fwd / tbn_mha_bwd: any number of queries, up to 1024 keys, any head_dim) and
+ * the attention-weight softmax (tbn_attn_weights_fwd / tbn_attn_weights_bwd) */
+#define TBN_CAP_ATTN_GENERAL 8
 int tbn_capabilities(void);
 const char* tbn_last_error(void);
 
@@ -446,6 +449,43 @@ int tbn_mha_q1_fwd(const float* q, const float* kv, const float* drop_mask, floa
 int tbn_mha_q1_bwd(const float* dctx, const float* davg_w, const float* q, const float* kv, const float* probs,
                    const float* drop_mask, float* dq, float* dkv, int r, int t, int e, int heads, float scale,
                    void* stream);
+/* torch.nn.MultiheadAttention core, general shape (attention.py:48-57): l queries and t keys per sample, key and value
+ * projected separately, any head_dim.  One wave per (sample, head, query); the scores of a query live in LDS.
+ * q (l*r rows, row i*r + s) projected queries, unscaled (scores = scale * q.k, scale = head_dim^-0.5); k, v (t*r rows, row
+ * j*r + s) projected keys / values.  Every matrix has its own leading dimension (floats between rows, >= e) and needs
+ * neither contiguous nor 16-byte aligned rows: k and v may be two column ranges of one buffer.  drop_mask (r,heads,l,t)
+ * holds 0 or 1/(1-p), NULL in eval.
+ * Outputs: ctx (l*r rows, ctx_ld; input of out_proj); probs, 2*r*heads*l*t floats = pre-dropout softmax (r,heads,l,t),
+ * saved for backward, followed by the post-dropout weights; avg_w (r,l,t) head mean of the post-dropout weights.
+ * tbn_mha_bwd: dctx (l*r rows, dctx_ld); davg_w (r,l,t) may be NULL; dscores is caller-owned scratch of r*heads*l*t
+ * floats (the score gradients, written by the first launch and read by the second).  dq / dk / dv are written, not
+ * accumulated; the sum over the l queries into dk / dv runs inside one thread in query order (no atomics: same bits every
+ * run).
+ * Limits: l >= 1, 1 <= t <= 1024, r >= 1, heads >= 1, e % heads == 0 (any head_dim >= 1), r*heads*l*t < 2^31, leading
+ * dimensions >= e; anything else, or a NULL required pointer, returns TBN_ERR_ARG with a message naming mha and writes
+ * nothing. */
+int tbn_mha_fwd(const float* q, int q_ld, const float* k, int k_ld, const float* v, int v_ld, const float* drop_mask,
+                float* ctx, int ctx_ld, float* probs, float* avg_w, int l, int t, int r, int e, int heads, float scale,
+                void* stream);
+int tbn_mha_bwd(const float* dctx, int dctx_ld, const float* davg_w, const float* q, int q_ld, const float* k, int k_ld,
+                const float* v, int v_ld, const float* probs, const float* drop_mask, float* dscores, float* dq, int dq_ld,
+                float* dk, int dk_ld, float* dv, int dv_ld, int l, int t, int r, int e, int heads, float scale,
+                void* stream);
+/* Attention weights of the learnt single-modality and prototype variants (attention.py:60-91 UniModalAttention,
+ * :94-145 PrototypeAttention) in one launch per direction -- F.softmax / F.gumbel_softmax plus the prototype mix.
+ * logits (r,k) with leading dimension logits_ld; noise (r,k) contiguous Exp(1) samples or NULL; protos (k,t) row-major or
+ * NULL.  g = -log(noise) (0 without noise); soft = softmax((logits + g) / tau) over k;
+ * m = hard ? (onehot(argmax soft) - soft) + soft : soft, evaluated in that fp32 order (the value
+ * F.gumbel_softmax(hard=True) returns), the first index winning ties; w = protos ? m @ protos : m.
+ * Writes soft (r,k) (saved for backward) and w (r, protos ? t : k), both contiguous.
+ * tbn_attn_weights_bwd is F.gumbel_softmax's straight-through rule (the gradient flows through soft only):
+ * dm = protos ? dw @ protos^T : dw; dlogits = soft * (dm - sum_k(dm * soft)) / tau, dlogits (r,k) contiguous.
+ * Limits: r >= 1, 1 <= k <= 1024, 1 <= t <= 1024 (t is ignored without protos), tau > 0; anything else, or a NULL required
+ * pointer, returns TBN_ERR_ARG with a message naming attn_weights and writes nothing.  One wave per row. */
+int tbn_attn_weights_fwd(const float* logits, int logits_ld, const float* noise, float tau, int hard, const float* protos,
+                         float* soft, float* w, int r, int k, int t, void* stream);
+int tbn_attn_weights_bwd(const float* dw, const float* soft, const float* protos, float tau, float* dlogits, int r, int k,
+                         int t, void* stream);
 /* fixed attention (model.py:224-228): out[r][c] = sum_t feat[r][t][c] * w[r][t] */
 int tbn_weighted_sum_fwd(const float* feat, const float* w, float* out, int out_ld, int r, int t, int c, void* stream);
 int tbn_weighted_sum_bwd(const float* dout, int dout_ld, const float* w, float* dfeat, int r, int t, int c,
