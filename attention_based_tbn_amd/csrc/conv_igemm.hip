@@ -1227,27 +1227,59 @@ __global__ void weight_flip_transpose_kernel(const float* __restrict__ w, float*
 }
 
 // ------------------------------------------------------------------------------------------ host
+// The epilogue a launch runs: template argument EPI (0 plain, 1 BN statistics, 2 eval BN + ReLU, 3 plain with the strided
+// scatter of a parity phase) and RED (a plain epilogue that also forms the BN-backward reduce partials).  The ONE place
+// that maps launch parameters to them: the kernel dispatch of every family and the profiler's kernel names both read it.
+struct EpiSel {
+  int epi;
+  bool red;
+};
+static EpiSel conv_epilogue(int mode, int nred, bool scatter, bool rowmode) {
+  const int epi = mode == CONV_EPI_STATS ? 1 : (mode == CONV_EPI_EVAL ? 2 : ((scatter && !rowmode) ? 3 : 0));
+  return {epi, epi == 0 && nred > 0 && !rowmode};
+}
+// f(integral_constant<int, EPI>, bool_constant<RED>) for the selected epilogue.  SCATTER / REDUCE: whether the kernel
+// family has epilogue 3 / the RED form at all -- a combination outside the family's set is refused, never instantiated
+template <bool SCATTER, bool REDUCE, class F>
+static int with_epilogue(EpiSel e, F&& f) {
+  if (e.epi == 1) return f(std::integral_constant<int, 1>{}, std::false_type{});
+  if (e.epi == 2) return f(std::integral_constant<int, 2>{}, std::false_type{});
+  if constexpr (SCATTER)
+    if (e.epi == 3) return f(std::integral_constant<int, 3>{}, std::false_type{});
+  if constexpr (REDUCE)
+    if (e.epi == 0 && e.red) return f(std::integral_constant<int, 0>{}, std::true_type{});
+  if (e.epi == 0 && !e.red) return f(std::integral_constant<int, 0>{}, std::false_type{});
+  tbn_set_error("conv: epilogue %d%s is not built for this kernel family", e.epi, e.red ? " + reduce" : "");
+  return TBN_ERR_UNSUPPORTED;
+}
+// f(integral_constant<int, MT>, integral_constant<int, NT>) for the tile (mt, nt) of a family that admits 1..MAXM x 1..MAXN;
+// any other tile is refused (I walks the admitted tiles in row order)
+template <int MAXM, int MAXN, int I = 0, class F>
+static int with_tile(int mt, int nt, F&& f) {
+  if constexpr (I == MAXM * MAXN) {
+    tbn_set_error("conv: unsupported tile %dx%d", mt, nt);
+    return TBN_ERR_UNSUPPORTED;
+  } else {
+    constexpr int MT = I / MAXN + 1, NT = I % MAXN + 1;
+    if (mt == MT && nt == NT) return f(std::integral_constant<int, MT>{}, std::integral_constant<int, NT>{});
+    return with_tile<MAXM, MAXN, I + 1>(mt, nt, f);
+  }
+}
+// the instantiation's name as the profiler reports it: kernel<mt, nt, [rowmode, ]epi[, stages][, true]>
+static void conv_kernel_name(char (&nm)[64], const char* kernel, int mt, int nt, const char* rowmode, EpiSel e, int stages) {
+  char stg[8] = "";
+  if (stages > 0) snprintf(stg, sizeof(stg), ", %d", stages);
+  snprintf(nm, sizeof(nm), "%s<%d, %d, %s%d%s%s>", kernel, mt, nt, rowmode, e.epi, stg, e.red ? ", true" : "");
+}
+
 // `rd` = the rider riding in this launch (rd.span == 0: none), `grid` = GEMM workgroups + rd.span (tbn_rider_place)
-template <int MT, int NT, bool RM, int EPI, bool RED = false>
-static void launch_conv_e(const ConvP& p, const RiderP& rd, int grid, hipStream_t st) {
+template <int MT, int NT, bool RM, int EPI, bool RED>
+static int launch_conv_e(const ConvP& p, const RiderP& rd, int grid, hipStream_t st) {
   if (p.stages == 2)
     TBN_LAUNCH((conv_igemm_kernel<MT, NT, RM, EPI, 2, RED>), dim3(grid), dim3(256), 0, st, p, rd);
   else
     TBN_LAUNCH((conv_igemm_kernel<MT, NT, RM, EPI, 1, RED>), dim3(grid), dim3(256), 0, st, p, rd);
-}
-template <int MT, int NT, bool RM>
-static void launch_conv(const ConvP& p, const RiderP& rd, int grid, hipStream_t st) {
-  const bool scatter = (p.out_sy != 1) || (p.out_sx != 1);
-  if (p.mode == CONV_EPI_STATS)
-    launch_conv_e<MT, NT, RM, 1>(p, rd, grid, st);
-  else if (p.mode == CONV_EPI_EVAL)
-    launch_conv_e<MT, NT, RM, 2>(p, rd, grid, st);
-  else if (!RM && scatter)
-    launch_conv_e<MT, NT, false, 3>(p, rd, grid, st);
-  else if (!RM && p.nred > 0)
-    launch_conv_e<MT, NT, false, 0, true>(p, rd, grid, st);
-  else
-    launch_conv_e<MT, NT, RM, 0>(p, rd, grid, st);
+  return TBN_OK;
 }
 
 // LDS bytes of the halo kernel; 0 if the shape is not a 3x3 / stride 1 / pad 1 layer it handles
@@ -1269,39 +1301,6 @@ static int launch_halo_e(const ConvP& p, const RiderP& rd, int grid, size_t lds_
   }
   TBN_LAUNCH((conv_halo_kernel<MT, NT, EPI, RED>), dim3(grid), dim3(256), lds_bytes, st, p, rd);
   return TBN_OK;
-}
-template <int MT, int NT>
-static int launch_halo(const ConvP& p, const RiderP& rd, int grid, size_t lds_bytes, hipStream_t st) {
-  if (p.mode == CONV_EPI_STATS) return launch_halo_e<MT, NT, 1, false>(p, rd, grid, lds_bytes, st);
-  if (p.mode == CONV_EPI_EVAL) return launch_halo_e<MT, NT, 2, false>(p, rd, grid, lds_bytes, st);
-  if (p.nred > 0) return launch_halo_e<MT, NT, 0, true>(p, rd, grid, lds_bytes, st);
-  return launch_halo_e<MT, NT, 0, false>(p, rd, grid, lds_bytes, st);
-}
-
-template <int MT, int NT>
-static void launch_sk4(const ConvP& p, const RiderP& rd, int nblocks, hipStream_t st) {
-  const dim3 grid(nblocks);
-  if (p.mode == CONV_EPI_STATS)
-    TBN_LAUNCH((conv_sk4_kernel<MT, NT, 1, false>), grid, dim3(256), 0, st, p, rd);
-  else if (p.mode == CONV_EPI_EVAL)
-    TBN_LAUNCH((conv_sk4_kernel<MT, NT, 2, false>), grid, dim3(256), 0, st, p, rd);
-  else if (p.nred > 0)
-    TBN_LAUNCH((conv_sk4_kernel<MT, NT, 0, true>), grid, dim3(256), 0, st, p, rd);
-  else
-    TBN_LAUNCH((conv_sk4_kernel<MT, NT, 0, false>), grid, dim3(256), 0, st, p, rd);
-}
-
-template <int MT, int NT>
-static void launch_dma(const ConvP& p, const RiderP& rd, int nblocks, hipStream_t st) {
-  const dim3 grid(nblocks);
-  if (p.mode == CONV_EPI_STATS)
-    TBN_LAUNCH((conv_dma_kernel<MT, NT, 1, false>), grid, dim3(256), 0, st, p, rd);
-  else if (p.mode == CONV_EPI_EVAL)
-    TBN_LAUNCH((conv_dma_kernel<MT, NT, 2, false>), grid, dim3(256), 0, st, p, rd);
-  else if (p.nred > 0)
-    TBN_LAUNCH((conv_dma_kernel<MT, NT, 0, true>), grid, dim3(256), 0, st, p, rd);
-  else
-    TBN_LAUNCH((conv_dma_kernel<MT, NT, 0, false>), grid, dim3(256), 0, st, p, rd);
 }
 
 void tbn_conv_pick_tile(int M, int Cout, int K, int* mt_out, int* nt_out) {
@@ -1358,7 +1357,8 @@ static int launch_conv_tiles(ConvP& p, int rowmode, int mt, int nt, hipStream_t 
     rd = *rider;
   else
     memset(&rd, 0, sizeof(rd));
-  if ((mt <= 0 || nt <= 0) && !rowmode && p.out_sy == 1 && p.out_sx == 1) {
+  const bool scatter = (p.out_sy != 1) || (p.out_sx != 1);
+  if ((mt <= 0 || nt <= 0) && !rowmode && !scatter) {
     // heuristic launches (the head Linear layers: M = 96 ... 768 rows): a grid of 128-row tiles that leaves most CUs
     // idle takes the split-K tile kernel instead (never with partial-sum epilogues: their row count is the caller's)
     if (p.halo == 0 && p.mode != CONV_EPI_STATS && p.nred == 0 && p.K >= 256 &&
@@ -1368,83 +1368,60 @@ static int launch_conv_tiles(ConvP& p, int rowmode, int mt, int nt, hipStream_t 
   }
   if (mt <= 0 || nt <= 0) tbn_conv_pick_tile(p.M, p.Cout, p.K, &mt, &nt);
   if (p.stages != 1 && p.stages != 2) p.stages = (mt == 1) ? 2 : 1;  // big tiles: keep 2 workgroups per CU
-  p.tiles_m = cdiv(p.M, 128 * mt);
-  p.tiles_n = cdiv(p.Cout, 32 * nt);
-  if (p.halo == 3 && !rowmode) {   // small-M layers: 32-row tiles, the four waves split K
-    const bool scatter = (p.out_sy != 1) || (p.out_sx != 1);
-    TBN_REQUIRE(!scatter && mt <= 2 && nt <= 2, "conv: the split-K tile kernel does not handle this launch");
-    p.tiles_m = cdiv(p.M, 32 * mt);
-    const int grid = tbn_rider_place(&rd, p.tiles_m * p.tiles_n);
-    char nm[64];
-    const int epi = p.mode == CONV_EPI_STATS ? 1 : (p.mode == CONV_EPI_EVAL ? 2 : 0);
-    snprintf(nm, sizeof(nm), "conv_sk4_kernel<%d, %d, %d%s>", mt, nt, epi, (p.nred > 0 && epi == 0) ? ", true" : "");
-    tbn_prof_begin(nm, p.alg_flops, st, conv_alg_bytes(p, rowmode));
-#define TBN_SCASE(MTv, NTv) \
-  if (mt == MTv && nt == NTv) launch_sk4<MTv, NTv>(p, rd, grid, st);
-    TBN_SCASE(1, 1) TBN_SCASE(1, 2) TBN_SCASE(2, 1) TBN_SCASE(2, 2)
-#undef TBN_SCASE
-    tbn_prof_end(st);
-    TBN_CHECK_LAUNCH("conv_sk4");
-    return TBN_OK;
-  }
-  if (p.halo == 2 && !rowmode) {   // LDS-DMA staging
-    const bool scatter = (p.out_sy != 1) || (p.out_sx != 1);
-    TBN_REQUIRE(!scatter && mt <= 2 && nt <= 4, "conv: the LDS-DMA kernel does not handle this launch");
-    const int grid = tbn_rider_place(&rd, p.tiles_m * p.tiles_n);
-    char nm[64];
-    const int epi = p.mode == CONV_EPI_STATS ? 1 : (p.mode == CONV_EPI_EVAL ? 2 : 0);
-    snprintf(nm, sizeof(nm), "conv_dma_kernel<%d, %d, %d%s>", mt, nt, epi, (p.nred > 0 && epi == 0) ? ", true" : "");
-    tbn_prof_begin(nm, p.alg_flops, st, conv_alg_bytes(p, rowmode));
-#define TBN_DCASE(MTv, NTv) \
-  if (mt == MTv && nt == NTv) launch_dma<MTv, NTv>(p, rd, grid, st);
-    TBN_DCASE(1, 1) TBN_DCASE(1, 2) TBN_DCASE(1, 3) TBN_DCASE(1, 4) TBN_DCASE(2, 1) TBN_DCASE(2, 2) TBN_DCASE(2, 3) TBN_DCASE(2, 4)
-#undef TBN_DCASE
-    tbn_prof_end(st);
-    TBN_CHECK_LAUNCH("conv_dma");
-    return TBN_OK;
-  }
-  if (p.halo == 1 && !rowmode) {
-    const size_t lds_bytes = tbn_conv_halo_lds_bytes(p, mt, nt);
+  // kernel family: 0 register-staged generic (the only one with packed rows and the scatter epilogue), 1 LDS-halo,
+  // 2 LDS-DMA staging, 3 split-K tile (small-M layers: 32-row tiles, the four waves split K)
+  const int family = (rowmode || p.halo < 1 || p.halo > 3) ? 0 : p.halo;
+  static const char* const kName[4] = {"conv_igemm", "conv_halo", "conv_dma", "conv_sk4"};
+  size_t lds_bytes = 0;
+  if (family == 3) TBN_REQUIRE(!scatter && mt <= 2 && nt <= 2, "conv: the split-K tile kernel does not handle this launch");
+  if (family == 2) TBN_REQUIRE(!scatter && mt <= 2 && nt <= 4, "conv: the LDS-DMA kernel does not handle this launch");
+  if (family == 1) {
+    lds_bytes = tbn_conv_halo_lds_bytes(p, mt, nt);
     TBN_REQUIRE(lds_bytes > 0 && lds_bytes <= 160 * 1024, "conv: the LDS-halo kernel does not handle this shape / tile");
-    TBN_REQUIRE(mt <= 2 && nt <= 4, "conv: unsupported halo tile %dx%d", mt, nt);
-    const int grid = tbn_rider_place(&rd, p.tiles_m * p.tiles_n);
-    char nm[64];
-    const int epi = p.mode == CONV_EPI_STATS ? 1 : (p.mode == CONV_EPI_EVAL ? 2 : 0);
-    snprintf(nm, sizeof(nm), "conv_halo_kernel<%d, %d, %d%s>", mt, nt, epi, (p.nred > 0 && epi == 0) ? ", true" : "");
-    tbn_prof_begin(nm, p.alg_flops, st, conv_alg_bytes(p, rowmode));
-    int rc = TBN_OK;
-#define TBN_HCASE(MTv, NTv) \
-  if (mt == MTv && nt == NTv) rc = launch_halo<MTv, NTv>(p, rd, grid, lds_bytes, st);
-    TBN_HCASE(1, 1) TBN_HCASE(1, 2) TBN_HCASE(1, 3) TBN_HCASE(1, 4) TBN_HCASE(2, 1) TBN_HCASE(2, 2) TBN_HCASE(2, 3) TBN_HCASE(2, 4)
-#undef TBN_HCASE
-    tbn_prof_end(st);
-    if (rc != TBN_OK) return rc;
-    TBN_CHECK_LAUNCH("conv_halo");
-    return TBN_OK;
+    TBN_REQUIRE(!scatter && mt <= 2 && nt <= 4, "conv: unsupported halo launch (tile %dx%d)", mt, nt);
   }
+  p.tiles_m = cdiv(p.M, (family == 3 ? 32 : 128) * mt);
+  p.tiles_n = cdiv(p.Cout, 32 * nt);
   const int grid = tbn_rider_place(&rd, p.tiles_m * p.tiles_n);
-  {
-    char nm[64];
-    const int epi = p.mode == CONV_EPI_STATS ? 1 : (p.mode == CONV_EPI_EVAL ? 2 : ((p.out_sy != 1 || p.out_sx != 1) ? 3 : 0));
-    snprintf(nm, sizeof(nm), "conv_igemm_kernel<%d, %d, %s, %d, %d%s>", mt, nt, rowmode ? "true" : "false", epi, p.stages,
-             (p.nred > 0 && epi == 0 && !rowmode) ? ", true" : "");
-    tbn_prof_begin(nm, p.alg_flops, st, conv_alg_bytes(p, rowmode));
+  const EpiSel es = conv_epilogue(p.mode, p.nred, scatter, rowmode != 0);
+  char nm[64], kernel[32];
+  snprintf(kernel, sizeof(kernel), "%s_kernel", kName[family]);
+  conv_kernel_name(nm, kernel, mt, nt, family != 0 ? "" : (rowmode ? "true, " : "false, "), es, family != 0 ? 0 : p.stages);
+  tbn_prof_begin(nm, p.alg_flops, st, conv_alg_bytes(p, rowmode));
+  int rc;
+  if (family == 3) {
+    rc = with_tile<2, 2>(mt, nt, [&](auto MT, auto NT) {
+      return with_epilogue<false, true>(es, [&](auto EPI, auto RED) {
+        TBN_LAUNCH((conv_sk4_kernel<MT, NT, EPI, RED>), dim3(grid), dim3(256), 0, st, p, rd);
+        return TBN_OK;
+      });
+    });
+  } else if (family == 2) {
+    rc = with_tile<2, 4>(mt, nt, [&](auto MT, auto NT) {
+      return with_epilogue<false, true>(es, [&](auto EPI, auto RED) {
+        TBN_LAUNCH((conv_dma_kernel<MT, NT, EPI, RED>), dim3(grid), dim3(256), 0, st, p, rd);
+        return TBN_OK;
+      });
+    });
+  } else if (family == 1) {
+    rc = with_tile<2, 4>(mt, nt, [&](auto MT, auto NT) {
+      return with_epilogue<false, true>(
+          es, [&](auto EPI, auto RED) { return launch_halo_e<MT, NT, EPI, RED>(p, rd, grid, lds_bytes, st); });
+    });
+  } else if (rowmode) {   // packed rows: no scatter, no fused reduce
+    rc = with_tile<2, 4>(mt, nt, [&](auto MT, auto NT) {
+      return with_epilogue<false, false>(
+          es, [&](auto EPI, auto RED) { return launch_conv_e<MT, NT, true, EPI, RED>(p, rd, grid, st); });
+    });
+  } else {
+    rc = with_tile<2, 4>(mt, nt, [&](auto MT, auto NT) {
+      return with_epilogue<true, true>(
+          es, [&](auto EPI, auto RED) { return launch_conv_e<MT, NT, false, EPI, RED>(p, rd, grid, st); });
+    });
   }
-#define TBN_CASE(MTv, NTv)                                     \
-  if (mt == MTv && nt == NTv) {                                \
-    if (rowmode)                                               \
-      launch_conv<MTv, NTv, true>(p, rd, grid, st);            \
-    else                                                       \
-      launch_conv<MTv, NTv, false>(p, rd, grid, st);           \
-  } else
-  TBN_CASE(1, 1) TBN_CASE(1, 2) TBN_CASE(1, 3) TBN_CASE(1, 4) TBN_CASE(2, 1) TBN_CASE(2, 2) TBN_CASE(2, 3)
-  TBN_CASE(2, 4) {
-    tbn_set_error("conv: unsupported tile %dx%d", mt, nt);
-    return TBN_ERR_UNSUPPORTED;
-  }
-#undef TBN_CASE
   tbn_prof_end(st);
-  TBN_CHECK_LAUNCH("conv_igemm");
+  if (rc != TBN_OK) return rc;
+  TBN_CHECK_LAUNCH(kName[family]);
   return TBN_OK;
 }
 
@@ -1743,15 +1720,6 @@ static int launch_pair_v(const ConvPair& q, const RiderP& rd, int blocks, int va
   }
   return TBN_OK;
 }
-template <int MT, int NT>
-static int launch_pair(const ConvPair& q, const RiderP& rd, int blocks, int variant, size_t lds_bytes, hipStream_t st) {
-  const ConvP& p = q.m[0];
-  if (p.mode == CONV_EPI_STATS) return launch_pair_v<MT, NT, 1, false>(q, rd, blocks, variant, lds_bytes, st);
-  if (p.mode == CONV_EPI_EVAL) return launch_pair_v<MT, NT, 2, false>(q, rd, blocks, variant, lds_bytes, st);
-  if (p.nred > 0) return launch_pair_v<MT, NT, 0, true>(q, rd, blocks, variant, lds_bytes, st);
-  return launch_pair_v<MT, NT, 0, false>(q, rd, blocks, variant, lds_bytes, st);
-}
-
 // variant: 0 LDS-halo (both members 3x3 / stride 1), 1 / 2 register-staged generic kernel with 1 / 2 LDS stages.
 // Tiles: (1,1) (1,2) (2,1) (2,2).  Both members: unit-stride launches (no parity phases), same epilogue mode, reduce
 // segments on both or on neither.
@@ -1798,18 +1766,14 @@ int tbn_launch_conv_pair(ConvP a, ConvP b, int variant, int mt, int nt, hipStrea
   }
   q.blk1 = ms[0]->tiles_m * ms[0]->tiles_n;
   const int blocks = tbn_rider_place(&rd, q.blk1 + ms[1]->tiles_m * ms[1]->tiles_n);
-  {
-    char nm[64];
-    const int epi = a.mode == CONV_EPI_STATS ? 1 : (a.mode == CONV_EPI_EVAL ? 2 : 0);
-    snprintf(nm, sizeof(nm), "conv_pair_%s_kernel<%d, %d, %d%s%s>", variant == 0 ? "halo" : "igemm", mt, nt, epi,
-             variant == 2 ? ", 2" : (variant == 1 ? ", 1" : ""), (a.nred > 0 && epi == 0) ? ", true" : "");
-    tbn_prof_begin(nm, a.alg_flops + b.alg_flops, st, conv_alg_bytes(a, 0) + conv_alg_bytes(b, 0));
-  }
-  rc = TBN_OK;
-  if (mt == 1 && nt == 1) rc = launch_pair<1, 1>(q, rd, blocks, variant, lds_bytes, st);
-  if (mt == 1 && nt == 2) rc = launch_pair<1, 2>(q, rd, blocks, variant, lds_bytes, st);
-  if (mt == 2 && nt == 1) rc = launch_pair<2, 1>(q, rd, blocks, variant, lds_bytes, st);
-  if (mt == 2 && nt == 2) rc = launch_pair<2, 2>(q, rd, blocks, variant, lds_bytes, st);
+  const EpiSel es = conv_epilogue(a.mode, a.nred, false, false);
+  char nm[64];
+  conv_kernel_name(nm, variant == 0 ? "conv_pair_halo_kernel" : "conv_pair_igemm_kernel", mt, nt, "", es, variant);
+  tbn_prof_begin(nm, a.alg_flops + b.alg_flops, st, conv_alg_bytes(a, 0) + conv_alg_bytes(b, 0));
+  rc = with_tile<2, 2>(mt, nt, [&](auto MT, auto NT) {
+    return with_epilogue<false, true>(
+        es, [&](auto EPI, auto RED) { return launch_pair_v<MT, NT, EPI, RED>(q, rd, blocks, variant, lds_bytes, st); });
+  });
   tbn_prof_end(st);
   if (rc != TBN_OK) return rc;
   TBN_CHECK_LAUNCH("conv_pair");

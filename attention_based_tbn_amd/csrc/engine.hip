@@ -1085,6 +1085,67 @@ void fill_fwd(const tbn_backbone_plan* P, const Conv& c, int training, float* ws
   }
 }
 
+// Forward epilogue of one GEMM (fill_fwd first).  Training: the raw (bias-free) conv output of every part goes to the
+// layer's y buffer, the per-channel statistics partials to scratch slot `slot`.  Eval: running-stat BN + ReLU folded
+// into the epilogue, every part straight into its concat slice; a pooled part (pool_proj) leaves the bare conv output
+// for its average pool.
+void fill_fwd_epilogue(const tbn_backbone_plan* P, const Conv& c, int training, float* ws, int slot, ConvP* pp) {
+  ConvP& p = *pp;
+  if (training) {
+    p.mode = CONV_EPI_STATS;
+    p.nseg = 1;
+    p.seg[0].ptr = ws + c.y_off;
+    p.seg[0].ld = c.cout;
+    p.seg[0].col_begin = 0;
+    p.stat_partial = ws + P->partial_off + (size_t)slot * P->partial_floats;
+    return;
+  }
+  float* scale = ws + P->stats_off + 2 * P->chan_floats;   // mean | rstd | scale | shift
+  p.mode = CONV_EPI_EVAL;
+  p.scale = scale + c.c_off;
+  p.shift = scale + P->chan_floats + c.c_off;
+  p.nseg = c.nparts;
+  for (int i = 0; i < c.nparts; ++i) {
+    const Part& q = c.parts[i];
+    const Buf& db = P->bufs[q.dst_buf];
+    p.seg[i].ptr = q.pooled ? ws + q.yraw_off : ws + db.off + q.dst_choff;
+    p.seg[i].ld = q.pooled ? q.cout : db.C;
+    p.seg[i].col_begin = q.col0;
+    if (q.pooled) p.raw_seg1 = i + 1;
+  }
+}
+
+// The tuned launch choices of one GEMM kind of a conv, as the walks read them: the forward in eval / training mode
+// (= the index into Conv::ft) or the data gradient.
+enum { GEMM_FWD_EVAL = 0, GEMM_FWD_TRAIN = 1, GEMM_DGRAD = 2 };
+struct Tuned {
+  int halo, mt;   // single launch: kernel variant and M tile
+  bool pair;      // sibling-pair decision (held by the first member)
+  int p_mt;       // M tile of the pair launch
+};
+Tuned tuned(const Conv& c, int gemm) {
+  if (gemm == GEMM_DGRAD) return {c.d_halo, c.d_mt, c.pair_dgrad, c.pd_mt};
+  const Conv::FwdTune& T = c.ft[gemm];
+  return {T.halo, T.mt, T.pair, T.p_mt};
+}
+// How conv `c` is issued in a walk: 0 as its own launch, 1 as the FIRST member of a sibling-pair launch (it issues the
+// launch for both), 2 as the SECOND member (it ran with its sibling).  Branch mode (`br`) never pairs, whatever the plan
+// holds: the siblings belong to different chains there -- 3x3 on the side stream, double_3x3_1 on the launch stream --
+// and one grid cannot run on two streams.
+int pair_role(const tbn_backbone_plan* P, const Conv& c, int gemm, bool br) {
+  if (br) return 0;
+  if (c.pair_next >= 0 && tuned(c, gemm).pair) return 1;
+  if (c.pair_prev >= 0 && tuned(P->convs[c.pair_prev], gemm).pair) return 2;
+  return 0;
+}
+// M rows per workgroup tile of the launch that wrote the partial rows of conv `c` (forward: BN statistics, data gradient:
+// fused BN-backward reduce) = rows summed into one partial row.  A pair launch has its own tile, 128-row kernels only.
+int writer_rows(const tbn_backbone_plan* P, const Conv& c, int gemm, bool br) {
+  const int role = pair_role(P, c, gemm, br);
+  if (role == 0) return tile_rows(tuned(c, gemm).halo, tuned(c, gemm).mt);
+  return 128 * tuned(role == 1 ? c : P->convs[c.pair_prev], gemm).p_mt;
+}
+
 // data-gradient launch parameters of one GEMM: conv of dy with flipped / transposed weights (parity phases for
 // stride 2), plus the fused BN-backward reduce of the layers whose dz it finishes
 void fill_dgrad(const tbn_backbone_plan* P, const Conv& c, float* ws, int R, ConvP* pp) {
@@ -1191,31 +1252,36 @@ int ensure_events(tbn_backbone_plan* PM) {
   return TBN_OK;
 }
 
+// whatever is enqueued on `to` from here on runs after everything `from` holds now
+void order_after(hipEvent_t e, hipStream_t from, hipStream_t to) {
+  (void)hipEventRecord(e, from);
+  (void)hipStreamWaitEvent(to, e, 0);
+}
+
 // joins the aux (weight-gradient) stream into the launch stream on every exit path of tbn_backbone_backward
 struct AuxJoin {
   hipStream_t st, aux;
   hipEvent_t ev;
   bool forked = false;
   ~AuxJoin() {
-    if (aux != nullptr && forked) {
-      (void)hipEventRecord(ev, aux);
-      (void)hipStreamWaitEvent(st, ev, 0);
-    }
+    if (aux != nullptr && forked) order_after(ev, aux, st);
   }
 };
 
-// joins the side (branch) stream into the launch stream on every exit path: a TBN_TRY / TBN_REQUIRE that returns between
-// an OP_FORK and its OP_JOIN would otherwise leave side-stream kernels reading and writing the workspace while the caller
-// (seeing the error) frees or reuses it, or enqueues on the launch stream (round-4 advisor)
+// The side (branch) stream of a walk.  turn(): at a FORK the side stream continues from where the launch stream is, at a
+// join the launch stream waits for the side chain of the block.  The destructor joins on every exit path: a TBN_TRY /
+// TBN_REQUIRE that returns between a fork and its join would otherwise leave side-stream kernels reading and writing the
+// workspace while the caller (seeing the error) frees or reuses it, or enqueues on the launch stream (round-4 advisor)
 struct SideJoin {
   hipStream_t st, side;
   hipEvent_t ev;
   bool open = false;   // the side chain of the current block has been forked and not yet joined
+  void turn(hipEvent_t e, bool fork) {
+    order_after(e, fork ? st : side, fork ? side : st);
+    open = fork;
+  }
   ~SideJoin() {
-    if (side != nullptr && open) {
-      (void)hipEventRecord(ev, side);
-      (void)hipStreamWaitEvent(st, ev, 0);
-    }
+    if (side != nullptr && open) order_after(ev, side, st);
   }
 };
 
@@ -1326,30 +1392,6 @@ int tbn_backbone_forward(const tbn_backbone_plan* P, int training, const float* 
     TBN_TRY(tbn_launch_bn_fold(prm->gamma, prm->beta, prm->running_mean, prm->running_var, prm->bias, prm->eps, scale,
                                shift, (int)P->chan_floats, st));
 
-  auto fwd_params = [&](const Conv& c, ConvP& p) {
-    fill_fwd(P, c, training, ws, prm->weight, R, &p);
-    if (training) {
-      p.mode = CONV_EPI_STATS;
-      p.nseg = 1;
-      p.seg[0].ptr = ws + c.y_off;
-      p.seg[0].ld = c.cout;
-      p.seg[0].col_begin = 0;
-      p.stat_partial = ws + P->partial_off + (size_t)c.slot * P->partial_floats;
-    } else {
-      p.mode = CONV_EPI_EVAL;
-      p.scale = scale + c.c_off;
-      p.shift = shift + c.c_off;
-      p.nseg = c.nparts;
-      for (int i = 0; i < c.nparts; ++i) {
-        const Part& q = c.parts[i];
-        const Buf& db = P->bufs[q.dst_buf];
-        p.seg[i].ptr = q.pooled ? ws + q.yraw_off : ws + db.off + q.dst_choff;
-        p.seg[i].ld = q.pooled ? q.cout : db.C;
-        p.seg[i].col_begin = q.col0;
-        if (q.pooled) p.raw_seg1 = i + 1;
-      }
-    }
-  };
   // TBN_BACKBONE_CONV_BF16X6 / _BF16X3 (eval forward only): every 3x3 / stride 1 / pad 1 layer on a map at most 64 wide goes
   // through the split-bf16 kernel as a single launch with the eval epilogue; its tile is the layer's tuned LDS-halo tile
   // where the plan holds one (same geometry), else that kernel's size heuristic.  The plan is not touched.
@@ -1377,64 +1419,39 @@ int tbn_backbone_forward(const tbn_backbone_plan* P, int training, const float* 
   for (const Op& o : (br ? P->ops_b : P->ops)) {
     st = (br && o.side) ? side : st_main;   // the stream this op launches on
     if (o.kind == OP_FORK || o.kind == OP_JOIN) {
-      // FORK: the side stream continues from here; JOIN: the launch stream waits for the side chain of the block
-      hipEvent_t e = PM->ev[ev_next++];
-      (void)hipEventRecord(e, o.kind == OP_FORK ? st_main : side);
-      (void)hipStreamWaitEvent(o.kind == OP_FORK ? side : st_main, e, 0);
-      sjoin.open = o.kind == OP_FORK;
+      sjoin.turn(PM->ev[ev_next++], o.kind == OP_FORK);
       continue;
     }
     if (o.kind == OP_CONV) {
       const Conv& c = P->convs[o.idx];
       const Conv::FwdTune& T = c.ft[tr];
-      if (!br && c.pair_prev >= 0 && P->convs[c.pair_prev].ft[tr].pair &&
-          !(bf16x_layer(c) || bf16x_layer(P->convs[c.pair_prev])))
-        continue;   // ran with its sibling
+      // a sibling pair with a split-bf16 member is issued as its two single launches (as branch mode does).  Eval only: the
+      // training BN step reads pair_role as it is
+      int role = pair_role(P, c, tr, br);
+      if (role != 0 && (bf16x_layer(c) || bf16x_layer(P->convs[role == 1 ? c.pair_next : c.pair_prev]))) role = 0;
+      if (role == 2) continue;   // ran with its sibling
       const RiderP* rd = (pend_host == o.idx) ? &pend_rider : nullptr;
       if (rd != nullptr) {
         pend_host = -1;
         ++PM->rider_launches[0];
       }
-      const bool bx = bf16x_layer(c);
-      // a sibling pair with a split-bf16 member is issued as its two single launches (as branch mode does)
-      const bool pair_bx = bx || (c.pair_next >= 0 && bf16x_layer(P->convs[c.pair_next])) ||
-                           (c.pair_prev >= 0 && bf16x_layer(P->convs[c.pair_prev]));
-      if (!br && !pair_bx && c.pair_next >= 0 && T.pair) {
+      ConvP p;
+      if (role == 1) {
         const Conv& c2 = P->convs[c.pair_next];
-        ConvP pa, pb;
-        fwd_params(c, pa);
-        fwd_params(c2, pb);
+        ConvP pb;
+        for (int k = 0; k < 2; ++k) {   // both members keep their one-chain scratch slot (role 1 implies !br)
+          const Conv& m = k ? c2 : c;
+          fill_fwd(P, m, training, ws, prm->weight, R, k ? &pb : &p);
+          fill_fwd_epilogue(P, m, training, ws, m.slot, k ? &pb : &p);
+        }
         tbn_prof_label(("fwd " + c.parts[0].name + " | " + c2.parts[0].name).c_str());
-        TBN_TRY(tbn_launch_conv_pair(pa, pb, T.p_variant, T.p_mt, T.p_nt, st, rd));
+        TBN_TRY(tbn_launch_conv_pair(p, pb, T.p_variant, T.p_mt, T.p_nt, st, rd));
         continue;
       }
-      ConvP p;
       fill_fwd(P, c, training, ws, prm->weight, R, &p);
+      fill_fwd_epilogue(P, c, training, ws, br ? c.slot_b : c.slot, &p);
       tbn_prof_label(("fwd " + c.parts[c.nparts - 1].name).c_str());
-      if (training) {
-        // raw (bias-free) conv output of every part into the layer's y buffer + per-channel statistics partials
-        p.mode = CONV_EPI_STATS;
-        p.nseg = 1;
-        p.seg[0].ptr = ws + c.y_off;
-        p.seg[0].ld = c.cout;
-        p.seg[0].col_begin = 0;
-        p.stat_partial = ws + P->partial_off + (size_t)(br ? c.slot_b : c.slot) * P->partial_floats;
-      } else {
-        // eval: running-stat BN + ReLU folded into the epilogue, straight into the concat slices; a pooled part
-        // (pool_proj) leaves the bare conv output for its average pool
-        p.mode = CONV_EPI_EVAL;
-        p.scale = scale + c.c_off;
-        p.shift = shift + c.c_off;
-        p.nseg = c.nparts;
-        for (int i = 0; i < c.nparts; ++i) {
-          const Part& q = c.parts[i];
-          const Buf& db = P->bufs[q.dst_buf];
-          p.seg[i].ptr = q.pooled ? ws + q.yraw_off : ws + db.off + q.dst_choff;
-          p.seg[i].ld = q.pooled ? q.cout : db.C;
-          p.seg[i].col_begin = q.col0;
-          if (q.pooled) p.raw_seg1 = i + 1;
-        }
-      }
+      const bool bx = bf16x_layer(c);
       if (bx || bf16x_pw_layer(c)) {
         p.flags |= bf16x_flag;
         p.halo = 0;
@@ -1442,8 +1459,8 @@ int tbn_backbone_forward(const tbn_backbone_plan* P, int training, const float* 
           p.flags |= CONV_FLAG_BF16X_PLANES;
           p.wt = reinterpret_cast<const float*>(static_cast<const char*>(prm->weight_planes) + planes_off[o.idx]);
         }
-        const bool tuned = bx && T.halo == 1;
-        TBN_TRY(tbn_launch_conv(p, 0, tuned ? T.mt : 0, tuned ? T.nt : 0, st, nullptr));
+        const bool own_tile = bx && T.halo == 1;
+        TBN_TRY(tbn_launch_conv(p, 0, own_tile ? T.mt : 0, own_tile ? T.nt : 0, st, nullptr));
         continue;
       }
       TBN_TRY(tbn_launch_conv(p, c.stem, T.mt, T.nt, st, rd));
@@ -1486,7 +1503,7 @@ int tbn_backbone_forward(const tbn_backbone_plan* P, int training, const float* 
         const Pool& pl = P->pools[c0.fuse_pool];
         const Buf& ob = P->bufs[pl.outbuf];
         if (!diag_skip(2)) {
-          TBN_TRY(tbn_launch_bn_finalize(ws + P->partial_off + (size_t)c0.slot * P->partial_floats, cdiv(M, tile_rows(c0.ft[1].halo, c0.ft[1].mt)), M,
+          TBN_TRY(tbn_launch_bn_finalize(ws + P->partial_off + (size_t)c0.slot * P->partial_floats, cdiv(M, writer_rows(P, c0, GEMM_FWD_TRAIN, br)), M,
                                          q.cout, prm->gamma + q.c_off, prm->beta + q.c_off, prm->bias + q.c_off,
                                          prm->running_mean + q.c_off, prm->running_var + q.c_off, prm->momentum, prm->eps,
                                          mean + q.c_off, rstd + q.c_off, scale + q.c_off, shift + q.c_off, st));
@@ -1520,13 +1537,7 @@ int tbn_backbone_forward(const tbn_backbone_plan* P, int training, const float* 
           L.y_ld = c.cout;
           L.partial = ws + P->partial_off + (size_t)(br ? c.slot_b : c.slot) * P->partial_floats + q.col0;
           L.pld = c.cout;
-          // M tile of the launch that wrote the statistics partials (a paired launch has its own); training mode here
-          const bool paired_first = !br && c.pair_next >= 0 && c.ft[1].pair;
-          const bool paired_second = !br && c.pair_prev >= 0 && P->convs[c.pair_prev].ft[1].pair;
-          int frows = tile_rows(c.ft[1].halo, c.ft[1].mt);
-          if (paired_first) frows = 128 * c.ft[1].p_mt;
-          if (paired_second) frows = 128 * P->convs[c.pair_prev].ft[1].p_mt;
-          L.nparts = cdiv(M, frows);
+          L.nparts = cdiv(M, writer_rows(P, c, GEMM_FWD_TRAIN, br));
         }
         L.gamma = prm->gamma + q.c_off;
         L.beta = prm->beta + q.c_off;
@@ -1574,6 +1585,114 @@ int tbn_backbone_forward(const tbn_backbone_plan* P, int training, const float* 
   return TBN_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// ---- autotune
+constexpr int kMaxCand = 40;
+struct Cand {
+  int mt, nt, stages, halo;
+  int variant;   // pair launches: tbn_launch_conv_pair's variant (0 LDS-halo members, 1 / 2 generic with 1 / 2 LDS stages)
+};
+
+// Experiment knobs (a -DTBN_EXPERIMENT=1 build only; the shipped library folds both to their defaults):
+//   TBN_TUNE_MIN_TILE=n  candidates whose wave tile has fewer than n 32x32 sub-tiles are skipped where a larger tile
+//                        exists (round-5 verdict item 1A: force the <1,1> class onto <1,2> / <2,1> / <2,2>)
+//   TBN_TUNE_CORUN=k     every candidate is timed as k+1 concurrent copies (k helper streams beside the launch stream):
+//                        what a launch costs in CU-time beside neighbours, not alone on an empty device.  The helper
+//                        streams run the SAME candidate sequence in lockstep -- forked once in front of a GEMM's batch of
+//                        candidates and joined once behind it: a fork / join per candidate (the first form of this knob)
+//                        put ~70 us of cross-stream waits into every 50 - 150-us bracket and made the ranking noise
+// What one autotune call owns on the device: a pair of timing events per candidate and the co-run helper streams.
+struct TuneRig {
+  hipEvent_t ce[2 * kMaxCand] = {};
+  const int corun;
+  hipStream_t hs[3] = {};
+  hipEvent_t hfork = nullptr, hjoin[3] = {};
+  bool ok = true;
+  explicit TuneRig(int corun_) : corun(corun_) {
+    for (hipEvent_t& e : ce) ok = ok && hipEventCreate(&e) == hipSuccess;
+    for (int k = 0; k < corun; ++k) {
+      (void)hipStreamCreateWithFlags(&hs[k], hipStreamNonBlocking);
+      (void)hipEventCreateWithFlags(&hjoin[k], hipEventDisableTiming);
+    }
+    if (corun) (void)hipEventCreateWithFlags(&hfork, hipEventDisableTiming);
+  }
+  ~TuneRig() {
+    for (hipEvent_t e : ce)
+      if (e != nullptr) (void)hipEventDestroy(e);
+    if (corun) {
+      (void)hipDeviceSynchronize();
+      (void)hipEventDestroy(hfork);
+      for (int k = 0; k < corun; ++k) {
+        (void)hipEventDestroy(hjoin[k]);
+        (void)hipStreamDestroy(hs[k]);
+      }
+    }
+  }
+  TuneRig(const TuneRig&) = delete;
+  TuneRig& operator=(const TuneRig&) = delete;
+};
+
+// Times the candidates of ONE GEMM (or sibling pair): `launch(cand, stream)` issues a candidate once.  All candidates are
+// enqueued back to back, each as an untimed first run and a second run between its own pair of events, and the host waits
+// ONCE (a host round trip per candidate cost more than the small layers' kernels themselves).  ms[k] = the measured time
+// of candidate k.  The co-run copies (TBN_TUNE_CORUN): the same two launches, in the same order, on the helper streams --
+// forked behind everything queued on `st`, joined behind the last candidate.
+template <class Launch>
+int time_candidates(TuneRig& X, hipStream_t st, const Cand* cand, int ncand, Launch&& launch, float* ms) {
+  int rc = TBN_OK, timed = 0;
+  if (X.corun) {
+    (void)hipEventRecord(X.hfork, st);
+    for (int h = 0; h < X.corun; ++h) (void)hipStreamWaitEvent(X.hs[h], X.hfork, 0);
+  }
+  for (int k = 0; k < ncand && rc == TBN_OK; ++k) {
+    for (int h = 0; h < X.corun && rc == TBN_OK; ++h)
+      for (int rep = 0; rep < 2 && rc == TBN_OK; ++rep) rc = launch(cand[k], X.hs[h]);
+    if (rc == TBN_OK) rc = launch(cand[k], st);
+    (void)hipEventRecord(X.ce[2 * k], st);
+    if (rc == TBN_OK) rc = launch(cand[k], st);
+    (void)hipEventRecord(X.ce[2 * k + 1], st);
+    timed = k + 1;
+  }
+  for (int h = 0; h < X.corun; ++h) order_after(X.hjoin[h], X.hs[h], st);
+  if (timed > 0) (void)hipEventSynchronize(X.ce[2 * timed - 1]);
+  if (X.corun) (void)hipStreamSynchronize(st);
+  for (int k = 0; k < ncand && rc == TBN_OK; ++k) {
+    ms[k] = 0.f;
+    (void)hipEventElapsedTime(&ms[k], X.ce[2 * k], X.ce[2 * k + 1]);
+  }
+  return rc;
+}
+
+// The fastest candidate (its index; -1: there is none).  A candidate is timed alone, back to back, on L2-warm operands; in
+// the step its launches share the fabric with the HBM-bound BN kernels of the other streams.  The per-tap gather forms
+// (register-staged / LDS-DMA) move 2-6x the bytes of the LDS-halo form on a 3x3 layer (profiles/r03_pmc_traffic.json):
+// where an LDS-halo candidate exists, they must beat it by a margin to win.  The margin only RANKS: ms[] stays the time.
+// (same-box A/B of the three-stream step: margin 0 -> 36.74, 6 % -> 36.49, 15 % -> 36.53 ms; one-stream GEMM totals equal.
+//  A like margin AGAINST the single-stage register-staged loop -- more latency tolerance beside the other streams --
+//  measured worse: 36.06 -> 36.33 / 36.38 ms at 5 / 12 %)
+int rank_candidates(const Cand* cand, const float* ms, int ncand) {
+  static const float halo_bias = 0.01f * (float)tbn_env_int("TBN_TUNE_HALO_BIAS", 8, 0, 100);
+  bool any_halo = false;
+  for (int k = 0; k < ncand; ++k) any_halo = any_halo || cand[k].halo == 1;
+  float best = 1e30f;
+  int bk = -1;
+  for (int k = 0; k < ncand; ++k) {
+    const float t = (any_halo && cand[k].halo != 1) ? ms[k] * (1.f + halo_bias) : ms[k];
+    if (t < best) {
+      best = t;
+      bk = k;
+    }
+  }
+  return bk;
+}
+
+}  // namespace
+
+extern "C" {
+
 // One-time tile autotuning: times every (MT, NT) tile of the forward and data-gradient implicit GEMM
 // of each layer on the real shapes (2 launches each, hipEvents) and stores the fastest in the plan.
 // Synchronises the device (the only entry point that does); activations in `workspace` are clobbered.
@@ -1585,272 +1704,142 @@ int tbn_backbone_autotune(tbn_backbone_plan* P, int training, const tbn_backbone
   float* ws = (float*)workspace;
   const int R = P->frames;
   const int tr = training ? 1 : 0;
-  float* scale = ws + P->stats_off + 2 * P->chan_floats;
-  float* shift = scale + P->chan_floats;
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+  static const int min_tile = tbn_env_int("TBN_TUNE_MIN_TILE", 1, 1, 4);   // experiment knobs: see TuneRig
+  static const int corun = tbn_env_int("TBN_TUNE_CORUN", 0, 0, 3);
+  TuneRig rig(corun);
+  if (!rig.ok) {
     tbn_set_error("autotune: hipEventCreate failed");
     return TBN_ERR_LAUNCH;
   }
   // candidates are timed one at a time: whatever other streams still run (the other modality backbones of a first
   // step) would make the choice depend on what happened to overlap -> drain the device first
   (void)hipDeviceSynchronize();
-  // all candidates of one GEMM are enqueued back to back, each between its own pair of events, and the host waits
-  // ONCE per GEMM (a host round trip per candidate cost more than the small layers' kernels themselves)
-  constexpr int kMaxCand = 40;
-  hipEvent_t ce[2 * kMaxCand];
-  for (int i = 0; i < 2 * kMaxCand; ++i) {
-    ce[i] = nullptr;
-    if (hipEventCreate(&ce[i]) != hipSuccess) {
-      tbn_set_error("autotune: hipEventCreate failed");
-      for (int k = 0; k < i; ++k) (void)hipEventDestroy(ce[k]);
-      (void)hipEventDestroy(e0);
-      (void)hipEventDestroy(e1);
-      return TBN_ERR_LAUNCH;
-    }
-  }
-  struct Cand { int mt, nt, stages, halo; };
-  int rc = TBN_OK;
-  // Experiment knobs (a -DTBN_EXPERIMENT=1 build only; the shipped library folds both to their defaults):
-  //   TBN_TUNE_MIN_TILE=n  candidates whose wave tile has fewer than n 32x32 sub-tiles are skipped where a larger tile
-  //                        exists (round-5 verdict item 1A: force the <1,1> class onto <1,2> / <2,1> / <2,2>)
-  //   TBN_TUNE_CORUN=k     every candidate is timed as k+1 concurrent copies (k helper streams beside the launch stream):
-  //                        what a launch costs in CU-time beside neighbours, not alone on an empty device.  The helper
-  //                        streams run the SAME candidate sequence in lockstep -- forked once in front of a GEMM's batch of
-  //                        candidates and joined once behind it: a fork / join per candidate (the first form of this knob)
-  //                        put ~70 us of cross-stream waits into every 50 - 150-us bracket and made the ranking noise
-  static const int min_tile = tbn_env_int("TBN_TUNE_MIN_TILE", 1, 1, 4);
-  static const int corun = tbn_env_int("TBN_TUNE_CORUN", 0, 0, 3);
-  hipStream_t hs[3] = {nullptr, nullptr, nullptr};
-  hipEvent_t hfork = nullptr, hjoin[3] = {nullptr, nullptr, nullptr};
-  for (int k = 0; k < corun; ++k) {
-    (void)hipStreamCreateWithFlags(&hs[k], hipStreamNonBlocking);
-    (void)hipEventCreateWithFlags(&hjoin[k], hipEventDisableTiming);
-  }
-  if (corun) (void)hipEventCreateWithFlags(&hfork, hipEventDisableTiming);
-  // the copies of a candidate on the helper streams: forked behind everything queued on `st`, joined before the next candidate
-  auto corun_fork = [&]() {
-    if (!corun) return;
-    (void)hipEventRecord(hfork, st);
-    for (int k = 0; k < corun; ++k) (void)hipStreamWaitEvent(hs[k], hfork, 0);
-  };
-  auto corun_join = [&]() {
-    for (int k = 0; k < corun; ++k) {
-      (void)hipEventRecord(hjoin[k], hs[k]);
-      (void)hipStreamWaitEvent(st, hjoin[k], 0);
-    }
-  };
+  Cand cand[kMaxCand];
+  float ms[kMaxCand];
   for (auto& c : P->convs) {
-    for (int pass = 0; pass < 2 && rc == TBN_OK; ++pass) {  // 0: forward, 1: data gradient
+    for (int pass = 0; pass < 2; ++pass) {  // 0: forward, 1: data gradient
       if (pass == 1 && (!training || !c.need_dgrad)) continue;
+      if (pass == 0 && !training && c.nparts > 1) continue;   // eval tuning on single-part layers only keeps all writes in range
+      const int rowmode = c.stem && pass == 0;
       ConvP p;
       if (pass == 0) {
+        // the step's own epilogue, written into the layer's own y buffer (training) or its first destination (eval);
+        // the statistics partials of every candidate go to scratch slot 0
         fill_fwd(P, c, training, ws, prm->weight, R, &p);
+        fill_fwd_epilogue(P, c, training, ws, 0, &p);
+        // the first destination only.  What the two calls leave anyway: training writes one y segment, and eval tunes
+        // single-part layers, none of which is pooled (a pooled part, whose segment would be its raw buffer with
+        // raw_seg1 set, only occurs as the last part of a fused 1x1 group of at least two parts)
         p.nseg = 1;
-        p.mode = training ? CONV_EPI_STATS : CONV_EPI_EVAL;
-        p.scale = scale + c.c_off;
-        p.shift = shift + c.c_off;
-        p.stat_partial = ws + P->partial_off;
-        // write into the layer's own y buffer (training) or its first destination (eval)
-        if (training) {
-          p.seg[0].ptr = ws + c.y_off;
-          p.seg[0].ld = c.cout;
-        } else {
-          if (c.nparts > 1) continue;   // eval tuning on single-part layers only keeps all writes in range
-          const Buf& db = P->bufs[c.parts[0].dst_buf];
-          p.seg[0].ptr = ws + db.off + c.parts[0].dst_choff;
-          p.seg[0].ld = db.C;
-        }
       } else {
         fill_dgrad(P, c, ws, R, &p);
       }
       // fastest of the candidates in isolation.  (Measured alternatives that lost: preferring the largest tile
       // within 3-15 % of the fastest -- monotonically slower steps; autotuning the weight-gradient tile the same
       // way -- 0.4 % slower than the size heuristic of tbn_wgrad_plan.)
-      float best = 1e30f;
-      int bm = 1, bn = 1, bs = 2, bh = 0;
       static const int force_halo = tbn_env_int("TBN_FORCE_HALO", -1, -1, 1);   // tests: 0 / 1
-      Cand cand[kMaxCand];
+      static const int use_dma = tbn_env_int("TBN_USE_DMA", 1, 0, 1);
+      static const int use_sk4 = tbn_env_int("TBN_USE_SK4", 1, 0, 1);
       int ncand = 0;
-      corun_fork();
-      for (int mt = 1; mt <= 2 && rc == TBN_OK; ++mt)
-        for (int nt = 1; nt <= 4 && rc == TBN_OK; ++nt)
-          for (int stg = 0; stg <= 4 && rc == TBN_OK; ++stg) {   // 0: LDS-halo kernel (3x3 / stride-1 layers), 3: LDS-DMA,
+      for (int mt = 1; mt <= 2; ++mt)
+        for (int nt = 1; nt <= 4; ++nt)
+          for (int stg = 0; stg <= 4; ++stg) {                   // 0: LDS-halo kernel (3x3 / stride-1 layers), 3: LDS-DMA,
             if (32 * (nt - 1) >= p.Cout) continue;               // 4: 32-row tiles, waves split K (small maps)
-            static const int use_dma = tbn_env_int("TBN_USE_DMA", 1, 0, 1);
-            static const int use_sk4 = tbn_env_int("TBN_USE_SK4", 1, 0, 1);
-            p.halo = stg == 0 ? 1 : (stg == 3 ? 2 : (stg == 4 ? 3 : 0));
+            const int halo = stg == 0 ? 1 : (stg == 3 ? 2 : (stg == 4 ? 3 : 0));
             if (stg == 4) {
-              if ((c.stem && pass == 0) || p.up != 1 || !use_sk4 || force_halo == 1 || p.M > kSk4MaxRows || mt > 2 || nt > 2)
-                continue;
+              if (rowmode || p.up != 1 || !use_sk4 || force_halo == 1 || p.M > kSk4MaxRows || mt > 2 || nt > 2) continue;
             } else if (stg == 3) {
-              if ((c.stem && pass == 0) || p.up != 1 || !use_dma || force_halo == 1) continue;
-            } else if (p.halo) {
-              const size_t lb = (c.stem && pass == 0) ? 0 : tbn_conv_halo_lds_bytes(p, mt, nt);
+              if (rowmode || p.up != 1 || !use_dma || force_halo == 1) continue;
+            } else if (halo) {
+              const size_t lb = rowmode ? 0 : tbn_conv_halo_lds_bytes(p, mt, nt);
               if (lb == 0 || lb > 160 * 1024 || force_halo == 0) continue;
-            } else if (force_halo == 1 && !(c.stem && pass == 0) && tbn_conv_halo_lds_bytes(p, 1, 1) > 0) {
+            } else if (force_halo == 1 && !rowmode && tbn_conv_halo_lds_bytes(p, 1, 1) > 0) {
               continue;
             }
-            p.stages = stg == 3 ? 2 : (stg == 4 ? 1 : stg);
             if (ncand >= kMaxCand) continue;
-            if (mt * nt < min_tile && (p.Cout > 32 || mt < 2) && !(c.stem && pass == 0)) continue;   // experiment: no small tiles
-            for (int k = 0; k < corun && rc == TBN_OK; ++k)     // the copies: same two launches, same order, on the helper streams
-              for (int rep = 0; rep < 2 && rc == TBN_OK; ++rep) rc = tbn_launch_conv(p, c.stem && pass == 0, mt, nt, hs[k]);
-            if (rc == TBN_OK) rc = tbn_launch_conv(p, c.stem && pass == 0, mt, nt, st);     // untimed first run of the candidate
-            (void)hipEventRecord(ce[2 * ncand], st);
-            if (rc == TBN_OK) rc = tbn_launch_conv(p, c.stem && pass == 0, mt, nt, st);
-            (void)hipEventRecord(ce[2 * ncand + 1], st);
-            cand[ncand++] = {mt, nt, p.stages, p.halo};
+            if (mt * nt < min_tile && (p.Cout > 32 || mt < 2) && !rowmode) continue;   // experiment: no small tiles
+            cand[ncand++] = {mt, nt, stg == 3 ? 2 : (stg == 4 ? 1 : stg), halo, 0};
           }
-      corun_join();
-      if (ncand > 0) (void)hipEventSynchronize(ce[2 * ncand - 1]);
-      if (corun) (void)hipStreamSynchronize(st);
-      // A candidate is timed alone, back to back, on L2-warm operands; in the step its launches share the fabric with the
-      // HBM-bound BN kernels of the other streams.  The per-tap gather forms (register-staged / LDS-DMA) move 2-6x the
-      // bytes of the LDS-halo form on a 3x3 layer (profiles/r03_pmc_traffic.json): they must beat it by a margin to win.
-      // (same-box A/B of the three-stream step: margin 0 -> 36.74, 6 % -> 36.49, 15 % -> 36.53 ms; one-stream GEMM totals equal)
-      static const float halo_bias = 0.01f * (float)tbn_env_int("TBN_TUNE_HALO_BIAS", 8, 0, 100);
-      bool any_halo = false;
-      for (int k = 0; k < ncand; ++k) any_halo = any_halo || cand[k].halo == 1;
-      float best_raw = 1e30f;   // the winner's MEASURED time: the traffic margin only ranks candidates, it is not a time
-      for (int k = 0; k < ncand && rc == TBN_OK; ++k) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, ce[2 * k], ce[2 * k + 1]);
-        const float raw = ms;
-        if (any_halo && cand[k].halo != 1) ms *= 1.f + halo_bias;
-        // (a like margin AGAINST the single-stage register-staged loop -- more latency tolerance beside the other
-        //  streams -- measured worse: 36.06 -> 36.33 / 36.38 ms at 5 / 12 %)
-        if (ms < best) {
-          best = ms;
-          best_raw = raw;
-          bm = cand[k].mt;
-          bn = cand[k].nt;
-          bs = cand[k].stages;
-          bh = cand[k].halo;
-        }
-      }
+      TBN_TRY(time_candidates(rig, st, cand, ncand, [&](const Cand& k, hipStream_t s) {
+        p.halo = k.halo;
+        p.stages = k.stages;
+        return tbn_launch_conv(p, rowmode, k.mt, k.nt, s);
+      }, ms));
+      const int w = rank_candidates(cand, ms, ncand);
+      const Cand win = w >= 0 ? cand[w] : Cand{1, 1, 2, 0, 0};
+      const float t_win = w >= 0 ? ms[w] : 1e30f;
       if (pass == 0) {
         Conv::FwdTune& T = c.ft[tr];
-        T.mt = bm;
-        T.nt = bn;
-        T.stages = bs;
-        T.halo = bh;
-        T.t = best_raw;
+        T.mt = win.mt;
+        T.nt = win.nt;
+        T.stages = win.stages;
+        T.halo = win.halo;
+        T.t = t_win;
       } else {
-        c.d_mt = bm;
-        c.d_nt = bn;
-        c.d_stages = bs;
-        c.d_halo = bh;
-        c.t_dgrad = best_raw;
+        c.d_mt = win.mt;
+        c.d_nt = win.nt;
+        c.d_stages = win.stages;
+        c.d_halo = win.halo;
+        c.t_dgrad = t_win;
       }
     }
-    if (rc != TBN_OK) break;
   }
   // sibling pairs (3x3 | double_3x3_1): one launch for both when that beats the two tuned single launches
   static const int use_pairs = tbn_env_int("TBN_USE_PAIRS", 1, 0, 1);
-  for (size_t ci = 0; ci < P->convs.size() && rc == TBN_OK; ++ci) {
+  for (size_t ci = 0; ci < P->convs.size(); ++ci) {
     Conv& c = P->convs[ci];
     c.ft[tr].pair = false;
     if (training) c.pair_dgrad = false;      // an eval-mode tuning run leaves every data-gradient choice alone
     if (c.pair_next < 0 || !use_pairs) continue;
     Conv& c2 = P->convs[c.pair_next];
-    for (int pass = 0; pass < 2 && rc == TBN_OK; ++pass) {
+    for (int pass = 0; pass < 2; ++pass) {
       if (pass == 1 && (!training || c.stride != 1 || c2.stride != 1)) continue;   // stride 2: parity-phase launch
-      ConvP pa, pb;
-      if (pass == 0) {
-        for (int k = 0; k < 2; ++k) {
-          Conv& m = k ? c2 : c;
-          ConvP& p = k ? pb : pa;
-          fill_fwd(P, m, training, ws, prm->weight, R, &p);
-          p.nseg = 1;
-          p.mode = training ? CONV_EPI_STATS : CONV_EPI_EVAL;
-          p.scale = scale + m.c_off;
-          p.shift = shift + m.c_off;
-          p.stat_partial = ws + P->partial_off + (size_t)m.slot * P->partial_floats;
-          if (training) {
-            p.seg[0].ptr = ws + m.y_off;
-            p.seg[0].ld = m.cout;
-          } else {
-            const Buf& db = P->bufs[m.parts[0].dst_buf];
-            p.seg[0].ptr = ws + db.off + m.parts[0].dst_choff;
-            p.seg[0].ld = db.C;
-          }
+      ConvP pm[2];
+      for (int k = 0; k < 2; ++k) {
+        const Conv& m = k ? c2 : c;
+        if (pass == 0) {   // as the single launches above, each member with its own scratch slot
+          fill_fwd(P, m, training, ws, prm->weight, R, &pm[k]);
+          fill_fwd_epilogue(P, m, training, ws, m.slot, &pm[k]);
+          pm[k].nseg = 1;
+        } else {
+          fill_dgrad(P, m, ws, R, &pm[k]);
         }
-      } else {
-        fill_dgrad(P, c, ws, R, &pa);
-        fill_dgrad(P, c2, ws, R, &pb);
       }
-      float best = 1e30f;
-      int bv = 1, bm = 1, bn = 1;
-      Cand cand[kMaxCand];
       int ncand = 0;
-      corun_fork();
-      for (int variant = 0; variant <= 2 && rc == TBN_OK; ++variant) {
-        if (variant == 0 && (tbn_conv_halo_lds_bytes(pa, 1, 1) == 0 || tbn_conv_halo_lds_bytes(pb, 1, 1) == 0)) continue;
-        for (int mt = 1; mt <= 2 && rc == TBN_OK; ++mt)
-          for (int nt = 1; nt <= 2 && rc == TBN_OK; ++nt) {
-            if (variant == 0 && (tbn_conv_halo_lds_bytes(pa, mt, nt) > 160 * 1024 || tbn_conv_halo_lds_bytes(pb, mt, nt) > 160 * 1024))
+      for (int variant = 0; variant <= 2; ++variant) {
+        if (variant == 0 && (tbn_conv_halo_lds_bytes(pm[0], 1, 1) == 0 || tbn_conv_halo_lds_bytes(pm[1], 1, 1) == 0)) continue;
+        for (int mt = 1; mt <= 2; ++mt)
+          for (int nt = 1; nt <= 2; ++nt) {
+            if (variant == 0 && (tbn_conv_halo_lds_bytes(pm[0], mt, nt) > 160 * 1024 || tbn_conv_halo_lds_bytes(pm[1], mt, nt) > 160 * 1024))
               continue;
             if (ncand >= kMaxCand) continue;
             if (mt * nt < min_tile) continue;   // experiment: no small tiles (a (2, 1) pair tile always exists)
-            for (int k = 0; k < corun && rc == TBN_OK; ++k)
-              for (int rep = 0; rep < 2 && rc == TBN_OK; ++rep) rc = tbn_launch_conv_pair(pa, pb, variant, mt, nt, hs[k]);
-            if (rc == TBN_OK) rc = tbn_launch_conv_pair(pa, pb, variant, mt, nt, st);
-            (void)hipEventRecord(ce[2 * ncand], st);
-            if (rc == TBN_OK) rc = tbn_launch_conv_pair(pa, pb, variant, mt, nt, st);
-            (void)hipEventRecord(ce[2 * ncand + 1], st);
-            cand[ncand++] = {mt, nt, variant, 0};
+            cand[ncand++] = {mt, nt, variant == 2 ? 2 : 1, variant == 0 ? 1 : 0, variant};
           }
       }
-      corun_join();
-      if (ncand > 0) (void)hipEventSynchronize(ce[2 * ncand - 1]);
-      if (corun) (void)hipStreamSynchronize(st);
-      static const float pair_halo_bias = 0.01f * (float)tbn_env_int("TBN_TUNE_HALO_BIAS", 8, 0, 100);
-      bool any_halo = false;   // cand[k].stages holds the pair variant: 0 = LDS-halo members (see the margin above)
-      for (int k = 0; k < ncand; ++k) any_halo = any_halo || cand[k].stages == 0;
-      float best_raw = 1e30f;
-      for (int k = 0; k < ncand && rc == TBN_OK; ++k) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, ce[2 * k], ce[2 * k + 1]);
-        const float raw = ms;
-        if (any_halo && cand[k].stages != 0) ms *= 1.f + pair_halo_bias;
-        if (ms < best) {
-          best = ms;
-          best_raw = raw;
-          bm = cand[k].mt;
-          bn = cand[k].nt;
-          bv = cand[k].stages;
-        }
-      }
+      TBN_TRY(time_candidates(rig, st, cand, ncand, [&](const Cand& k, hipStream_t s) {
+        return tbn_launch_conv_pair(pm[0], pm[1], k.variant, k.mt, k.nt, s);
+      }, ms));
+      const int w = rank_candidates(cand, ms, ncand);
+      const Cand win = w >= 0 ? cand[w] : Cand{1, 1, 1, 0, 1};
       const float singles = pass == 0 ? c.ft[tr].t + c2.ft[tr].t : c.t_dgrad + c2.t_dgrad;
       // (margins of 0.88 / 1.05 instead of 0.97 measured 0.1-0.15 ms worse on the three-stream step; moving the weight flip
       //  to the tail of the forward, under the other streams, +-0: 36.81 vs 36.75 ms)
-      const bool take = rc == TBN_OK && best_raw < 0.97f * singles;   // measured pair time against the measured singles
+      const bool take = w >= 0 && ms[w] < 0.97f * singles;   // measured pair time against the measured singles
       if (pass == 0) {
         c.ft[tr].pair = take;
-        c.ft[tr].p_variant = bv;
-        c.ft[tr].p_mt = bm;
-        c.ft[tr].p_nt = bn;
+        c.ft[tr].p_variant = win.variant;
+        c.ft[tr].p_mt = win.mt;
+        c.ft[tr].p_nt = win.nt;
       } else {
         c.pair_dgrad = take;
-        c.pd_variant = bv;
-        c.pd_mt = bm;
-        c.pd_nt = bn;
+        c.pd_variant = win.variant;
+        c.pd_mt = win.mt;
+        c.pd_nt = win.nt;
       }
     }
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  for (int i = 0; i < 2 * kMaxCand; ++i) (void)hipEventDestroy(ce[i]);
-  if (corun) {
-    (void)hipDeviceSynchronize();
-    (void)hipEventDestroy(hfork);
-    for (int k = 0; k < corun; ++k) {
-      (void)hipEventDestroy(hjoin[k]);
-      (void)hipStreamDestroy(hs[k]);
-    }
-  }
-  return rc;
+  return TBN_OK;
 }
 
 int tbn_backbone_flip_weights(const tbn_backbone_plan* P, const tbn_backbone_params* prm, void* workspace, size_t workspace_bytes,
@@ -1949,9 +1938,7 @@ int tbn_backbone_backward(const tbn_backbone_plan* P, const float* dfeatures, co
     const size_t lo = P->convs[P->block_conv[blk]].w_off;
     TBN_REQUIRE(ndef == 0, "backbone_backward: a weight gradient of block %d is still deferred at its bucket boundary", blk);
     if (aux != nullptr && join.forked) {   // the bucket's weight gradients ran on the aux stream: order the launch stream behind them
-      hipEvent_t e = PM->ev[ev_next++];
-      (void)hipEventRecord(e, aux);
-      (void)hipStreamWaitEvent(st_main, e, 0);
+      order_after(PM->ev[ev_next++], aux, st_main);
     }
     g->bucket_cb(g->bucket_user, lo, bucket_hi - lo);
     bucket_hi = lo;
@@ -1967,10 +1954,7 @@ int tbn_backbone_backward(const tbn_backbone_plan* P, const float* dfeatures, co
       // reverse walk: a forward JOIN is where the side chain of the block STARTS (the block's output gradient is final),
       // a forward FORK where it is joined back, ahead of the 1x1 group's BN backward
       const bool fork = o.kind == OP_JOIN;
-      hipEvent_t e = PM->ev[ev_next++];
-      (void)hipEventRecord(e, fork ? st_main : side);
-      (void)hipStreamWaitEvent(fork ? side : st_main, e, 0);
-      sjoin.open = fork;
+      sjoin.turn(PM->ev[ev_next++], fork);
       if (!fork) {
         for (int k = 0; k < ndef; ++k) TBN_TRY(issue_wgrad(P->convs[deferred[k]], st_main));
         ndef = 0;
@@ -2048,11 +2032,7 @@ int tbn_backbone_backward(const tbn_backbone_plan* P, const float* dfeatures, co
           // S1 / S2 partials were formed by the data-gradient epilogue that finished dz (conv RedSeg)
           const Conv& f = P->convs[q.red_src];
           L.partial = ws + q.bpart_off;
-          int dmt = f.d_mt;    // M tile of the launch that wrote the partials (a paired launch has its own tile)
-          if (!br && f.pair_next >= 0 && f.pair_dgrad) dmt = f.pd_mt;
-          if (!br && f.pair_prev >= 0 && P->convs[f.pair_prev].pair_dgrad) dmt = P->convs[f.pair_prev].pd_mt;
-          const bool paired = !br && ((f.pair_next >= 0 && f.pair_dgrad) || (f.pair_prev >= 0 && P->convs[f.pair_prev].pair_dgrad));
-          L.ext_parts = tbn_conv_red_rows(R, f.inH, f.inW, f.stride, paired ? 128 * dmt : tile_rows(f.d_halo, dmt));
+          L.ext_parts = tbn_conv_red_rows(R, f.inH, f.inW, f.stride, writer_rows(P, f, GEMM_DGRAD, br));
         } else {
           L.partial = partial + (size_t)slot * P->partial_floats;
           L.ext_parts = 0;
@@ -2100,9 +2080,7 @@ int tbn_backbone_backward(const tbn_backbone_plan* P, const float* dfeatures, co
     // weight gradient -- on the aux stream when given: it only reads dy (final after the BN backward) and
     // the layer input, so it overlaps the data-gradient / BN-backward chain that continues on `st`
     if (aux != nullptr) {
-      hipEvent_t e = PM->ev[ev_next++];
-      (void)hipEventRecord(e, st);
-      (void)hipStreamWaitEvent(aux, e, 0);
+      order_after(PM->ev[ev_next++], st, aux);
       join.forked = true;
       TBN_TRY(issue_wgrad(c, aux));
     } else if (br && o.side) {
@@ -2117,8 +2095,9 @@ int tbn_backbone_backward(const tbn_backbone_plan* P, const float* dfeatures, co
       TBN_TRY(issue_wgrad(c, st));
     }
     if (c.need_dgrad) {
-      if (!br && c.pair_prev >= 0 && P->convs[c.pair_prev].pair_dgrad) continue;   // issued with its sibling (next in this walk)
-      if (!br && c.pair_next >= 0 && c.pair_dgrad) {
+      const int role = pair_role(P, c, GEMM_DGRAD, br);
+      if (role == 2) continue;   // issued with its sibling (next in this walk)
+      if (role == 1) {
         const Conv& c2 = P->convs[c.pair_next];
         ConvP pa, pb;
         fill_dgrad(P, c, ws, R, &pa);

@@ -613,7 +613,7 @@ __global__ __launch_bounds__(256) void dropout_fwd_kernel(const float* __restric
 // and the mean divides by the number of the other rows; any other out-of-range label poisons the loss with NaN instead of
 // reading out of bounds (torch raises a device assert there).
 struct CeHeads {
-  int n;
+  int n;   // read by no kernel; kept, because dropping it moves the kernel arguments of the three ce_heads kernels
   int col0[4], ncls[4];
   const long long* label[4];
 };
@@ -774,8 +774,7 @@ int tbn_mha_q1_fwd(const float* q, const float* kv, const float* drop_mask, floa
   TBN_REQUIRE(t >= 1 && t <= 32 && heads >= 1 && e % heads == 0 && (e / heads) % 4 == 0,
               "mha_q1: need 1<=T<=32 and head_dim %% 4 == 0");
   hipStream_t st = (hipStream_t)stream;
-  // ctx doubles as nothing else; post-dropout probabilities are staged in avg_w's tail is not possible
-  // (r*t floats only), so they go to `probs + r*heads*t` -- the probs buffer is 2*r*heads*t floats.
+  // the probs buffer is 2*r*heads*t floats: the softmax probabilities, then the post-dropout probabilities
   float* pdrop = probs + (size_t)r * heads * t;
   const int blocks = cdiv(r * heads, 4);
   if (t <= 16)
