@@ -133,6 +133,10 @@ SIGNATURES = {
                           c_i] + [c_i] * 5 + [c_f, c_fp]),
     "tbn_attn_weights_fwd": (c_i, [c_fp, c_i, c_fp, c_f, c_i, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_fp]),
     "tbn_attn_weights_bwd": (c_i, [c_fp, c_fp, c_fp, c_f, c_fp, c_i, c_i, c_i, c_fp]),
+    "tbn_attn_reg_fwd": (c_i, [c_fp, c_i, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_f, c_f, c_i, c_f, c_i, c_fp, c_fp,
+                               c_fp]),
+    "tbn_attn_reg_bwd": (c_i, [c_fp, c_fp, c_i, c_fp, c_i, c_fp, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_f, c_f, c_i, c_f,
+                               c_i, c_fp, c_i, c_fp]),
     "tbn_weighted_sum_fwd": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp]),
     "tbn_weighted_sum_bwd": (c_i, [c_fp, c_i, c_fp, c_fp, c_i, c_i, c_i, c_fp]),
     "tbn_segment_mean_fwd": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp]),

@@ -1,5 +1,8 @@
 """ContrastLoss on the attention weights -- mirrors reference core/models/contrast_loss.py:4-25.
-A handful of elementwise torch ops on an (R, T<=25) tensor; kept as PyTorch-ROCm ops."""
+The definition of the term: TBNModel.get_loss evaluates it (with the prior and entropy terms) in the HIP operator
+ops.attn_regularisers (tbn_attn_reg_fwd / _bwd) when the weights are float32 on the GPU and the reduction is mean or
+batchmean; this module runs on CPU tensors, for the unreduced reduction="sum" vector and whenever the operator does not
+cover the criterion table (TBNModel._fused_attention_losses returns None)."""
 import torch.nn as nn
 
 

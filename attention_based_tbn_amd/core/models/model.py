@@ -19,6 +19,7 @@ from torch.distributions import Categorical
 from ... import ops
 from .attention import MultiheadedAttention, PositionalEncoding, PrototypeAttention, UniModalAttention
 from .bn_inception import bninception
+from .contrast_loss import ContrastLoss
 
 
 class _ArenaCatFn(torch.autograd.Function):
@@ -120,6 +121,9 @@ class TBNModel(nn.Module):
         # the modality streams are joined for the heads, so they run beside the heads' small launches instead of in the
         # serial turn between forward and backward (BNInception.flip_weights_early; bench.py --no-early-flip for the A/B)
         self.flip_weights_early = True
+        # get_loss: the prior / contrast / entropy terms of the attention weights from ops.attn_regularisers where it covers
+        # the case (_fused_attention_losses); False keeps them on the torch ops -- the switch of an A/B script
+        self.fused_attention_losses = True
         self.shared_streams = {}          # {"Flow": "RGB"}: Flow's backbone runs on RGB's stream (fewer concurrent chains)
         if cfg.model.agg_type.lower() == "avg":
             self.agg_type = "avg"
@@ -370,6 +374,55 @@ class TBNModel(nn.Module):
             labels.append(lab)
         return dict(zip(keys, ops.cross_entropy_heads(base, heads, labels)))
 
+    def _fused_attention_losses(self, criterion, target, wts, mults):
+        """(prior, contrast, entropy, total) of the attention-weight loss terms from one operator
+        (ops.attn_regularisers: two launches forward, one backward; a term that is off is None), or None when the operator
+        does not cover the case -- the torch code in get_loss then runs unchanged.  Covered: float32 GPU weights; a prior
+        criterion that is exactly nn.KLDivLoss (log_target False, with wt_loss "kl") or exactly nn.MSELoss /
+        nn.SmoothL1Loss (beta 1, with another wt_loss) under a reduction the operator has, against float32 GPU target
+        weights; a contrast criterion that is exactly ContrastLoss with reduction mean or batchmean."""
+        att = self.cfg.model.attention
+        if not (self.fused_attention_losses and torch.is_tensor(wts) and wts.is_cuda and wts.dtype == torch.float32
+                and wts.dim() == 2):
+            return None
+        kind, red, prior = None, "sum", None
+        if att.use_prior:
+            crit = criterion.get("prior")
+            if type(crit) is nn.KLDivLoss:
+                kind = "kl"
+                if att.wt_loss != "kl" or getattr(crit, "log_target", False):
+                    return None
+            elif type(crit) is nn.MSELoss or type(crit) is nn.SmoothL1Loss:
+                kind = "mse" if type(crit) is nn.MSELoss else "smoothl1"
+                if att.wt_loss == "kl" or getattr(crit, "beta", 1.0) != 1.0:
+                    return None
+            else:
+                return None
+            red = crit.reduction
+            if red not in (("sum", "mean", "batchmean") if kind == "kl" else ("sum", "mean")):
+                return None
+            prior = target.get("weights")
+            if not (torch.is_tensor(prior) and prior.is_cuda and prior.dtype == torch.float32 and prior.dim() == 4):
+                return None
+            b, n, _, _ = prior.shape
+            assert wts.shape[0] == b * n
+            prior = prior.reshape(b * n, -1)
+            if prior.shape != wts.shape:
+                return None
+        thresh = 0.0
+        if att.use_contrast:
+            crit = criterion.get("contrast")
+            if type(crit) is not ContrastLoss or crit.reduction not in ("mean", "batchmean"):
+                return None
+            thresh = crit.threshold
+        if kind is None and not att.use_contrast and not att.use_entropy:
+            return None
+        # reference model.py:316-317 rebinds `wts` to log(wts + 1e-7) for the kl prior, and the contrast and entropy terms
+        # (:320-324) then read the rebound tensor
+        return ops.attn_regularisers(wts, prior, prior_kind=kind, prior_reduction=red, contrast_thresh=thresh,
+                                     use_contrast=att.use_contrast, use_entropy=att.use_entropy, mults=mults,
+                                     training=self.training, entropy_thresh=att.entropy_thresh, log_rebind=kind == "kl")
+
     def get_loss(self, criterion, target, preds, epoch=0):
         assert isinstance(target, dict)
         assert isinstance(preds, dict)
@@ -392,6 +445,14 @@ class TBNModel(nn.Module):
                 contrast_multiplier = att.contrast_decay
                 entropy_multiplier = att.entropy_decay
             wts = preds["weights"].squeeze(1)
+            reg = self._fused_attention_losses(criterion, target, wts,
+                                               (prior_multiplier, contrast_multiplier, entropy_multiplier))
+            if reg is not None:
+                for key, term in zip(("prior", "contrast", "entropy"), reg[:3]):
+                    if term is not None:
+                        loss[key] = term
+                loss["total"] += reg[3]
+                return loss, batch_size
             if att.use_prior:
                 b, n, _, _ = target["weights"].shape
                 assert wts.shape[0] == b * n

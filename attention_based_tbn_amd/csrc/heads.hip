@@ -2,9 +2,11 @@
 // multi-head attention core (one 64-lane wave per (sample, head): dot products and the softmax
 // are wavefront reductions), the general attention core (any number of queries, up to 1024 keys, scores in LDS), the
 // attention-weight softmax of the learnt variants (gumbel noise, straight-through one-hot, prototype mix),
-// fixed-attention weighted sum, temporal-consensus mean.
+// fixed-attention weighted sum, temporal-consensus mean, the cross entropy of the class heads and the regularisers of the
+// attention weights (prior / contrast / entropy losses).
 //
-// Reference: core/models/attention.py:8-145, core/models/model.py:62-67,178-203,224-237.
+// Reference: core/models/attention.py:8-145, core/models/model.py:62-67,178-203,224-237,272-279,299-332,
+// core/models/contrast_loss.py:4-25.
 // All tensors are row-major with channels fastest: audio sequence (r, t, c), features (r, c).
 #include "tbn_common.h"
 #include "../../include/tbn_hip.h"
@@ -15,6 +17,11 @@ static inline int ew_grid(size_t items) {
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
@@ -680,6 +687,155 @@ __global__ __launch_bounds__(256) void ce_heads_bwd_kernel(const float* __restri
   for (int c = threadIdx.x; c < hd.ncls[h]; c += 256) out[o + c] = dsc[o + c] * g;
 }
 
+// ---------------------------------------------------------------- attention-weight regularisers (prior, contrast, entropy)
+// Reference core/models/model.py:299-332 (the prior criterion on log(w + 1e-7) or w, Categorical(probs=w + 1e-6).entropy()
+// with its threshold switch-off) and core/models/contrast_loss.py:4-25.  One wave (a 64-thread workgroup) per row of
+// w (R, T), lanes stride over T; the row terms land in rowterms[3 * R] and attn_reg_mean_kernel -- one wave -- sums them
+// in a fixed order (no atomics) and forms the four losses.  x, the tensor the contrast and entropy terms read, is w, or
+// with log_rebind the log(w + 1e-7) that model.py:316-317 rebinds `wts` to for the kl prior.
+struct AttnReg {
+  int prior_kind, prior_red, use_contrast, use_entropy, training, log_rebind;
+  float contrast_thresh, prior_mult, contrast_mult, entropy_mult, entropy_thresh;
+};
+#define ATTN_REG_EPS_W 1e-7f    // model.py:317
+#define ATTN_REG_EPS_Q 1e-6f    // model.py:324
+#define ATTN_REG_EPS_P 1.1920928955078125e-7f   // FLT_EPSILON: torch.distributions.utils.clamp_probs in fp32
+
+// what the summed prior terms are divided by: 1 (sum), r*t (mean) or r (batchmean)
+__device__ __forceinline__ double attn_reg_prior_div(const AttnReg& a, int R, int T) {
+  return a.prior_red == TBN_ATTN_RED_SUM ? 1.0 : (a.prior_red == TBN_ATTN_RED_MEAN ? (double)R * (double)T : (double)R);
+}
+// log(w + 1e-7) where a term reads it (the kl prior, the rebound x), else unused
+__device__ __forceinline__ float attn_reg_logw(const AttnReg& a, float wv) {
+  return (a.prior_kind == TBN_ATTN_PRIOR_KL || a.log_rebind) ? logf(wv + ATTN_REG_EPS_W) : 0.f;
+}
+
+__global__ __launch_bounds__(64) void attn_reg_rows_kernel(const float* __restrict__ w, int w_ld,
+                                                           const float* __restrict__ prior, int prior_ld, int R, int T,
+                                                           AttnReg a, float* __restrict__ rowterms) {
+  const int lane = threadIdx.x;
+  const size_t row = blockIdx.x;
+  const float* wr = w + row * w_ld;
+  const float* pr = a.prior_kind ? prior + row * prior_ld : nullptr;
+  double sp = 0.0, sc = 0.0, sq = 0.0;   // fp32 terms, summed in double: the row sums carry no error of their own
+  for (int c = lane; c < T; c += 64) {
+    const float wv = wr[c];
+    const float lw = attn_reg_logw(a, wv);
+    if (a.prior_kind == TBN_ATTN_PRIOR_KL) {
+      const float p = pr[c];
+      sp += p > 0.f ? p * (logf(p) - lw) : 0.f;
+    } else if (a.prior_kind) {
+      const float d = wv - pr[c], ad = fabsf(d);
+      sp += a.prior_kind == TBN_ATTN_PRIOR_MSE ? d * d : (ad < 1.f ? 0.5f * d * d : ad - 0.5f);
+    }
+    const float x = a.log_rebind ? lw : wv;
+    sc += x >= a.contrast_thresh ? -x : x;
+    sq += x + ATTN_REG_EPS_Q;
+  }
+  sp = wave_sum(sp);
+  sc = wave_sum(sc);
+  double h = 0.0;
+  if (a.use_entropy) {
+    const float s = (float)wave_sum(sq);
+    for (int c = lane; c < T; c += 64) {
+      const float wv = wr[c];
+      const float x = a.log_rebind ? attn_reg_logw(a, wv) : wv;
+      const float p = (x + ATTN_REG_EPS_Q) / s;
+      h += p * logf(fminf(fmaxf(p, ATTN_REG_EPS_P), 1.f - ATTN_REG_EPS_P));
+    }
+    h = -wave_sum(h);
+  }
+  if (lane == 0) {
+    rowterms[row] = (float)sp;
+    rowterms[(size_t)R + row] = a.use_contrast ? (float)sc : 0.f;
+    rowterms[2 * (size_t)R + row] = (float)h;
+  }
+}
+
+// entropy multiplier after the switch-off of model.py:326-331, from the entropy loss the forward pass wrote
+__device__ __forceinline__ float attn_reg_entropy_mult(const AttnReg& a, float entropy) {
+  return (a.training && a.entropy_mult > 0.f && entropy < a.entropy_thresh) ? 0.f : a.entropy_mult;
+}
+
+__global__ __launch_bounds__(64) void attn_reg_mean_kernel(const float* __restrict__ rowterms, int R, int T, AttnReg a,
+                                                           float* __restrict__ losses) {
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (int i = threadIdx.x; i < R; i += 64) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) acc[k] += (double)rowterms[(size_t)k * R + i];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o);
+  if (threadIdx.x == 0) {
+    const float prior = a.prior_kind ? (float)(acc[0] / attn_reg_prior_div(a, R, T)) : 0.f;
+    const float contrast = a.use_contrast ? (float)(acc[1] / (double)R) : 0.f;
+    const float entropy = a.use_entropy ? (float)(acc[2] / (double)R) : 0.f;
+    float total = 0.f;
+    if (a.prior_kind) total += a.prior_mult * prior;
+    if (a.use_contrast) total += a.contrast_mult * contrast;
+    if (a.use_entropy) total += attn_reg_entropy_mult(a, entropy) * entropy;
+    losses[0] = prior;
+    losses[1] = contrast;
+    losses[2] = entropy;
+    losses[3] = total;
+  }
+}
+
+__global__ __launch_bounds__(64) void attn_reg_bwd_kernel(const float* __restrict__ up, const float* __restrict__ w, int w_ld,
+                                                          const float* __restrict__ prior, int prior_ld,
+                                                          const float* __restrict__ losses, int R, int T, AttnReg a,
+                                                          float* __restrict__ dw, int dw_ld) {
+  const int lane = threadIdx.x;
+  const size_t row = blockIdx.x;
+  const float* wr = w + row * w_ld;
+  const float* pr = a.prior_kind ? prior + row * prior_ld : nullptr;
+  const float u3 = up[3], invR = 1.f / (float)R;
+  const float gp = a.prior_kind ? (float)((double)(up[0] + u3 * a.prior_mult) / attn_reg_prior_div(a, R, T)) : 0.f;
+  const float gc = a.use_contrast ? (up[1] + u3 * a.contrast_mult) * invR : 0.f;
+  const float ge = a.use_entropy ? (up[2] + u3 * attn_reg_entropy_mult(a, losses[2])) * invR : 0.f;
+  // entropy through the normalisation p = q / s: dH/dq_j = (g_j - sum_k g_k p_k) / s with g_j = dH/dp_j =
+  // -(log clamp(p_j) + [p_j inside the clamp]); inside the clamp everywhere this is -(log p_j + H_row) / s
+  float s = 1.f, gdot = 0.f;
+  if (a.use_entropy) {
+    double sq = 0.0, gd = 0.0;
+    for (int c = lane; c < T; c += 64) {
+      const float wv = wr[c];
+      sq += (a.log_rebind ? attn_reg_logw(a, wv) : wv) + ATTN_REG_EPS_Q;
+    }
+    s = (float)wave_sum(sq);
+    for (int c = lane; c < T; c += 64) {
+      const float wv = wr[c];
+      const float p = ((a.log_rebind ? attn_reg_logw(a, wv) : wv) + ATTN_REG_EPS_Q) / s;
+      const bool in = p >= ATTN_REG_EPS_P && p <= 1.f - ATTN_REG_EPS_P;
+      gd += -(logf(fminf(fmaxf(p, ATTN_REG_EPS_P), 1.f - ATTN_REG_EPS_P)) + (in ? 1.f : 0.f)) * p;
+    }
+    gdot = (float)wave_sum(gd);
+  }
+  for (int c = lane; c < T; c += 64) {
+    const float wv = wr[c];
+    const float we = wv + ATTN_REG_EPS_W;
+    float g = 0.f;
+    if (a.prior_kind == TBN_ATTN_PRIOR_KL) {
+      const float p = pr[c];
+      g = p > 0.f ? -(p * gp) / we : 0.f;
+    } else if (a.prior_kind) {
+      const float d = wv - pr[c];
+      g = gp * (a.prior_kind == TBN_ATTN_PRIOR_MSE ? 2.f * d : (fabsf(d) < 1.f ? d : (d > 0.f ? 1.f : -1.f)));
+    }
+    const float x = a.log_rebind ? attn_reg_logw(a, wv) : wv;
+    float gx = 0.f;
+    if (a.use_contrast) gx = x >= a.contrast_thresh ? -gc : gc;
+    if (a.use_entropy) {
+      const float p = (x + ATTN_REG_EPS_Q) / s;
+      const bool in = p >= ATTN_REG_EPS_P && p <= 1.f - ATTN_REG_EPS_P;
+      const float gj = -(logf(fminf(fmaxf(p, ATTN_REG_EPS_P), 1.f - ATTN_REG_EPS_P)) + (in ? 1.f : 0.f));
+      gx += ge * ((gj - gdot) / s);
+    }
+    dw[row * dw_ld + c] = g + (a.log_rebind ? gx / we : gx);
+  }
+}
+
 extern "C" {
 
 int tbn_dropout_fwd(const float* x, const float* rnd, float p, float* y, float* mask, size_t count, void* stream) {
@@ -870,6 +1026,70 @@ int tbn_attn_weights_bwd(const float* dw, const float* soft, const float* protos
               AW_LIMITS " (r = %d, k = %d, t = %d, tau = %g)", r, k, t, (double)tau);
   TBN_KLAUNCH(attn_weights_bwd_kernel, dim3(r), dim3(64), 0, (hipStream_t)stream, dw, soft, protos, tau, dlogits, k, t);
   TBN_CHECK_LAUNCH("attn_weights_bwd");
+  return TBN_OK;
+}
+
+// the argument checks the two attn_reg entries share; fills `a`
+static int attn_reg_args(const float* w, int w_ld, const float* prior, int prior_ld, int r, int t, int prior_kind,
+                         int prior_reduction, int use_contrast, float contrast_thresh, int use_entropy, float prior_mult,
+                         float contrast_mult, float entropy_mult, int training, float entropy_thresh, int log_rebind,
+                         AttnReg* a) {
+  TBN_REQUIRE(w, "attn_reg: null argument (only prior may be NULL, with TBN_ATTN_PRIOR_NONE)");
+  TBN_REQUIRE(r >= 1 && t >= 1 && w_ld >= t, "attn_reg: need r >= 1, t >= 1 and w_ld >= t (r = %d, t = %d, w_ld = %d)", r, t,
+              w_ld);
+  TBN_REQUIRE(prior_kind >= TBN_ATTN_PRIOR_NONE && prior_kind <= TBN_ATTN_PRIOR_SMOOTHL1,
+              "attn_reg: unknown prior kind %d (0 none, 1 kl, 2 mse, 3 smoothl1)", prior_kind);
+  TBN_REQUIRE(prior_reduction >= TBN_ATTN_RED_SUM && prior_reduction <= TBN_ATTN_RED_BATCHMEAN,
+              "attn_reg: unknown prior reduction %d (0 sum, 1 mean, 2 batchmean)", prior_reduction);
+  TBN_REQUIRE(!prior_kind || (prior && prior_ld >= t), "attn_reg: prior kind %d needs prior with prior_ld >= t (prior_ld = %d, "
+              "t = %d)", prior_kind, prior_ld, t);
+  TBN_REQUIRE(prior_kind <= TBN_ATTN_PRIOR_KL || prior_reduction != TBN_ATTN_RED_BATCHMEAN,
+              "attn_reg: batchmean is a reduction of the kl prior only (prior kind %d)", prior_kind);
+  TBN_REQUIRE(!log_rebind || prior_kind == TBN_ATTN_PRIOR_KL, "attn_reg: log_rebind needs the kl prior (prior kind %d)",
+              prior_kind);
+  a->prior_kind = prior_kind;
+  a->prior_red = prior_reduction;
+  a->use_contrast = use_contrast != 0;
+  a->use_entropy = use_entropy != 0;
+  a->training = training != 0;
+  a->log_rebind = log_rebind != 0;
+  a->contrast_thresh = contrast_thresh;
+  a->prior_mult = prior_mult;
+  a->contrast_mult = contrast_mult;
+  a->entropy_mult = entropy_mult;
+  a->entropy_thresh = entropy_thresh;
+  return TBN_OK;
+}
+
+int tbn_attn_reg_fwd(const float* w, int w_ld, const float* prior, int prior_ld, int r, int t, int prior_kind,
+                     int prior_reduction, int use_contrast, float contrast_thresh, int use_entropy, float prior_mult,
+                     float contrast_mult, float entropy_mult, int training, float entropy_thresh, int log_rebind,
+                     float* rowterms, float* losses, void* stream) {
+  AttnReg a;
+  TBN_REQUIRE(rowterms && losses, "attn_reg: null argument (rowterms or losses)");
+  const int rc = attn_reg_args(w, w_ld, prior, prior_ld, r, t, prior_kind, prior_reduction, use_contrast, contrast_thresh,
+                               use_entropy, prior_mult, contrast_mult, entropy_mult, training, entropy_thresh, log_rebind, &a);
+  if (rc != TBN_OK) return rc;
+  TBN_KLAUNCH(attn_reg_rows_kernel, dim3(r), dim3(64), 0, (hipStream_t)stream, w, w_ld, prior, prior_ld, r, t, a, rowterms);
+  TBN_CHECK_LAUNCH("attn_reg_rows");
+  TBN_KLAUNCH(attn_reg_mean_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, rowterms, r, t, a, losses);
+  TBN_CHECK_LAUNCH("attn_reg_mean");
+  return TBN_OK;
+}
+
+int tbn_attn_reg_bwd(const float* up, const float* w, int w_ld, const float* prior, int prior_ld, const float* losses, int r,
+                     int t, int prior_kind, int prior_reduction, int use_contrast, float contrast_thresh, int use_entropy,
+                     float prior_mult, float contrast_mult, float entropy_mult, int training, float entropy_thresh,
+                     int log_rebind, float* dw, int dw_ld, void* stream) {
+  AttnReg a;
+  TBN_REQUIRE(up && losses && dw, "attn_reg: null argument (up, losses or dw)");
+  const int rc = attn_reg_args(w, w_ld, prior, prior_ld, r, t, prior_kind, prior_reduction, use_contrast, contrast_thresh,
+                               use_entropy, prior_mult, contrast_mult, entropy_mult, training, entropy_thresh, log_rebind, &a);
+  if (rc != TBN_OK) return rc;
+  TBN_REQUIRE(dw_ld >= t, "attn_reg: dw_ld = %d is smaller than t = %d", dw_ld, t);
+  TBN_KLAUNCH(attn_reg_bwd_kernel, dim3(r), dim3(64), 0, (hipStream_t)stream, up, w, w_ld, prior, prior_ld, losses, r, t, a, dw,
+              dw_ld);
+  TBN_CHECK_LAUNCH("attn_reg_bwd");
   return TBN_OK;
 }
 

@@ -512,6 +512,77 @@ def cross_entropy_heads(scores, heads, labels):
     return _CeHeadsFn.apply(scores, tuple(heads), *labels)
 
 
+_PRIOR_KINDS = {None: 0, "kl": 1, "mse": 2, "smoothl1": 3}
+_PRIOR_REDUCTIONS = {"sum": 0, "mean": 1, "batchmean": 2}
+
+
+class _AttnRegFn(torch.autograd.Function):
+    """prior / contrast / entropy losses of the attention weights and their weighted total -> 4 scalar losses, one
+    launch pair forward and one launch backward (tbn_attn_reg_fwd / _bwd)  [reference model.py:299-332,
+    contrast_loss.py:4-25]"""
+
+    @staticmethod
+    def forward(ctx, w, prior, sw):
+        _need_cuda(w, "attn_regularisers")
+        if w.dim() != 2 or w.dtype != torch.float32:
+            raise TbnHipError(f"attn_regularisers: weights must be a float32 (r, t) matrix, got {w.dtype} "
+                              f"{tuple(w.shape)}")
+        w = _rows(w)
+        R, T = w.shape
+        if prior is not None:
+            _need_cuda(prior, "attn_regularisers")
+            if tuple(prior.shape) != (R, T):
+                raise TbnHipError(f"attn_regularisers: prior {tuple(prior.shape)} does not match weights {(R, T)}")
+            prior = _rows(prior)
+        rowterms = torch.empty(3 * R, device=w.device, dtype=torch.float32)
+        losses = torch.empty(4, device=w.device, dtype=torch.float32)
+        call("tbn_attn_reg_fwd", ptr(w), _ld(w), ptr(prior), _ld(prior) if prior is not None else 0, R, T, *sw,
+             ptr(rowterms), ptr(losses), stream_ptr())
+        ctx.sw = sw
+        ctx.set_materialize_grads(False)      # an output nobody differentiates arrives as None, not as a zero-filled tensor
+        ctx.save_for_backward(w, prior, losses)
+        return tuple(losses[i] for i in range(4))
+
+    @staticmethod
+    def backward(ctx, *grads):
+        w, prior, losses = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        R, T = w.shape
+        if all(g is not None for g in grads):
+            up = torch.stack(grads).float()
+        else:
+            # the train step differentiates `total` alone: one fill and one copy, not a zero tensor per missing gradient
+            up = torch.zeros(4, device=w.device, dtype=torch.float32)
+            for i, g in enumerate(grads):
+                if g is not None:
+                    up[i].copy_(g)
+        dw = torch.empty(R, T, device=w.device, dtype=torch.float32)
+        call("tbn_attn_reg_bwd", ptr(up), ptr(w), _ld(w), ptr(prior), _ld(prior) if prior is not None else 0, ptr(losses),
+             R, T, *ctx.sw, ptr(dw), T, stream_ptr())
+        return dw, None, None
+
+
+def attn_regularisers(w, prior=None, *, prior_kind=None, prior_reduction="batchmean", contrast_thresh=0.1,
+                      use_contrast=False, use_entropy=False, mults=(0.0, 0.0, 0.0), training=False, entropy_thresh=0.0,
+                      log_rebind=False):
+    """The loss terms that train the attention weights w (r, t) -> (prior, contrast, entropy, total), 0-dim views of one
+    4-float tensor; a term that is off is None.  prior_kind None / "kl" / "mse" / "smoothl1" against `prior` (r, t) with
+    prior_reduction "sum" / "mean" / "batchmean" (kl: nn.KLDivLoss on log(w + 1e-7)); ContrastLoss(contrast_thresh) with
+    reduction mean; Categorical(probs=w + 1e-6).entropy().mean(); total = mults . (prior, contrast, entropy) with the
+    entropy multiplier switched off on the device when training and entropy < entropy_thresh.  log_rebind (kl only)
+    evaluates contrast and entropy on log(w + 1e-7), as reference model.py:316-324 does after rebinding `wts`.  w and
+    prior may be row-pitched.  `prior` gets no gradient."""
+    if prior_kind not in _PRIOR_KINDS or prior_reduction not in _PRIOR_REDUCTIONS:
+        raise TbnHipError(f"attn_regularisers: unknown prior kind {prior_kind!r} or reduction {prior_reduction!r}")
+    kind = _PRIOR_KINDS[prior_kind]
+    pm, cm, em = (float(m) for m in mults)
+    sw = (kind, _PRIOR_REDUCTIONS[prior_reduction], int(bool(use_contrast)), float(contrast_thresh), int(bool(use_entropy)),
+          pm, cm, em, int(bool(training)), float(entropy_thresh), int(bool(log_rebind)))
+    out = _AttnRegFn.apply(w, prior if kind else None, sw)
+    return (out[0] if kind else None, out[1] if use_contrast else None, out[2] if use_entropy else None, out[3])
+
+
 def dropout_mask(shape, p, training, device):
     if not training or p <= 0:
         return None

@@ -44,6 +44,8 @@ int tbn_version(void);
 /* bit 4: the general attention core (tbn_mha_fwd / tbn_mha_bwd: any number of queries, up to 1024 keys, any head_dim) and
  * the attention-weight softmax (tbn_attn_weights_fwd / tbn_attn_weights_bwd) */
 #define TBN_CAP_ATTN_GENERAL 8
+/* bit 5: the attention-weight regularisers (tbn_attn_reg_fwd / tbn_attn_reg_bwd: prior, contrast and entropy losses) */
+#define TBN_CAP_ATTN_REG 16
 int tbn_capabilities(void);
 const char* tbn_last_error(void);
 
@@ -486,6 +488,47 @@ int tbn_attn_weights_fwd(const float* logits, int logits_ld, const float* noise,
                          float* soft, float* w, int r, int k, int t, void* stream);
 int tbn_attn_weights_bwd(const float* dw, const float* soft, const float* protos, float tau, float* dlogits, int r, int k,
                          int t, void* stream);
+/* The three loss terms that train the attention weights (reference core/models/model.py:299-332 and
+ * core/models/contrast_loss.py:4-25: the prior criterion, ContrastLoss and the Categorical entropy with its threshold
+ * switch-off) over w (r,t) with leading dimension w_ld and prior (r,t) with leading dimension prior_ld.
+ *   prior term, prior_kind TBN_ATTN_PRIOR_*: NONE: off.  KL: p > 0 ? p * (log p - log(w + 1e-7)) : 0 (nn.KLDivLoss,
+ *     log_target False, on log(w + 1e-7)).  MSE: (w - p)^2.  SMOOTHL1 (beta 1): |d| < 1 ? 0.5 d^2 : |d| - 0.5, d = w - p.
+ *     prior_reduction TBN_ATTN_RED_*: SUM, MEAN (/ (r*t)) or BATCHMEAN (/ r, KL only: MSE / SMOOTHL1 with it are refused, as
+ *     torch refuses them).
+ *   contrast term (use_contrast): row term sum_t (x >= contrast_thresh ? -x : x), compared in fp32; the loss is the mean
+ *     over rows (ContrastLoss with reduction mean or batchmean; its unreduced "sum" vector is not covered).
+ *   entropy term (use_entropy): q = x + 1e-6, p = q / sum_t q, row term -sum_t p * log(clamp(p, eps, 1 - eps)) with
+ *     eps = FLT_EPSILON (torch.distributions.Categorical(probs=q).entropy()); the loss is the mean over rows.
+ *   x = w.  With log_rebind != 0 (KL only) x = log(w + 1e-7) instead: model.py:316-317 rebinds `wts` to the logarithm for
+ *     the kl prior and :320-324 hand that tensor to the contrast and entropy terms; the gradient is chained through
+ *     dx/dw = 1 / (w + 1e-7).
+ *   total = prior_mult * prior + contrast_mult * contrast + e * entropy, e = entropy_mult except e = 0 when
+ *     training && entropy_mult > 0 && entropy < entropy_thresh -- decided on the device, no host read.
+ * tbn_attn_reg_fwd writes losses[4] = {prior, contrast, entropy, total} (device; a term that is off is 0) and rowterms
+ * (scratch, 3*r floats: the row terms, then summed in a fixed order by one wave).  tbn_attn_reg_bwd is ONE launch: it
+ * recomputes the row sums, reads the saved losses[2] to repeat the switch-off decision and the four upstream gradients
+ * up[4] = d/d{prior, contrast, entropy, total} from device memory, and writes
+ *   dw = (up[0] + up[3]*prior_mult) * dPrior + (up[1] + up[3]*contrast_mult) * dContrast + (up[2] + up[3]*e) * dEntropy,
+ * dEntropy through the normalisation (dH/dq_j = -(log p_j + H_row) / sum q inside the clamp, the clamp's zero-gradient
+ * region honoured), rows scaled by 1/r.  One wave per row, lanes stride over t (any t >= 1); no atomics: the same input
+ * gives the same bits.  A NULL pointer (prior may be NULL with TBN_ATTN_PRIOR_NONE), r < 1, t < 1, a leading dimension
+ * < t, an unknown kind or reduction, a prior kind without prior, MSE / SMOOTHL1 with BATCHMEAN or log_rebind without KL
+ * returns TBN_ERR_ARG with a message naming attn_reg before any launch. */
+#define TBN_ATTN_PRIOR_NONE 0
+#define TBN_ATTN_PRIOR_KL 1
+#define TBN_ATTN_PRIOR_MSE 2
+#define TBN_ATTN_PRIOR_SMOOTHL1 3
+#define TBN_ATTN_RED_SUM 0
+#define TBN_ATTN_RED_MEAN 1
+#define TBN_ATTN_RED_BATCHMEAN 2
+int tbn_attn_reg_fwd(const float* w, int w_ld, const float* prior, int prior_ld, int r, int t, int prior_kind,
+                     int prior_reduction, int use_contrast, float contrast_thresh, int use_entropy, float prior_mult,
+                     float contrast_mult, float entropy_mult, int training, float entropy_thresh, int log_rebind,
+                     float* rowterms, float* losses, void* stream);
+int tbn_attn_reg_bwd(const float* up, const float* w, int w_ld, const float* prior, int prior_ld, const float* losses, int r,
+                     int t, int prior_kind, int prior_reduction, int use_contrast, float contrast_thresh, int use_entropy,
+                     float prior_mult, float contrast_mult, float entropy_mult, int training, float entropy_thresh,
+                     int log_rebind, float* dw, int dw_ld, void* stream);
 /* fixed attention (model.py:224-228): out[r][c] = sum_t feat[r][t][c] * w[r][t] */
 int tbn_weighted_sum_fwd(const float* feat, const float* w, float* out, int out_ld, int r, int t, int c, void* stream);
 int tbn_weighted_sum_bwd(const float* dout, int dout_ld, const float* w, float* dfeat, int r, int t, int c,
