@@ -487,23 +487,26 @@ static int desc_to_convp(const tbn_conv_desc* d, float* workspace, hipStream_t s
   return TBN_OK;
 }
 
+// a weight tensor [cout][ksize][ksize][cin] a split-bf16 kernel can read (the shape rule at the layer's stride 1 and
+// same-size padding) and a plane count
+static bool planes_args_ok(int cout, int ksize, int cin, int np) {
+  return cout > 0 && cin > 0 && bf16x_layer_kind(ksize, 1, ksize / 2, cin) != BF16X_LAYER_NONE && (np == 6 || np == 3);
+}
+
 size_t tbn_conv_weight_planes_bytes(int cout, int ksize, int cin, int np) {
-  if (cout <= 0 || ksize <= 0 || cin <= 0 || cin % 32 != 0 || (np != 6 && np != 3)) return 0;
+  if (!planes_args_ok(cout, ksize, cin, np)) return 0;
   return tbn_bf16x_planes_bytes((size_t)cout * ksize * ksize * cin, np);
 }
 
 int tbn_conv_split_weights(const float* weight, int cout, int ksize, int cin, int np, void* planes, void* stream) {
   TBN_REQUIRE(weight && planes, "conv_split_weights: null pointer");
-  TBN_REQUIRE(cout > 0 && ksize > 0 && cin > 0 && cin % 32 == 0 && (np == 6 || np == 3),
-              "conv_split_weights: bf16x weight planes need cin a multiple of 32 and np 6 | 3 (got cin %d, np %d)", cin, np);
+  TBN_REQUIRE(planes_args_ok(cout, ksize, cin, np),
+              "conv_split_weights: bf16x weight planes need ksize 1 | 3, cin a multiple of 32 and np 6 | 3 (got ksize %d, cin %d, np %d)",
+              ksize, cin, np);
   TBN_REQUIRE((((uintptr_t)weight | (uintptr_t)planes) & 15) == 0, "conv_split_weights: pointers must be 16-B aligned");
   static thread_local SplitTab tab;
-  tab.n = 1;
-  tab.w_off[0] = 0;
-  tab.p_off[0] = 0;
-  tab.floats[0] = (size_t)cout * ksize * ksize * cin;
-  tab.blk0[0] = 0;
-  tab.blk0[1] = (int)((tab.floats[0] + 1023) / 1024);
+  tab.n = 0;
+  split_tab_push(tab, 0, 0, (size_t)cout * ksize * ksize * cin);
   return tbn_launch_bf16x_split(weight, planes, tab, np, (hipStream_t)stream);
 }
 

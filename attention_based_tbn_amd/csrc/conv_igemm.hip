@@ -56,11 +56,8 @@ __device__ __forceinline__ void conv_igemm_body(const ConvP& p, const int bid, f
   constexpr int TILE_F = (BM + BN) * LDT;  // floats per LDS stage (A rows then B rows)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // XCD-aware bijective remap: blocks b, b+8, ... share an XCD -> give them consecutive tiles
-  const int nb = p.tiles_m * p.tiles_n;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, idx = bid >> 3;
-  const int nid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-  const int tm = nid / p.tiles_n, tn = nid - tm * p.tiles_n;
+  int tm, tn;
+  xcd_tile(bid, p.tiles_m, p.tiles_n, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
 
   // descriptors are built from kernel arguments only (wave-uniform): loads need no branches, an
@@ -317,10 +314,8 @@ __device__ __forceinline__ void conv_halo_body(const ConvP& p, const int bid, fl
   constexpr int BM = 128 * MT, BN = 32 * NT;
   constexpr int NJ = (BM + 2 * 64 + 2 + 31) / 32;   // float4 slots per thread for a halo of up to W = 64
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nb = p.tiles_m * p.tiles_n;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, idx = bid >> 3;
-  const int nid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-  const int tm = nid / p.tiles_n, tn = nid - tm * p.tiles_n;
+  int tm, tn;
+  xcd_tile(bid, p.tiles_m, p.tiles_n, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
   const int W = p.W, HR = BM + 2 * W + 2;   // halo rows; row HR is the zero row
   float* As = lds;
@@ -551,10 +546,8 @@ __device__ __forceinline__ void conv_dma_body(const ConvP& p, const int bid, flo
   constexpr int AR = 4 * MT;                 // 8-row DMA instructions per wave for the A tile
   constexpr int TILE_B = (BM + BN) * 128;    // bytes per LDS stage (A rows then B rows, 128 B each)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nb = p.tiles_m * p.tiles_n;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, idx = bid >> 3;
-  const int nid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-  const int tm = nid / p.tiles_n, tn = nid - tm * p.tiles_n;
+  int tm, tn;
+  xcd_tile(bid, p.tiles_m, p.tiles_n, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
   const i32x4 in_rsrc = make_rsrc(p.in, p.in_bytes);
   const i32x4 wt_rsrc = make_rsrc(p.wt, p.wt_bytes);
@@ -745,10 +738,8 @@ __device__ __forceinline__ void conv_sk4_body(const ConvP& p, const int bid, flo
   constexpr int TILE_F = (BM + BN) * LDT;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nb = p.tiles_m * p.tiles_n;
-  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, idx = bid >> 3;
-  const int nid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-  const int tm = nid / p.tiles_n, tn = nid - tm * p.tiles_n;
+  int tm, tn;
+  xcd_tile(bid, p.tiles_m, p.tiles_n, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
   const i32x4 in_rsrc = make_rsrc(p.in, p.in_bytes);
   const i32x4 wt_rsrc = make_rsrc(p.wt, p.wt_bytes);
@@ -962,12 +953,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
   // block -> (split, tap, tile_ci, tile_co), split slowest.  All tiles x taps of one split re-read the same
   // dy / x row slab, so the XCD-aware bijective remap (blocks b, b+8, ... share an XCD and its L2) hands each
   // XCD a CONTIGUOUS run of logical ids: a slab is then fetched into one L2 instead of all eight.
-  int b;
-  {
-    const int nb = gridDim.x, bid = blockIdx.x;
-    const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, idx = bid >> 3;
-    b = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-  }
+  int b = xcd_remap(blockIdx.x, gridDim.x);
   const int tco = b % p.tiles_co;
   b /= p.tiles_co;
   const int tci = b % p.tiles_ci;
@@ -1252,19 +1238,6 @@ static int with_epilogue(EpiSel e, F&& f) {
   tbn_set_error("conv: epilogue %d%s is not built for this kernel family", e.epi, e.red ? " + reduce" : "");
   return TBN_ERR_UNSUPPORTED;
 }
-// f(integral_constant<int, MT>, integral_constant<int, NT>) for the tile (mt, nt) of a family that admits 1..MAXM x 1..MAXN;
-// any other tile is refused (I walks the admitted tiles in row order)
-template <int MAXM, int MAXN, int I = 0, class F>
-static int with_tile(int mt, int nt, F&& f) {
-  if constexpr (I == MAXM * MAXN) {
-    tbn_set_error("conv: unsupported tile %dx%d", mt, nt);
-    return TBN_ERR_UNSUPPORTED;
-  } else {
-    constexpr int MT = I / MAXN + 1, NT = I % MAXN + 1;
-    if (mt == MT && nt == NT) return f(std::integral_constant<int, MT>{}, std::integral_constant<int, NT>{});
-    return with_tile<MAXM, MAXN, I + 1>(mt, nt, f);
-  }
-}
 // the instantiation's name as the profiler reports it: kernel<mt, nt, [rowmode, ]epi[, stages][, true]>
 static void conv_kernel_name(char (&nm)[64], const char* kernel, int mt, int nt, const char* rowmode, EpiSel e, int stages) {
   char stg[8] = "";
@@ -1514,24 +1487,18 @@ static int conv_prepare(ConvP& p, int rowmode, int* single) {
 
 int tbn_launch_conv(ConvP p, int rowmode, int mt, int nt, hipStream_t st, const RiderP* rider) {
   if (p.flags & CONV_FLAG_BF16X_PLANES) {   // refused here, in bf16x terms, before the generic checks see the launch
-    if ((p.flags & (CONV_FLAG_BF16X6 | CONV_FLAG_BF16X3)) == 0) {
-      tbn_set_error("conv: flag 128 (pre-split bf16x weight planes) is only valid with a bf16x math flag (32 / 64)");
-      return TBN_ERR_ARG;
-    }
-    if (rowmode || p.Cin % 32 != 0 || p.stride != 1) {
-      tbn_set_error("conv: the bf16x kernels on weight planes (flag 128) need stride 1 and cin a multiple of 32 (got stride %d, cin %d)",
-                    p.stride, p.Cin);
-      return TBN_ERR_UNSUPPORTED;
-    }
+    TBN_REQUIRE((p.flags & (CONV_FLAG_BF16X6 | CONV_FLAG_BF16X3)) != 0,
+                "conv: flag 128 (pre-split bf16x weight planes) is only valid with a bf16x math flag (32 / 64)");
+    TBN_REQUIRE_OR(TBN_ERR_UNSUPPORTED, !rowmode && bf16x_gemm_ok(p.stride, p.Cin),
+                   "conv: the bf16x kernels on weight planes (flag 128) need stride 1 and cin a multiple of 32 (got stride %d, cin %d)",
+                   p.stride, p.Cin);
   }
   int single = 0;
   const int prc = conv_prepare(p, rowmode, &single);
   if (prc != TBN_OK) return prc;
   if (single) return launch_conv_tiles(p, rowmode, mt, nt, st, rider);
-  if (p.flags & (CONV_FLAG_BF16X6 | CONV_FLAG_BF16X3 | CONV_FLAG_BF16X_PLANES)) {
-    tbn_set_error("conv: the bf16x kernels (flags 32 / 64) do not compute strided data gradients");
-    return TBN_ERR_UNSUPPORTED;
-  }
+  TBN_REQUIRE_OR(TBN_ERR_UNSUPPORTED, (p.flags & (CONV_FLAG_BF16X6 | CONV_FLAG_BF16X3 | CONV_FLAG_BF16X_PLANES)) == 0,
+                 "conv: the bf16x kernels (flags 32 / 64) do not compute strided data gradients");
   TBN_REQUIRE(!rowmode && p.stride == 1 && p.R == p.S && p.R * p.S <= 9, "conv: unsupported strided data gradient");
   const double flops_total = p.alg_flops;
   const int full_M = p.N * p.OH * p.OW;

@@ -1289,21 +1289,17 @@ struct SideJoin {
 
 extern "C" {
 
-// bf16 weight planes of the backbone (TBN_BACKBONE_CONV_BF16X_ALL): every GEMM with k in {1, 3}, stride 1 and cin a multiple
-// of 32 owns a run of records (conv_bf16x.hip) in plan order; off[i] = byte offset of conv i's records, -1 = none
-// The predicate looks at the layer only, not at the map it runs on, on purpose: the layout is then a function of the graph
-// and np alone, so ONE plane buffer serves every plan of a backbone (any frame count and input size; the Python host keeps
-// one per module).  The price: a conv2_3x3 on a map wider than 64 stays on the fp32 kernel and its planes (110592 weights,
-// 0.65 MB of ~40 MB at np 6) are written and never read.
-static bool planes_conv(const Conv& c) {
-  return !c.stem && c.stride == 1 && c.cin % 32 == 0 && ((c.k == 1 && c.pad == 0) || (c.k == 3 && c.pad == 1));
-}
+// bf16 weight planes of the backbone (TBN_BACKBONE_CONV_BF16X_ALL): every GEMM the shape rule (tbn_kernels.h) gives to a
+// split-bf16 kernel owns a run of records (conv_bf16x.hip) in plan order; off[i] = byte offset of conv i's records,
+// -1 = none.  The map width is not asked (see bf16x_3x3_map_ok): a conv2_3x3 on a map wider than 64 stays on the fp32
+// kernel and its planes (110592 weights, 0.65 MB of ~40 MB at np 6) are written and never read.
+static Bf16xLayer conv_bf16x_layer(const Conv& c) { return c.stem ? BF16X_LAYER_NONE : bf16x_layer_kind(c.k, c.stride, c.pad, c.cin); }
 static size_t planes_layout(const tbn_backbone_plan* P, int np, std::vector<long long>* off) {
   size_t total = 0;
   if (off) off->assign(P->convs.size(), -1);
   for (size_t i = 0; i < P->convs.size(); ++i) {
     const Conv& c = P->convs[i];
-    if (!planes_conv(c)) continue;
+    if (conv_bf16x_layer(c) == BF16X_LAYER_NONE) continue;
     if (off) (*off)[i] = (long long)total;
     total += tbn_bf16x_planes_bytes((size_t)c.cout * c.k * c.k * c.cin, np);
   }
@@ -1323,16 +1319,11 @@ int tbn_backbone_split_weights(const tbn_backbone_plan* P, const float* weight, 
   planes_layout(P, np, &off);
   static thread_local SplitTab tab;
   tab.n = 0;
-  tab.blk0[0] = 0;
   for (size_t i = 0; i < P->convs.size(); ++i) {
     if (off[i] < 0) continue;
     const Conv& c = P->convs[i];
-    TBN_REQUIRE(tab.n < 64, "backbone_split_weights: more than 64 weight tensors");
-    tab.w_off[tab.n] = c.w_off;
-    tab.p_off[tab.n] = (size_t)off[i];
-    tab.floats[tab.n] = (size_t)c.cout * c.k * c.k * c.cin;
-    tab.blk0[tab.n + 1] = tab.blk0[tab.n] + (int)((tab.floats[tab.n] + 1023) / 1024);
-    ++tab.n;
+    TBN_REQUIRE(split_tab_push(tab, c.w_off, (size_t)off[i], (size_t)c.cout * c.k * c.k * c.cin),
+                "backbone_split_weights: more than 64 weight tensors");
   }
   return tbn_launch_bf16x_split(weight, planes, tab, np, (hipStream_t)stream);
 }
@@ -1399,14 +1390,12 @@ int tbn_backbone_forward(const tbn_backbone_plan* P, int training, const float* 
                                   : ((prm->flags & TBN_BACKBONE_CONV_BF16X6) ? CONV_FLAG_BF16X6
                                                                              : ((prm->flags & TBN_BACKBONE_CONV_BF16X3) ? CONV_FLAG_BF16X3 : 0));
   auto bf16x_layer = [&](const Conv& c) {
-    return bf16x_flag != 0 && !c.stem && c.k == 3 && c.stride == 1 && c.pad == 1 && c.inW <= 64 && c.cin % 32 == 0;
+    return bf16x_flag != 0 && conv_bf16x_layer(c) == BF16X_LAYER_3X3 && bf16x_3x3_map_ok(c.inW);
   };
   // TBN_BACKBONE_CONV_BF16X_ALL: those layers read their weight tiles from the caller's pre-split planes, and every
   // 1x1 / stride 1 GEMM (merged sibling groups with a pooled part included) goes through the pointwise split-bf16 kernel
   // with that kernel's size heuristic -- the plan holds no tile for it
-  auto bf16x_pw_layer = [&](const Conv& c) {
-    return bf16x_all && !c.stem && c.k == 1 && c.stride == 1 && c.pad == 0 && c.cin % 32 == 0;
-  };
+  auto bf16x_pw_layer = [&](const Conv& c) { return bf16x_all && conv_bf16x_layer(c) == BF16X_LAYER_PW; };
   std::vector<long long> planes_off;
   if (bf16x_all) planes_layout(P, (bf16x_flag & CONV_FLAG_BF16X6) ? 6 : 3, &planes_off);
   const hipStream_t st_main = st;

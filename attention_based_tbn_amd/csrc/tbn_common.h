@@ -13,13 +13,15 @@
 // thread-local last-error string (tbn_last_error() in the C-ABI)
 void tbn_set_error(const char* fmt, ...);
 
-#define TBN_REQUIRE(cond, ...)                   \
+// refuses with `code` and a message unless `cond` holds; TBN_REQUIRE: the caller's arguments are wrong (TBN_ERR_ARG)
+#define TBN_REQUIRE_OR(code, cond, ...)          \
   do {                                           \
     if (!(cond)) {                               \
       tbn_set_error(__VA_ARGS__);                \
-      return TBN_ERR_ARG;                        \
+      return code;                               \
     }                                            \
   } while (0)
+#define TBN_REQUIRE(cond, ...) TBN_REQUIRE_OR(TBN_ERR_ARG, cond, __VA_ARGS__)
 
 #define TBN_CHECK_LAUNCH(what)                                                     \
   do {                                                                             \

@@ -1,5 +1,5 @@
 // Device code shared by the convolution kernels (conv_igemm.hip, conv_bf16x.hip): hardware-bounds-checked buffer
-// loads / stores and the epilogue of a finished accumulator tile.
+// loads / stores, the XCD tile map and the epilogue of a finished accumulator tile.
 #pragma once
 #include "tbn_common.h"
 #include "tbn_kernels.h"
@@ -39,6 +39,19 @@ __device__ float tbn_llvm_buffer_load_f32(i32x4 srsrc, int voffset, int soffset,
 __device__ __forceinline__ float4 buf_load4(i32x4 r, unsigned voff, unsigned soff = 0u) {
   const f32x4 v = tbn_llvm_buffer_load_f32x4(r, (int)voff, (int)soff, 0);
   return make_float4(v.x, v.y, v.z, v.w);
+}
+
+// XCD-aware bijective remap of a 1-D grid of `nb` workgroups: blocks b, b + 8, ... share an XCD (and its L2) -> they get
+// consecutive logical ids, so each XCD owns one contiguous run of the ids
+__device__ __forceinline__ int xcd_remap(const int bid, const int nb) {
+  const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, idx = bid >> 3;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+}
+// ... for the tiles_m x tiles_n output tiles of a conv GEMM, N fastest: the tiles of an activation row panel share an XCD
+__device__ __forceinline__ void xcd_tile(const int bid, const int tiles_m, const int tiles_n, int& tm, int& tn) {
+  const int nid = xcd_remap(bid, tiles_m * tiles_n);
+  tm = nid / tiles_n;
+  tn = nid - tm * tiles_n;
 }
 
 // ---------------------------------------------------------------- epilogue (shared by the GEMM bodies)

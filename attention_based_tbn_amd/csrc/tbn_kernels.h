@@ -2,6 +2,7 @@
 #pragma once
 #include "tbn_common.h"
 #include <hip/hip_ext.h>
+#include <type_traits>
 
 enum { CONV_EPI_PLAIN = 0, CONV_EPI_STATS = 1, CONV_EPI_EVAL = 2 };
 enum {
@@ -164,14 +165,40 @@ int tbn_launch_conv(ConvP p, int rowmode, int mt, int nt, hipStream_t st, const 
 int tbn_launch_conv_pair(ConvP a, ConvP b, int variant, int mt, int nt, hipStream_t st, const RiderP* rider = nullptr);
 int tbn_conv_red_rows(int N, int OH, int OW, int up, int tile_rows);   // tile_rows = M rows per workgroup tile (128 * mt; 32 * mt for the split-K tile kernel)
 size_t tbn_conv_halo_lds_bytes(const ConvP& p, int mt, int nt);   // 0: shape not handled by the LDS-halo kernel
-// conv_bf16x.hip: 3x3 / stride 1 / pad 1 forward on the bf16 MFMA (np = 6 | 3 plane products); tbn_launch_conv routes a
-// launch whose flags carry CONV_FLAG_BF16X6 / _BF16X3 there and refuses what that kernel does not cover
-size_t tbn_conv_bf16x_lds_bytes(const ConvP& p, int np, int mt, int nt);   // 0: shape not handled
-void tbn_conv_bf16x_pick_tile(int M, int Cout, int K, int np, int* mt, int* nt);
+// f(integral_constant<int, MT>, integral_constant<int, NT>) for the tile (mt, nt) of a kernel family that admits
+// 1..MAXM x 1..MAXN; any other tile is refused (I walks the admitted tiles in row order)
+template <int MAXM, int MAXN, int I = 0, class F>
+static int with_tile(int mt, int nt, F&& f) {
+  if constexpr (I == MAXM * MAXN) {
+    tbn_set_error("conv: unsupported tile %dx%d", mt, nt);
+    return TBN_ERR_UNSUPPORTED;
+  } else {
+    constexpr int MT = I / MAXN + 1, NT = I % MAXN + 1;
+    if (mt == MT && nt == NT) return f(std::integral_constant<int, MT>{}, std::integral_constant<int, NT>{});
+    return with_tile<MAXM, MAXN, I + 1>(mt, nt, f);
+  }
+}
+
+// conv_bf16x.hip: eval-forward convolutions on the bf16 MFMA (np = 6 | 3 plane products); tbn_launch_conv routes a launch
+// whose flags carry CONV_FLAG_BF16X6 / _BF16X3 there and refuses what those kernels do not cover.
+// THE SHAPE RULE -- which layer runs on which split-bf16 kernel, a function of the layer alone.  Everything that has to
+// agree on it reads it here: the launcher's classifier (conv_bf16x.hip), the pre-check of tbn_launch_conv, the engine's
+// routing and plane layout (engine.hip) and the one-tensor plane size / split of the C-ABI (api.hip).
+enum Bf16xLayer { BF16X_LAYER_NONE = 0, BF16X_LAYER_3X3, BF16X_LAYER_PW };
+// what every split-bf16 GEMM needs: unit stride and whole 32-channel K chunks (one plane record each)
+static inline bool bf16x_gemm_ok(int stride, int cin) { return stride == 1 && cin % 32 == 0; }
+static inline Bf16xLayer bf16x_layer_kind(int k, int stride, int pad, int cin) {
+  if (!bf16x_gemm_ok(stride, cin)) return BF16X_LAYER_NONE;
+  if (k == 3 && pad == 1) return BF16X_LAYER_3X3;
+  if (k == 1 && pad == 0) return BF16X_LAYER_PW;   // on pre-split weight planes only (CONV_FLAG_BF16X_PLANES)
+  return BF16X_LAYER_NONE;
+}
+// The 3x3 kernel stages the halo of its tile in a fixed number of register slots: the MAP it runs on is at most 64 wide
+// (the pointwise kernel has no such limit).  Deliberately NOT part of the rule above: the weight-plane layout asks the rule
+// alone, so it is a function of the graph and np, and ONE plane buffer serves every plan of a backbone (any frame count and
+// input size).  The price: a 3x3 layer on a wider map stays on the fp32 kernel and its planes are written and never read.
+static inline bool bf16x_3x3_map_ok(int W) { return W <= 64; }
 int tbn_launch_conv_bf16x(ConvP& p, int rowmode, int mt, int nt, double alg_bytes, hipStream_t st, const RiderP* rider);
-// with CONV_FLAG_BF16X_PLANES: the pointwise (1x1 / stride 1 / pad 0) kernel on weight planes
-size_t tbn_conv_bf16x_pw_lds_bytes(const ConvP& p, int np, int mt, int nt);   // 0: shape not handled
-void tbn_conv_bf16x_pw_pick_tile(int M, int Cout, int K, int np, int* mt, int* nt);
 // weight planes (layout: include/tbn_hip.h): up to 64 weight tensors of one flat fp32 array split in ONE launch
 struct SplitTab {
   int n;
@@ -180,6 +207,17 @@ struct SplitTab {
   size_t floats[64];   // cout * taps * cin (cin a multiple of 32)
   int blk0[65];        // first workgroup of each tensor (1024 floats per workgroup); blk0[n] = grid size
 };
+// appends a tensor to `tab` (tab.n = 0: an empty table); false: the table is full
+static inline bool split_tab_push(SplitTab& tab, size_t w_off, size_t p_off, size_t floats) {
+  if (tab.n >= 64) return false;
+  if (tab.n == 0) tab.blk0[0] = 0;
+  tab.w_off[tab.n] = w_off;
+  tab.p_off[tab.n] = p_off;
+  tab.floats[tab.n] = floats;
+  tab.blk0[tab.n + 1] = tab.blk0[tab.n] + (int)((floats + 1023) / 1024);
+  ++tab.n;
+  return true;
+}
 size_t tbn_bf16x_planes_bytes(size_t floats, int np);
 int tbn_launch_bf16x_split(const float* w, void* planes, const SplitTab& tab, int np, hipStream_t st);
 void tbn_wgrad_plan(int M, int Cout, int Cin, int taps, int* mt, int* nt, int* splits, int* rows_per_split);

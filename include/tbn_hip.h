@@ -289,7 +289,8 @@ int tbn_conv2d_fwd(const float* in, int in_ld, const float* weight, const float*
                    int n, int h, int w, int cin, int cout, int ksize, int stride, int pad, int epilogue, int flags,
                    const float* scale, const float* shift, float* stat_partial, void* stream);
 int tbn_conv2d_stat_tiles(int n, int h, int w, int cin, int cout, int ksize, int stride, int pad);
-/* bf16 weight planes of ONE conv weight tensor [cout][ksize][ksize][cin] (cin a multiple of 32) for conv flag 128; np = 6
+/* bf16 weight planes of ONE conv weight tensor [cout][ksize][ksize][cin] (ksize 1 or 3 -- the layers the split-bf16 kernels
+ * take -- and cin a multiple of 32) for conv flag 128; np = 6
  * writes three planes (bf16x6), np = 3 two (bf16x3):  hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid), round to
  * nearest even -- the values the split-bf16 kernels compute while staging fp32 weights.
  * LAYOUT: one record per (cout row, tap, 32-channel chunk), record index = (row * ksize * ksize + tap) * (cin / 32) + chunk,
