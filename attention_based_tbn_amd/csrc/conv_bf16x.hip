@@ -407,16 +407,11 @@ template <int MT, int NT>
 static int launch_bf16x(const ConvP& p, int np, int epi, Bf16xKind kind, int grid, size_t lds_bytes, hipStream_t st) {
   auto go = [&](auto NPc, auto EPIc, auto KINDc) -> int {
     constexpr int NP = decltype(NPc)::value, EPI = decltype(EPIc)::value, KIND = decltype(KINDc)::value;
-    static size_t allowed = 64 * 1024;   // per instantiation: raise the dynamic-LDS limit once when a shape needs it
+    static size_t allowed = TBN_DYN_LDS_DEFAULT;   // per instantiation
     const void* fn = KIND == BF16X_PW ? reinterpret_cast<const void*>(&conv_bf16x_pw_kernel<NP, MT, NT, EPI>)
                                       : reinterpret_cast<const void*>(&conv_bf16x_kernel<NP, MT, NT, EPI, KIND == BF16X_3X3_PLANES>);
-    if (lds_bytes > allowed) {
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-        tbn_set_error("conv_bf16x: cannot raise the dynamic LDS limit");
-        return TBN_ERR_LAUNCH;
-      }
-      allowed = 160 * 1024;
-    }
+    const int rc = tbn_raise_dyn_lds(fn, lds_bytes, allowed, "conv_bf16x");
+    if (rc != TBN_OK) return rc;
     if (KIND == BF16X_PW)
       TBN_LAUNCH((conv_bf16x_pw_kernel<NP, MT, NT, EPI>), dim3(grid), dim3(256), lds_bytes, st, p);
     else
@@ -476,8 +471,7 @@ int tbn_launch_conv_bf16x(ConvP& p, int rowmode, int mt, int nt, double alg_byte
     p.wt_bytes = (unsigned)pb;
   }
   TBN_REQUIRE_OR(TBN_ERR_UNSUPPORTED, lds_bytes <= 160 * 1024, "conv: bf16x%d tile %dx%d needs %zu B of LDS", np, mt, nt, lds_bytes);
-  p.tiles_m = cdiv(p.M, 128 * mt);
-  p.tiles_n = cdiv(p.Cout, 32 * nt);
+  conv_set_tiles(p, 128, mt, nt);
   const int grid = p.tiles_m * p.tiles_n;
   const int epi = p.mode == CONV_EPI_EVAL ? 2 : 0;
   char nm[64];

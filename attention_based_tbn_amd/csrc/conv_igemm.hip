@@ -22,6 +22,18 @@
 //   output pixel is R contiguous runs of `Cin` floats (4 s2d pixels x 4*cin channels), one per s2d row, packed back to
 //   back -- 32-float K chunks straddle runs -- and the image carries its zero border physically, so the loads need
 //   no masks at all.
+// SHARED PIECES.  Device: the four GEMM bodies (conv_igemm_body: register-staged generic, conv_halo_body: 3x3 with the
+//   input patch staged once, conv_dma_body: LDS-DMA staging, conv_sk4_body: 32-row tiles whose waves split K) differ in how
+//   a tile gets into LDS and share CONV_KSTEP (the fragment reads, MFMA groups and scheduling chain of one 32-float K step;
+//   a body supplies the two fragment addresses), CONV_ROW_DECODE (GEMM row -> input pixel offset and tap-validity mask;
+//   conv_dma_body keeps a copy of its own), dma_swizzle (THE slot swizzle of an LDS-DMA tile) and, from tbn_conv_dev.h,
+//   xcd_tile and conv_epilogue.  The K step and the row decode are macros, and the accumulator clear and the
+//   register-staged B tile stay written out: as functions they changed the code the compiler emits
+//   (profiles/conv_igemm_refactor.md).  The weight-gradient kernel has its own K loop (b32 fragments, rotating accumulators).
+// Host: every family's instantiation is chosen by with_tile / with_wgrad_tile and a compile-time (epilogue | stages, reduce)
+//   selection; conv_prepare fills the derived geometry, conv_build_phases the parity phases of a strided data gradient
+//   (parity_tap: THE contribution rule, conv_push_tap: a tap-table entry); conv_stages, conv_set_tiles, conv_longest_first,
+//   rider_arg and tbn_raise_dyn_lds (tbn_kernels.h) each state one launch rule.
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -44,6 +56,85 @@
 #define WABL(bit) (TBN_ABLATE && (p.ablate & (bit)))   // weight-gradient kernel: 1 no loop loads, 2 no LDS stores, 4 no MFMA
 
 #include "tbn_conv_dev.h"
+
+// Row decode of the generic-tap bodies, stated once: GEMM row `m` -> `off`, the byte offset of the row's (n, iy0, ix0)
+// input pixel, and `mask`, bit t of which says that tap t of the row lies inside the image.  The taps form a (tny x tnx)
+// grid starting at (ty0, tx0): validity = row bits x column bits.  Rows >= M keep what the caller preset (no tap).
+// RM (the stem's packed rows): no masks, the border is in the image, and the pixel pitch is cp.
+// Several lanes share each tile row, so every body decodes a row ONCE (thread t < BM takes row m0 + t) into an LDS table
+// of (off, mask) that overlays the tile buffer, and reads its own rows back from there.
+// A macro for the reason given at CONV_KSTEP: as a function it moved 192 kernels of this file.  Used by conv_igemm_body and
+// conv_sk4_body; conv_dma_body keeps its own copy (see there).
+#define CONV_ROW_DECODE(RM, m, off, mask)                                                          \
+  if ((m) < p.M) {                                                                                 \
+    const uint32_t n_ = fdiv((uint32_t)(m), p.div_ohw);                                            \
+    const uint32_t rem_ = (uint32_t)(m) - n_ * p.div_ohw.d;                                        \
+    const uint32_t a_ = fdiv(rem_, p.div_ow);                                                      \
+    const uint32_t b_ = rem_ - a_ * p.div_ow.d;                                                    \
+    const int iy0_ = (int)a_ * p.in_sy;                                                            \
+    const int ix0_ = (int)b_ * p.in_sx;                                                            \
+    if (RM) {                                                                                      \
+      off = (unsigned)((((int)n_ * p.H + iy0_) * p.W + ix0_) * p.cp * 4);                          \
+    } else {                                                                                       \
+      unsigned yb_ = 0, xb_ = 0;                                                                   \
+      _Pragma("unroll") for (int r_ = 0; r_ < 3; ++r_)                                             \
+        if (r_ < p.tny && (unsigned)(iy0_ + p.ty0 + r_) < (unsigned)p.H) yb_ |= 1u << r_;          \
+      off = (unsigned)((((int)n_ * p.H + iy0_) * p.W + ix0_) * p.in_ld * 4);                       \
+      _Pragma("unroll") for (int c_ = 0; c_ < 3; ++c_)                                             \
+        if (c_ < p.tnx && (unsigned)(ix0_ + p.tx0 + c_) < (unsigned)p.W) xb_ |= 1u << c_;          \
+      _Pragma("unroll") for (int r_ = 0; r_ < 3; ++r_)                                             \
+        if ((yb_ >> r_) & 1u) mask |= xb_ << (r_ * p.tnx);                                         \
+    }                                                                                              \
+  }
+
+// One 32-float K step of a wave's (32 MT) x (32 NT) tile, stated once for the four GEMM bodies.  A_FRAG is the address
+// of this lane's float4 of A sub-tile row `i` in the 8-wide k group `kg`, B_FRAG the same for B sub-tile row `j`: two
+// expressions in those names, all a body has to supply.
+// Software pipeline over the four k groups: the fragments of group g + 1 are read while group g multiplies; the
+// sched_group_barrier chain pins that order (DS-read group, MFMA group, ...).  The fragment reads and MFMAs are ONE basic
+// block (no run-time conditions inside), so the scheduler issues the ds_reads ahead of the MFMAs that hide them.
+// The 4 MFMAs of one accumulator stay back to back: a dependent MFMA is only free when it directly follows its
+// producer (scripts/ubench: alternating two accumulators halves the rate).
+// -DTBN_ABLATE=1 builds: flag 32 drops the LDS fragment reads, flag 8 the MFMAs (in every family).
+// A macro, expanded where p, MT, NT and acc[MT][NT] are in scope (its own names end in an underscore): as a
+// __forceinline__ function template taking the two addresses as lambdas the same text moved 170 of this file's kernels
+// (profiles/conv_igemm_refactor.md); expanded in place every kernel is the machine code it was with the block written out.
+#define CONV_KSTEP(A_FRAG, B_FRAG)                                                                                       \
+  {                                                                                                                      \
+    float4 fa_[2][MT], fb_[2][NT];                                                                                       \
+    auto frag_load_ = [&](int buf_, int kg) {                                                                            \
+      _Pragma("unroll") for (int i = 0; i < MT; ++i) fa_[buf_][i] = *reinterpret_cast<const float4*>(A_FRAG);            \
+      _Pragma("unroll") for (int j = 0; j < NT; ++j) fb_[buf_][j] = *reinterpret_cast<const float4*>(B_FRAG);            \
+    };                                                                                                                   \
+    auto mfma_group_ = [&](int buf_) {                                                                                   \
+      _Pragma("unroll") for (int j = 0; j < NT; ++j) _Pragma("unroll") for (int i = 0; i < MT; ++i) {                    \
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa_[buf_][i].x, fb_[buf_][j].x, acc[i][j], 0, 0, 0);            \
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa_[buf_][i].y, fb_[buf_][j].y, acc[i][j], 0, 0, 0);            \
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa_[buf_][i].z, fb_[buf_][j].z, acc[i][j], 0, 0, 0);            \
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa_[buf_][i].w, fb_[buf_][j].w, acc[i][j], 0, 0, 0);            \
+      }                                                                                                                  \
+    };                                                                                                                   \
+    if (!ABL(32)) {                                                                                                      \
+      frag_load_(0, 0);                                                                                                  \
+      frag_load_(1, 1);                                                                                                  \
+    }                                                                                                                    \
+    if (!ABL(8)) mfma_group_(0);                                                                                         \
+    if (!ABL(32)) frag_load_(0, 2);                                                                                      \
+    if (!ABL(8)) mfma_group_(1);                                                                                         \
+    if (!ABL(32)) frag_load_(1, 3);                                                                                      \
+    if (!ABL(8)) mfma_group_(0);                                                                                         \
+    if (!ABL(8)) mfma_group_(1);                                                                                         \
+    if (!TBN_ABLATE) {                                                                                                   \
+      constexpr int NR_ = MT + NT, NM_ = 4 * MT * NT;                                                                    \
+      __builtin_amdgcn_sched_group_barrier(0x100, 2 * NR_, 0);                                                           \
+      __builtin_amdgcn_sched_group_barrier(0x008, NM_, 0);                                                               \
+      __builtin_amdgcn_sched_group_barrier(0x100, NR_, 0);                                                               \
+      __builtin_amdgcn_sched_group_barrier(0x008, NM_, 0);                                                               \
+      __builtin_amdgcn_sched_group_barrier(0x100, NR_, 0);                                                               \
+      __builtin_amdgcn_sched_group_barrier(0x008, 2 * NM_, 0);                                                           \
+      __builtin_amdgcn_sched_barrier(0); /* what follows (a barrier and its lgkmcnt(0)) stays below the last MFMA group */ \
+    }                                                                                                                    \
+  }
 
 // EPI: 0 plain (+bias, optional ReLU / accumulate), 1 training-BN statistics, 2 eval-BN fold + ReLU,
 //      3 plain with output scatter (parity phase of a strided data gradient)
@@ -87,30 +178,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvP& p, const int bid, f
       const int m = m0 + tid;
       unsigned mask = 0;
       unsigned off = ROWMODE ? TBN_OOB : 0u;
-      if (m < p.M) {
-        const uint32_t n = fdiv((uint32_t)m, p.div_ohw);
-        const uint32_t rem = (uint32_t)m - n * p.div_ohw.d;
-        const uint32_t a = fdiv(rem, p.div_ow);
-        const uint32_t b = rem - a * p.div_ow.d;
-        const int iy0 = (int)a * p.in_sy;
-        const int ix0 = (int)b * p.in_sx;
-        if (ROWMODE) {
-          off = (unsigned)((((int)n * p.H + iy0) * p.W + ix0) * p.cp * 4);
-        } else {
-          // taps form a (tny x tnx) grid starting at (ty0, tx0): validity = row bits x column bits
-          unsigned yb = 0, xb = 0;
-#pragma unroll
-          for (int r = 0; r < 3; ++r)
-            if (r < p.tny && (unsigned)(iy0 + p.ty0 + r) < (unsigned)p.H) yb |= 1u << r;
-          off = (unsigned)((((int)n * p.H + iy0) * p.W + ix0) * p.in_ld * 4);
-#pragma unroll
-          for (int c = 0; c < 3; ++c)
-            if (c < p.tnx && (unsigned)(ix0 + p.tx0 + c) < (unsigned)p.W) xb |= 1u << c;
-#pragma unroll
-          for (int r = 0; r < 3; ++r)
-            if ((yb >> r) & 1u) mask |= xb << (r * p.tnx);
-        }
-      }
+      CONV_ROW_DECODE(ROWMODE, m, off, mask)
       rowtab[2 * tid] = off;
       rowtab[2 * tid + 1] = mask;
     }
@@ -128,7 +196,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvP& p, const int bid, f
     if (a_off[0] == 0x12345u && a_mask[AR - 1] == 77u) p.seg[0].ptr[0] = 1.f;
     return;
   }
-  f32x16 acc[MT][NT];
+  f32x16 acc[MT][NT];   // (the clear stays written out in the four bodies: as a helper it moved 232 kernels, profiles/bf16x_refactor.md)
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -203,59 +271,14 @@ __device__ __forceinline__ void conv_igemm_body(const ConvP& p, const int bid, f
   const int lrow = lane & 31, lhalf = lane >> 5;
   // two LDS stages, ONE barrier per K-step: the stage written in step ks was last read in step ks-1,
   // and every wave has passed the barrier that ended step ks-1 before any wave writes it.
-  // The fragment reads and MFMAs of a K-step are ONE basic block (no run-time conditions inside), so the
-  // scheduler issues the ds_reads ahead of the MFMAs that hide them.  A ragged last N tile multiplies its
-  // zero-filled weight rows (rows >= Cout are out-of-range loads) instead of branching around MFMAs.
+  // A ragged last N tile multiplies its zero-filled weight rows (rows >= Cout are out-of-range loads) instead of
+  // branching around MFMAs.
   for (int ks = 0; ks < ksteps; ++ks) {
     const bool more = (ks + 1 < ksteps) && !ABL(4);   // flag 4: ablation, no loads in the loop
     if (more) load_tiles();  // global loads stay in flight under the MFMA phase
     const float* As = lds + (STAGES == 2 ? (ks & 1) * TILE_F : 0);
     const float* Bs = As + BM * LDT;
-    float4 fa[2][MT], fb[2][NT];
-    auto frag_load = [&](int buf, int kg) {
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-        fa[buf][i] =
-            *reinterpret_cast<const float4*>(&As[(wave * 32 * MT + i * 32 + lrow) * LDT + kg * 8 + lhalf * 4]);
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-        fb[buf][j] = *reinterpret_cast<const float4*>(&Bs[(j * 32 + lrow) * LDT + kg * 8 + lhalf * 4]);
-    };
-    auto mfma_group = [&](int buf) {
-      // the 4 MFMAs of one accumulator stay back to back: a dependent MFMA is only free when it directly
-      // follows its producer (scripts/ubench: alternating two accumulators halves the rate)
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[buf][i].x, fb[buf][j].x, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[buf][i].y, fb[buf][j].y, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[buf][i].z, fb[buf][j].z, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[buf][i].w, fb[buf][j].w, acc[i][j], 0, 0, 0);
-        }
-    };
-    // software pipeline over the four 8-wide k groups: the fragments of group g+1 are read while group g
-    // multiplies; the sched_group_barrier chain pins that order (DS-read group, MFMA group, ...)
-    if (!ABL(32)) {   // flag 32: ablation, no LDS fragment reads
-      frag_load(0, 0);
-      frag_load(1, 1);
-    }
-    if (!ABL(8)) mfma_group(0);   // flag 8: ablation, no MFMA
-    if (!ABL(32)) frag_load(0, 2);
-    if (!ABL(8)) mfma_group(1);
-    if (!ABL(32)) frag_load(1, 3);
-    if (!ABL(8)) mfma_group(0);
-    if (!ABL(8)) mfma_group(1);
-    if (!TBN_ABLATE) {
-      constexpr int NR = MT + NT, NM = 4 * MT * NT;
-      __builtin_amdgcn_sched_group_barrier(0x100, 2 * NR, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 2 * NM, 0);
-      __builtin_amdgcn_sched_barrier(0);  // keep the barrier (and its lgkmcnt(0)) below the last MFMA group
-    }
+    CONV_KSTEP(&As[(wave * 32 * MT + i * 32 + lrow) * LDT + kg * 8 + lhalf * 4], &Bs[(j * 32 + lrow) * LDT + kg * 8 + lhalf * 4])
     if (STAGES == 2) {
       if (more) store_tiles(lds + ((ks + 1) & 1) * TILE_F);
       if (!ABL(64)) __syncthreads();   // flag 64: ablation, no barrier
@@ -287,6 +310,11 @@ __device__ __forceinline__ void lds_dma16(i32x4 rsrc, unsigned lds_dst, unsigned
                : "memory");   // (m0 cannot be named as a clobber: clang rejects it as a reserved register; nothing else in this
                               //  kernel keeps a value in M0 -- no readlane / movrel / LDS-direct uses)
 }
+// THE SWIZZLE of an LDS-DMA tile.  A wave instruction writes 8 rows x 128 B, so rows are UNPADDED and conflict-free b128
+// fragment reads come from an XOR swizzle instead: 16-B slot q of tile row r lives at slot q ^ ((r >> 1) & 7).  Returns the
+// byte offset inside the row.  Applied twice: on the global SOURCE address of each lane (the lane whose bytes land in
+// slot q of row r fetches chunk q ^ f(r)) and again on the fragment read (logical chunk 2 kg + lhalf).
+__device__ __forceinline__ constexpr unsigned dma_swizzle(const int q, const int r) { return (unsigned)((q ^ ((r >> 1) & 7)) << 4); }
 
 // Round 6: the LDS-halo kernel's WEIGHT tiles (one 32*NT x 32 tile per tap) go global -> LDS by LDS-DMA for the MT = 1 tiles -- no
 // VGPR round trip, no ds_write, the store's issue slots go to the MFMAs (scripts/ubench/kstep_cost.hip: the tile store costs the
@@ -392,20 +420,19 @@ __device__ __forceinline__ void conv_halo_body(const ConvP& p, const int bid, fl
     for (int i = 0; i < NT; ++i) *reinterpret_cast<float4*>(&Bs[(r0 + 32 * i) * LDT + c4 * 4]) = rb[i];
   };
   // DMAB: the weight tile of a tap goes global -> LDS directly (no VGPR round trip, no ds_write): rows are 128 B, unpadded,
-  // 16-B slot q of row r at slot q ^ ((r >> 1) & 7) (the swizzle of conv_dma_body, applied on the source address and again
-  // on the fragment read); a wave instruction writes 8 rows
+  // their 16-B slots swizzled (dma_swizzle); a wave instruction writes 8 rows
   const int dr = lane >> 3, dslot = lane & 7;
   unsigned bd_voff[NT], fb_addr[NT][4];
 #pragma unroll
   for (int i = 0; i < NT; ++i) {
     const int r = (wave + 4 * i) * 8 + dr;
-    bd_voff[i] = (unsigned)(n0 + r) * (unsigned)p.Krow * 4u + (unsigned)((dslot ^ ((r >> 1) & 7)) << 4);
+    bd_voff[i] = (unsigned)(n0 + r) * (unsigned)p.Krow * 4u + dma_swizzle(dslot, r);
   }
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
     const int r = j * 32 + lrow;
 #pragma unroll
-    for (int kg = 0; kg < 4; ++kg) fb_addr[j][kg] = (unsigned)(r * 128 + (((2 * kg + lhalf) ^ ((r >> 1) & 7)) << 4));
+    for (int kg = 0; kg < 4; ++kg) fb_addr[j][kg] = (unsigned)(r * 128) + dma_swizzle(2 * kg + lhalf, r);
   }
   const int wv = __builtin_amdgcn_readfirstlane(wave);
   const unsigned ldsB = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(uintptr_t)reinterpret_cast<char*>(Bs0));
@@ -461,47 +488,12 @@ __device__ __forceinline__ void conv_halo_body(const ConvP& p, const int bid, fl
       }
       const float* Bs = Bs0 + (ks & 1) * (BN * LDT);
       const char* Bd = reinterpret_cast<const char*>(Bs0) + (ks & 1) * (BN * 128);
-      float4 fa[2][MT], fb[2][NT];
-      auto frag_load = [&](int buf, int kg) {
-#pragma unroll
-        for (int i = 0; i < MT; ++i) fa[buf][i] = *reinterpret_cast<const float4*>(As_b + fa_off[i][t] + kg * 32);
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-          fb[buf][j] = DMAB ? *reinterpret_cast<const float4*>(Bd + fb_addr[j][kg])
-                            : *reinterpret_cast<const float4*>(&Bs[(j * 32 + lrow) * LDT + kg * 8 + lhalf * 4]);
-      };
-      auto mfma_group = [&](int buf) {
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-          for (int i = 0; i < MT; ++i) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[buf][i].x, fb[buf][j].x, acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[buf][i].y, fb[buf][j].y, acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[buf][i].z, fb[buf][j].z, acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[buf][i].w, fb[buf][j].w, acc[i][j], 0, 0, 0);
-          }
-      };
-      frag_load(0, 0);
-      frag_load(1, 1);
-      mfma_group(0);
-      frag_load(0, 2);
-      mfma_group(1);
-      frag_load(1, 3);
-      mfma_group(0);
-      mfma_group(1);
-      {
-        constexpr int NR = MT + NT, NM = 4 * MT * NT;
-        // (the B-tile loads of the next tap are left to the scheduler, which sinks them to 4-12 MFMAs in front of the
-        // ds_write that waits for them: pinning them to the top of the tap with a VMEM group measured 0-2 % SLOWER on
-        // warm clocks, 25 % on one <1,3> shape -- the weights are L2 hits and the early loads lengthen live ranges)
-        __builtin_amdgcn_sched_group_barrier(0x100, 2 * NR, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 2 * NM, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+      // (the B-tile loads of the next tap are left to the scheduler, which sinks them to 4-12 MFMAs in front of the
+      // ds_write that waits for them: pinning them to the top of the tap with a VMEM group in the K step's chain measured
+      // 0-2 % SLOWER on warm clocks, 25 % on one <1,3> shape -- the weights are L2 hits and the early loads lengthen
+      // live ranges)
+      CONV_KSTEP(As_b + fa_off[i][t] + kg * 32,
+                 DMAB ? Bd + fb_addr[j][kg] : reinterpret_cast<const char*>(&Bs[(j * 32 + lrow) * LDT + kg * 8 + lhalf * 4]))
       if (DMAB)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA of the next tap's weights has landed (and so has
                                                            // the next chunk's halo prefetch issued at the top of tap 0)
@@ -530,11 +522,9 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(ConvP p, RiderP rider) {
 // LDS-DMA variant of the generic implicit GEMM (1x1 / 3x3, any stride; not the stem): the A and B tiles go from
 // global memory STRAIGHT into LDS (`buffer_load_dwordx4 ... lds`: no VGPR round trip, no ds_write issue, 4*MT + NT
 // fewer VGPR quads), two stages, one barrier per K-step.  An LDS-DMA instruction writes lane l's 16 bytes at
-// (wave-uniform base) + 16 l, i.e. 8 rows x 128 B per wave instruction: rows are UNPADDED and conflict-free b128
-// fragment reads come from an XOR swizzle instead -- 16-B slot q of tile row r lives at slot q ^ ((r >> 1) & 7); the
-// swizzle is applied on the global SOURCE address of each lane (lane (row l >> 3, slot l & 7) fetches chunk
-// (l & 7) ^ f(row)) and again on the fragment read.  Out-of-image taps / rows beyond M or Cout are out-of-range buffer
-// offsets: the DMA writes zeros.
+// (wave-uniform base) + 16 l, i.e. 8 rows x 128 B per wave instruction: rows are UNPADDED and their 16-B slots swizzled
+// (dma_swizzle, above: on the source address and again on the fragment read).  Out-of-image taps / rows beyond M or Cout
+// are out-of-range buffer offsets: the DMA writes zeros.
 // The DMA is issued through inline asm: hipcc would otherwise treat each LDS-DMA as a pending LDS write and put an
 // `s_waitcnt vmcnt(0)` in front of the next fragment read -- draining the prefetch it is supposed to overlap.  The
 // asm statement is invisible to that bookkeeping; the wait is placed by hand before the barrier that publishes the
@@ -557,6 +547,9 @@ __device__ __forceinline__ void conv_dma_body(const ConvP& p, const int bid, flo
   {
     // each tile row is decoded once (thread t < BM takes row t) into an LDS table -- eight lanes share a row; decoding
     // per lane repeated the two magic divisions and the tap masks 8x (see conv_igemm_body)
+    // (CONV_ROW_DECODE written out, with the offset formed LAST: the order of these statements decides the code of this
+    // body's 32 kernels, and the macro's order is the one the 160 kernels of the other two bodies need --
+    // profiles/conv_igemm_refactor.md.  Same values.)
     unsigned* rowtab = reinterpret_cast<unsigned*>(lds);   // [BM][2]: no DMA has been issued yet
     if (tid < BM) {
       const int m = m0 + tid;
@@ -588,7 +581,7 @@ __device__ __forceinline__ void conv_dma_body(const ConvP& p, const int bid, flo
     for (int i = 0; i < AR; ++i) {
       const int r = (wave * AR + i) * 8 + rl;    // tile row
       const uint2 e = *reinterpret_cast<const uint2*>(&rowtab[2 * r]);
-      a_off[i] = e.x + (unsigned)((slot ^ ((r >> 1) & 7)) << 4);   // swizzled source chunk (masked rows never load)
+      a_off[i] = e.x + dma_swizzle(slot, r);   // swizzled source chunk (masked rows never load)
       a_mask[i] = e.y;
     }
     __syncthreads();   // the table is dead: the first DMA may overwrite it
@@ -597,7 +590,7 @@ __device__ __forceinline__ void conv_dma_body(const ConvP& p, const int bid, flo
 #pragma unroll
   for (int i = 0; i < NT; ++i) {
     const int r = (wave + 4 * i) * 8 + rl;     // B tile row (= output channel n0 + r); rows >= Cout: beyond wt_bytes
-    b_voff[i] = (unsigned)(n0 + r) * (unsigned)p.Krow * 4u + (unsigned)((slot ^ ((r >> 1) & 7)) << 4);
+    b_voff[i] = (unsigned)(n0 + r) * (unsigned)p.Krow * 4u + dma_swizzle(slot, r);
   }
   // wave-uniform LDS byte addresses of this wave's DMA instructions (stage 0)
   const int wv = __builtin_amdgcn_readfirstlane(wave);
@@ -647,14 +640,14 @@ __device__ __forceinline__ void conv_dma_body(const ConvP& p, const int bid, flo
   for (int i = 0; i < MT; ++i) {
     const int r = wave * 32 * MT + i * 32 + lrow;
 #pragma unroll
-    for (int kg = 0; kg < 4; ++kg) fa_addr[i][kg] = (unsigned)(r * 128 + (((2 * kg + lhalf) ^ ((r >> 1) & 7)) << 4));
+    for (int kg = 0; kg < 4; ++kg) fa_addr[i][kg] = (unsigned)(r * 128) + dma_swizzle(2 * kg + lhalf, r);
   }
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
     const int r = j * 32 + lrow;
 #pragma unroll
     for (int kg = 0; kg < 4; ++kg)
-      fb_addr[j][kg] = (unsigned)(BM * 128 + r * 128 + (((2 * kg + lhalf) ^ ((r >> 1) & 7)) << 4));
+      fb_addr[j][kg] = (unsigned)(BM * 128 + r * 128) + dma_swizzle(2 * kg + lhalf, r);
   }
 
   const int ksteps = p.K >> 5;
@@ -663,42 +656,7 @@ __device__ __forceinline__ void conv_dma_body(const ConvP& p, const int bid, flo
   __syncthreads();   // publishes stage 0
 
   auto compute = [&](const char* sb) {
-    float4 fa[2][MT], fb[2][NT];
-    auto frag_load = [&](int buf, int kg) {
-#pragma unroll
-      for (int i = 0; i < MT; ++i) fa[buf][i] = *reinterpret_cast<const float4*>(sb + fa_addr[i][kg]);
-#pragma unroll
-      for (int j = 0; j < NT; ++j) fb[buf][j] = *reinterpret_cast<const float4*>(sb + fb_addr[j][kg]);
-    };
-    auto mfma_group = [&](int buf) {
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[buf][i].x, fb[buf][j].x, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[buf][i].y, fb[buf][j].y, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[buf][i].z, fb[buf][j].z, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[buf][i].w, fb[buf][j].w, acc[i][j], 0, 0, 0);
-        }
-    };
-    frag_load(0, 0);
-    frag_load(1, 1);
-    mfma_group(0);
-    frag_load(0, 2);
-    mfma_group(1);
-    frag_load(1, 3);
-    mfma_group(0);
-    mfma_group(1);
-    {
-      constexpr int NR = MT + NT, NM = 4 * MT * NT;
-      __builtin_amdgcn_sched_group_barrier(0x100, 2 * NR, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 2 * NM, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    CONV_KSTEP(sb + fa_addr[i][kg], sb + fb_addr[j][kg])
   };
   // two K-steps per iteration: the stage is a compile-time constant (fragment offsets stay immediates)
   for (int ks = 0; ks < ksteps; ks += 2) {
@@ -753,24 +711,7 @@ __device__ __forceinline__ void conv_sk4_body(const ConvP& p, const int bid, flo
     if (tid < BM) {
       const int m = m0 + tid;
       unsigned mask = 0, off = 0;
-      if (m < p.M) {
-        const uint32_t n = fdiv((uint32_t)m, p.div_ohw);
-        const uint32_t rem = (uint32_t)m - n * p.div_ohw.d;
-        const uint32_t a = fdiv(rem, p.div_ow);
-        const uint32_t b = rem - a * p.div_ow.d;
-        const int iy0 = (int)a * p.in_sy, ix0 = (int)b * p.in_sx;
-        unsigned yb = 0, xb = 0;
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-          if (r < p.tny && (unsigned)(iy0 + p.ty0 + r) < (unsigned)p.H) yb |= 1u << r;
-        off = (unsigned)((((int)n * p.H + iy0) * p.W + ix0) * p.in_ld * 4);
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          if (c < p.tnx && (unsigned)(ix0 + p.tx0 + c) < (unsigned)p.W) xb |= 1u << c;
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-          if ((yb >> r) & 1u) mask |= xb << (r * p.tnx);
-      }
+      CONV_ROW_DECODE(false, m, off, mask)
       rowtab[2 * tid] = off;
       rowtab[2 * tid + 1] = mask;
     }
@@ -828,44 +769,7 @@ __device__ __forceinline__ void conv_sk4_body(const ConvP& p, const int bid, flo
     const bool more = q + 4 < ksteps;
     __builtin_amdgcn_wave_barrier();
     if (more) load_tiles();   // in flight under the MFMA phase
-    float4 fa[2][MT], fb[2][NT];
-    auto frag_load = [&](int buf, int kg) {
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-        fa[buf][i] = *reinterpret_cast<const float4*>(&As[(i * 32 + lrow) * LDT + kg * 8 + lhalf * 4]);
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-        fb[buf][j] = *reinterpret_cast<const float4*>(&Bs[(j * 32 + lrow) * LDT + kg * 8 + lhalf * 4]);
-    };
-    auto mfma_group = [&](int buf) {
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[buf][i].x, fb[buf][j].x, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[buf][i].y, fb[buf][j].y, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[buf][i].z, fb[buf][j].z, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[buf][i].w, fb[buf][j].w, acc[i][j], 0, 0, 0);
-        }
-    };
-    frag_load(0, 0);
-    frag_load(1, 1);
-    mfma_group(0);
-    frag_load(0, 2);
-    mfma_group(1);
-    frag_load(1, 3);
-    mfma_group(0);
-    mfma_group(1);
-    {
-      constexpr int NR = MT + NT, NM = 4 * MT * NT;
-      __builtin_amdgcn_sched_group_barrier(0x100, 2 * NR, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 2 * NM, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    CONV_KSTEP(&As[(i * 32 + lrow) * LDT + kg * 8 + lhalf * 4], &Bs[(j * 32 + lrow) * LDT + kg * 8 + lhalf * 4])
     __builtin_amdgcn_wave_barrier();
     if (more) store_tiles();   // behind this step's fragment reads in the wave's LDS queue
   }
@@ -899,6 +803,9 @@ __global__ __launch_bounds__(256) void conv_sk4_kernel(ConvP p, RiderP rider) {
   TBN_RIDER_DISPATCH(rider, bid)
   conv_sk4_body<MT, NT, EPI, RED>(p, bid, lds);
 }
+
+#undef CONV_KSTEP
+#undef CONV_ROW_DECODE
 
 // The four output-parity phases of a stride-2 data gradient in ONE launch: each phase alone is a small GEMM
 // (M / 4 rows, 1-4 taps) that leaves most CUs idle; a workgroup finds its phase by a scalar scan.
@@ -1245,6 +1152,25 @@ static void conv_kernel_name(char (&nm)[64], const char* kernel, int mt, int nt,
   snprintf(nm, sizeof(nm), "%s<%d, %d, %s%d%s%s>", kernel, mt, nt, rowmode, e.epi, stg, e.red ? ", true" : "");
 }
 
+// the rider of a launch as the by-value kernel argument: a copy of *rider, or all zeros (span 0: no rider)
+static RiderP& rider_arg(const RiderP* rider) {
+  static thread_local RiderP rd;
+  if (rider != nullptr)
+    rd = *rider;
+  else
+    memset(&rd, 0, sizeof(rd));
+  return rd;
+}
+// LDS stages of the register-staged kernel where the caller does not say: big tiles take one (keeps 2 workgroups per CU)
+static int conv_stages(int asked, int mt) { return (asked == 1 || asked == 2) ? asked : ((mt == 1) ? 2 : 1); }
+// Longest workgroups first: the dispatcher hands out workgroups in block order, so the members of a joint launch (parity
+// phases, a pair) are ordered by the length of their K loop -- a launch should not end with its long workgroups running
+// alone.  A/B runs: TBN_LPT=0 keeps the original order.
+static bool conv_longest_first() {
+  static const int lpt = tbn_env_int("TBN_LPT", 1, 0, 1);
+  return lpt != 0;
+}
+
 // `rd` = the rider riding in this launch (rd.span == 0: none), `grid` = GEMM workgroups + rd.span (tbn_rider_place)
 template <int MT, int NT, bool RM, int EPI, bool RED>
 static int launch_conv_e(const ConvP& p, const RiderP& rd, int grid, hipStream_t st) {
@@ -1263,15 +1189,9 @@ size_t tbn_conv_halo_lds_bytes(const ConvP& p, int mt, int nt) {
 
 template <int MT, int NT, int EPI, bool RED>
 static int launch_halo_e(const ConvP& p, const RiderP& rd, int grid, size_t lds_bytes, hipStream_t st) {
-  static size_t allowed = 64 * 1024;   // per instantiation: raise the dynamic-LDS limit once when a shape needs it
-  if (lds_bytes > allowed) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<MT, NT, EPI, RED>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      tbn_set_error("conv_halo: cannot raise the dynamic LDS limit");
-      return TBN_ERR_LAUNCH;
-    }
-    allowed = 160 * 1024;
-  }
+  static size_t allowed = TBN_DYN_LDS_DEFAULT;   // per instantiation
+  const int rc = tbn_raise_dyn_lds(reinterpret_cast<const void*>(&conv_halo_kernel<MT, NT, EPI, RED>), lds_bytes, allowed, "conv_halo");
+  if (rc != TBN_OK) return rc;
   TBN_LAUNCH((conv_halo_kernel<MT, NT, EPI, RED>), dim3(grid), dim3(256), lds_bytes, st, p, rd);
   return TBN_OK;
 }
@@ -1325,11 +1245,7 @@ static double conv_alg_bytes(const ConvP& p, int rowmode) {
 static int launch_conv_tiles(ConvP& p, int rowmode, int mt, int nt, hipStream_t st, const RiderP* rider) {
   if (p.flags & (CONV_FLAG_BF16X6 | CONV_FLAG_BF16X3))
     return tbn_launch_conv_bf16x(p, rowmode, mt, nt, conv_alg_bytes(p, rowmode), st, rider);
-  static thread_local RiderP rd;      // by value into the kernel arguments (zeroed: no rider)
-  if (rider != nullptr)
-    rd = *rider;
-  else
-    memset(&rd, 0, sizeof(rd));
+  RiderP& rd = rider_arg(rider);
   const bool scatter = (p.out_sy != 1) || (p.out_sx != 1);
   if ((mt <= 0 || nt <= 0) && !rowmode && !scatter) {
     // heuristic launches (the head Linear layers: M = 96 ... 768 rows): a grid of 128-row tiles that leaves most CUs
@@ -1340,7 +1256,7 @@ static int launch_conv_tiles(ConvP& p, int rowmode, int mt, int nt, hipStream_t 
     if (p.halo == 3) mt = nt = 1;
   }
   if (mt <= 0 || nt <= 0) tbn_conv_pick_tile(p.M, p.Cout, p.K, &mt, &nt);
-  if (p.stages != 1 && p.stages != 2) p.stages = (mt == 1) ? 2 : 1;  // big tiles: keep 2 workgroups per CU
+  p.stages = conv_stages(p.stages, mt);
   // kernel family: 0 register-staged generic (the only one with packed rows and the scatter epilogue), 1 LDS-halo,
   // 2 LDS-DMA staging, 3 split-K tile (small-M layers: 32-row tiles, the four waves split K)
   const int family = (rowmode || p.halo < 1 || p.halo > 3) ? 0 : p.halo;
@@ -1353,8 +1269,7 @@ static int launch_conv_tiles(ConvP& p, int rowmode, int mt, int nt, hipStream_t 
     TBN_REQUIRE(lds_bytes > 0 && lds_bytes <= 160 * 1024, "conv: the LDS-halo kernel does not handle this shape / tile");
     TBN_REQUIRE(!scatter && mt <= 2 && nt <= 4, "conv: unsupported halo launch (tile %dx%d)", mt, nt);
   }
-  p.tiles_m = cdiv(p.M, (family == 3 ? 32 : 128) * mt);
-  p.tiles_n = cdiv(p.Cout, 32 * nt);
+  conv_set_tiles(p, family == 3 ? 32 : 128, mt, nt);
   const int grid = tbn_rider_place(&rd, p.tiles_m * p.tiles_n);
   const EpiSel es = conv_epilogue(p.mode, p.nred, scatter, rowmode != 0);
   char nm[64], kernel[32];
@@ -1398,10 +1313,16 @@ static int launch_conv_tiles(ConvP& p, int rowmode, int mt, int nt, hipStream_t 
   return TBN_OK;
 }
 
-// Fills the derived geometry and launches.  `up == 2` (data gradient of a stride-2 conv; the caller
-// passes stride 1, pad = k-1-pad_fwd and tap-flipped weights) is decomposed into the 4 output-parity
-// phases: each phase only visits the taps that hit a real (non zero-inserted) dy sample, so no MFMA
-// work is spent on inserted zeros (2.25 instead of 9 taps per output pixel for 3x3).
+// appends a tap to the launch's tap table: input offset (dy, dx) from the window origin pixel (padding folded in), weights
+// at float `koff` of a weight row (packed rows: the runs are addressed by the kernel, no byte offset)
+static void conv_push_tap(ConvP& q, int dy, int dx, int koff, bool rowmode = false) {
+  const int t = q.ntaps++;
+  q.tap_dy[t] = dy;
+  q.tap_dx[t] = dx;
+  q.tap_koff[t] = koff;
+  q.tap_off[t] = rowmode ? 0 : (dy * q.W + dx) * q.in_ld * 4;
+}
+
 // validation + derived fields common to every launch form; `*single` = 1 when the launch is a single GEMM
 // (up == 1: geometry completely filled), 0 when the caller still has to split it into parity phases (up == 2)
 static int conv_prepare(ConvP& p, int rowmode, int* single) {
@@ -1463,13 +1384,10 @@ static int conv_prepare(ConvP& p, int rowmode, int* single) {
     p.out_sy = p.out_sx = 1;
     p.out_oy = p.out_ox = 0;
     p.in_sy = p.in_sx = p.stride;
-    p.ntaps = taps_full;
+    p.ntaps = 0;
     for (int t = 0; t < taps_full; ++t) {
       const int r = rowmode ? 0 : t / p.S, s = rowmode ? 0 : t % p.S;
-      p.tap_dy[t] = r - p.pad;
-      p.tap_dx[t] = s - p.pad;
-      p.tap_koff[t] = t * p.Cin;
-      p.tap_off[t] = rowmode ? 0 : (p.tap_dy[t] * p.W + p.tap_dx[t]) * p.in_ld * 4;
+      conv_push_tap(p, r - p.pad, s - p.pad, t * p.Cin, rowmode != 0);
     }
     if (!rowmode) p.K = p.ntaps * p.Cin;
     p.ty0 = -p.pad;
@@ -1485,6 +1403,72 @@ static int conv_prepare(ConvP& p, int rowmode, int* single) {
   return TBN_OK;
 }
 
+// Stride-2 data gradient, one axis: filter tap r reaches a real (not zero-inserted) dy sample of the output pixels of
+// parity `par` when par - pad + r is even; *d = that sample's offset in dy (the number halved is even, possibly
+// negative: the division is exact)
+static bool parity_tap(int par, int pad, int r, int* d) {
+  const int o = par - pad + r;
+  *d = o / 2;
+  return (o & 1) == 0;
+}
+// The output-parity phases of the strided data gradient `p` (prepared, up == 2): each phase is a unit-stride GEMM over
+// the output pixels of one parity with the taps that contribute there.  *empty_phase: a parity with pixels but no tap
+// (1x1 / stride 2 only) -- its gradient is zero and no phase writes it.
+static void conv_build_phases(const ConvP& p, ConvPhases& phases, bool* empty_phase) {
+  const int full_M = p.N * p.OH * p.OW;
+  phases.n = 0;
+  *empty_phase = false;
+  for (int py = 0; py < 2; ++py)
+    for (int px = 0; px < 2; ++px) {
+      ConvP q = p;
+      q.OHs = (p.OH - py + 1) / 2;
+      q.OWs = (p.OW - px + 1) / 2;
+      if (q.OHs <= 0 || q.OWs <= 0) continue;
+      q.out_sy = q.out_sx = 2;
+      q.out_oy = py;
+      q.out_ox = px;
+      q.in_sy = q.in_sx = 1;
+      q.div_ohw = make_fastdiv((uint32_t)(q.OHs * q.OWs));
+      q.div_ow = make_fastdiv((uint32_t)q.OWs);
+      // the tap grid of this parity: (tny x tnx) taps, the first at (ty0, tx0) (offsets grow with r / s)
+      q.ntaps = 0;
+      q.tny = q.tnx = 0;
+      q.ty0 = q.tx0 = 1 << 20;
+      int dy, dx;
+      for (int r = 0; r < p.R; ++r) {
+        if (!parity_tap(py, p.pad, r, &dy)) continue;
+        if (q.tny++ == 0) q.ty0 = dy;
+        q.tnx = 0;   // the same columns in every contributing row
+        for (int s2 = 0; s2 < p.S; ++s2) {
+          if (!parity_tap(px, p.pad, s2, &dx)) continue;
+          if (q.tnx++ == 0) q.tx0 = dx;
+          conv_push_tap(q, dy, dx, (r * p.S + s2) * p.Cin);
+        }
+      }
+      q.M = p.N * q.OHs * q.OWs;
+      q.alg_flops = p.alg_flops * ((double)q.M / full_M);
+      if (q.ntaps == 0) {
+        *empty_phase = true;
+        continue;
+      }
+      q.K = q.ntaps * p.Cin;
+      phases.ph[phases.n++] = q;
+    }
+  // longest workgroups first: a phase's K is (its taps) x Cin -- 1, 2, 2 and 4 taps for a 3x3 / stride-2 layer; with the
+  // 4-tap phase LAST (parity order) its 4x longer workgroups started when the others were nearly done
+  for (int a = 0; a < phases.n && conv_longest_first(); ++a)
+    for (int b = a + 1; b < phases.n; ++b)
+      if (phases.ph[b].K > phases.ph[a].K) {
+        const ConvP t = phases.ph[a];
+        phases.ph[a] = phases.ph[b];
+        phases.ph[b] = t;
+      }
+}
+
+// Fills the derived geometry and launches: pre-checks, conv_prepare, then a single GEMM (launch_conv_tiles) or, for
+// `up == 2` (data gradient of a stride-2 conv; the caller passes stride 1, pad = k-1-pad_fwd and tap-flipped weights), the
+// output-parity phases in one launch: each phase only visits the taps that hit a real (non zero-inserted) dy sample, so
+// no MFMA work is spent on inserted zeros (2.25 instead of 9 taps per output pixel for 3x3).
 int tbn_launch_conv(ConvP p, int rowmode, int mt, int nt, hipStream_t st, const RiderP* rider) {
   if (p.flags & CONV_FLAG_BF16X_PLANES) {   // refused here, in bf16x terms, before the generic checks see the launch
     TBN_REQUIRE((p.flags & (CONV_FLAG_BF16X6 | CONV_FLAG_BF16X3)) != 0,
@@ -1500,7 +1484,6 @@ int tbn_launch_conv(ConvP p, int rowmode, int mt, int nt, hipStream_t st, const 
   TBN_REQUIRE_OR(TBN_ERR_UNSUPPORTED, (p.flags & (CONV_FLAG_BF16X6 | CONV_FLAG_BF16X3 | CONV_FLAG_BF16X_PLANES)) == 0,
                  "conv: the bf16x kernels (flags 32 / 64) do not compute strided data gradients");
   TBN_REQUIRE(!rowmode && p.stride == 1 && p.R == p.S && p.R * p.S <= 9, "conv: unsupported strided data gradient");
-  const double flops_total = p.alg_flops;
   const int full_M = p.N * p.OH * p.OW;
   {
     // the scatter epilogue forms its byte offsets as 24-bit products (output pixel) x (row pitch in bytes): v_mul_u32_u24
@@ -1514,55 +1497,8 @@ int tbn_launch_conv(ConvP p, int rowmode, int mt, int nt, hipStream_t st, const 
                 full_M);
   }
   static thread_local ConvPhases phases;   // ~2 KB kernel argument, built in place
-  phases.n = 0;
   bool empty_phase = false;
-  for (int py = 0; py < 2; ++py)
-    for (int px = 0; px < 2; ++px) {
-      ConvP q = p;
-      q.OHs = (p.OH - py + 1) / 2;
-      q.OWs = (p.OW - px + 1) / 2;
-      if (q.OHs <= 0 || q.OWs <= 0) continue;
-      q.out_sy = q.out_sx = 2;
-      q.out_oy = py;
-      q.out_ox = px;
-      q.in_sy = q.in_sx = 1;
-      q.ntaps = 0;
-      q.tny = q.tnx = 0;
-      q.ty0 = q.tx0 = 1 << 20;
-      for (int r = 0; r < p.R; ++r)
-        if (((py - p.pad + r) & 1) == 0) {
-          ++q.tny;
-          if ((py - p.pad + r) / 2 < q.ty0) q.ty0 = (py - p.pad + r) / 2;
-        }
-      for (int s2 = 0; s2 < p.S; ++s2)
-        if (((px - p.pad + s2) & 1) == 0) {
-          ++q.tnx;
-          if ((px - p.pad + s2) / 2 < q.tx0) q.tx0 = (px - p.pad + s2) / 2;
-        }
-      q.div_ohw = make_fastdiv((uint32_t)(q.OHs * q.OWs));
-      q.div_ow = make_fastdiv((uint32_t)q.OWs);
-      for (int r = 0; r < p.R; ++r) {
-        if (((py - p.pad + r) & 1) != 0) continue;
-        for (int s2 = 0; s2 < p.S; ++s2) {
-          if (((px - p.pad + s2) & 1) != 0) continue;
-          // floor division by 2 of a possibly negative even number
-          q.tap_dy[q.ntaps] = (py - p.pad + r) / 2;
-          q.tap_dx[q.ntaps] = (px - p.pad + s2) / 2;
-          q.tap_koff[q.ntaps] = (r * p.S + s2) * p.Cin;
-          q.tap_off[q.ntaps] = (q.tap_dy[q.ntaps] * p.W + q.tap_dx[q.ntaps]) * p.in_ld * 4;
-          ++q.ntaps;
-        }
-      }
-      q.M = p.N * q.OHs * q.OWs;
-      q.alg_flops = flops_total * ((double)q.M / full_M);
-      if (q.ntaps == 0) {
-        // no contributing tap (1x1 stride-2 only): the gradient at this parity is zero
-        empty_phase = true;
-        continue;
-      }
-      q.K = q.ntaps * p.Cin;
-      phases.ph[phases.n++] = q;
-    }
+  conv_build_phases(p, phases, &empty_phase);
   if (empty_phase && !(p.flags & CONV_FLAG_ACCUM)) {
     // pixels no phase writes: clear the whole destination first (stream order keeps this ahead of the phases)
     TBN_REQUIRE(p.nseg == 1, "conv: 1x1 strided data gradient writes one segment");
@@ -1573,17 +1509,6 @@ int tbn_launch_conv(ConvP p, int rowmode, int mt, int nt, hipStream_t st, const 
     }
   }
   if (phases.n == 0) return TBN_OK;
-  // longest workgroups first: a phase's K is (its taps) x Cin -- 1, 2, 2 and 4 taps for a 3x3 / stride-2 layer -- and the
-  // dispatcher hands out workgroups in block order, so with the 4-tap phase LAST (parity order) its 4x longer workgroups
-  // started when the others were nearly done and ran the launch's tail alone
-  static const int lpt = tbn_env_int("TBN_LPT", 1, 0, 1);   // A/B runs: 0 = parity order
-  for (int a = 0; a < phases.n && lpt; ++a)
-    for (int b = a + 1; b < phases.n; ++b)
-      if (phases.ph[b].K > phases.ph[a].K) {
-        const ConvP t = phases.ph[a];
-        phases.ph[a] = phases.ph[b];
-        phases.ph[b] = t;
-      }
   // one tile shape for all phases (picked on the largest one), one launch
   int pmt = mt, pnt = nt;
   if (pmt <= 0 || pnt <= 0) {
@@ -1592,14 +1517,13 @@ int tbn_launch_conv(ConvP p, int rowmode, int mt, int nt, hipStream_t st, const 
       if (phases.ph[i].M > phases.ph[big].M) big = i;
     tbn_conv_pick_tile(phases.ph[big].M, p.Cout, phases.ph[big].K, &pmt, &pnt);
   }
-  const int stages = (p.stages == 1 || p.stages == 2) ? p.stages : ((pmt == 1) ? 2 : 1);
+  const int stages = conv_stages(p.stages, pmt);
   phases.blk0[0] = 0;
   int red_rows = p.red_row0;
   for (int i = 0; i < phases.n; ++i) {
     ConvP& q = phases.ph[i];
     q.stages = stages;
-    q.tiles_m = cdiv(q.M, 128 * pmt);
-    q.tiles_n = cdiv(q.Cout, 32 * pnt);
+    conv_set_tiles(q, 128, pmt, pnt);
     q.red_row0 = red_rows;      // the phases of one layer append their M tiles to the same partial buffers
     red_rows += q.tiles_m;
     phases.blk0[i + 1] = phases.blk0[i] + q.tiles_m * q.tiles_n;
@@ -1607,38 +1531,21 @@ int tbn_launch_conv(ConvP p, int rowmode, int mt, int nt, hipStream_t st, const 
   {
     char nm[64];
     snprintf(nm, sizeof(nm), "conv_igemm_phases_kernel<%d, %d, %d%s>", pmt, pnt, stages, p.nred > 0 ? ", true" : "");
-    tbn_prof_begin(nm, flops_total, st, conv_alg_bytes(p, 0));
+    tbn_prof_begin(nm, p.alg_flops, st, conv_alg_bytes(p, 0));
   }
-  static thread_local RiderP prd;
-  if (rider != nullptr)
-    prd = *rider;
-  else
-    memset(&prd, 0, sizeof(prd));
+  RiderP& prd = rider_arg(rider);
   const int pgrid = tbn_rider_place(&prd, phases.blk0[phases.n]);
-#define TBN_PLAUNCH(MTv, NTv, STv, REDv) \
-  TBN_LAUNCH((conv_igemm_phases_kernel<MTv, NTv, STv, REDv>), dim3(pgrid), dim3(256), 0, st, phases, prd)
-#define TBN_PCASE(MTv, NTv)                          \
-  if (pmt == MTv && pnt == NTv) {                    \
-    if (stages == 2) {                               \
-      if (p.nred > 0)                                \
-        TBN_PLAUNCH(MTv, NTv, 2, true);              \
-      else                                           \
-        TBN_PLAUNCH(MTv, NTv, 2, false);             \
-    } else {                                         \
-      if (p.nred > 0)                                \
-        TBN_PLAUNCH(MTv, NTv, 1, true);              \
-      else                                           \
-        TBN_PLAUNCH(MTv, NTv, 1, false);             \
-    }                                                \
-  } else
-  TBN_PCASE(1, 1) TBN_PCASE(1, 2) TBN_PCASE(1, 3) TBN_PCASE(1, 4) TBN_PCASE(2, 1) TBN_PCASE(2, 2) TBN_PCASE(2, 3)
-  TBN_PCASE(2, 4) {
-    tbn_set_error("conv: unsupported tile %dx%d", pmt, pnt);
-    return TBN_ERR_UNSUPPORTED;
-  }
-#undef TBN_PCASE
-#undef TBN_PLAUNCH
+  const int rc = with_tile<2, 4>(pmt, pnt, [&](auto MT, auto NT) {
+    auto go = [&](auto STG, auto RED) {
+      TBN_LAUNCH((conv_igemm_phases_kernel<MT, NT, STG, RED>), dim3(pgrid), dim3(256), 0, st, phases, prd);
+      return TBN_OK;
+    };
+    using std::integral_constant;
+    if (stages == 2) return p.nred > 0 ? go(integral_constant<int, 2>{}, std::true_type{}) : go(integral_constant<int, 2>{}, std::false_type{});
+    return p.nred > 0 ? go(integral_constant<int, 1>{}, std::true_type{}) : go(integral_constant<int, 1>{}, std::false_type{});
+  });
   tbn_prof_end(st);
+  if (rc != TBN_OK) return rc;
   TBN_CHECK_LAUNCH("conv_igemm_phases");
   return TBN_OK;
 }
@@ -1670,15 +1577,9 @@ __global__ __launch_bounds__(256) void conv_pair_halo_kernel(ConvPair q, RiderP 
 template <int MT, int NT, int EPI, bool RED>
 static int launch_pair_v(const ConvPair& q, const RiderP& rd, int blocks, int variant, size_t lds_bytes, hipStream_t st) {
   if (variant == 0) {   // LDS-halo members
-    static size_t allowed = 64 * 1024;
-    if (lds_bytes > allowed) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pair_halo_kernel<MT, NT, EPI, RED>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-        tbn_set_error("conv_pair: cannot raise the dynamic LDS limit");
-        return TBN_ERR_LAUNCH;
-      }
-      allowed = 160 * 1024;
-    }
+    static size_t allowed = TBN_DYN_LDS_DEFAULT;   // per instantiation
+    const int rc = tbn_raise_dyn_lds(reinterpret_cast<const void*>(&conv_pair_halo_kernel<MT, NT, EPI, RED>), lds_bytes, allowed, "conv_pair");
+    if (rc != TBN_OK) return rc;
     TBN_LAUNCH((conv_pair_halo_kernel<MT, NT, EPI, RED>), dim3(blocks), dim3(256), lds_bytes, st, q, rd);
   } else if (variant == 2) {
     TBN_LAUNCH((conv_pair_igemm_kernel<MT, NT, EPI, 2, RED>), dim3(blocks), dim3(256), 0, st, q, rd);
@@ -1692,15 +1593,11 @@ static int launch_pair_v(const ConvPair& q, const RiderP& rd, int blocks, int va
 // segments on both or on neither.
 int tbn_launch_conv_pair(ConvP a, ConvP b, int variant, int mt, int nt, hipStream_t st, const RiderP* rider) {
   static thread_local ConvPair q;
-  static thread_local RiderP rd;
   if ((a.flags | b.flags) & (CONV_FLAG_BF16X6 | CONV_FLAG_BF16X3 | CONV_FLAG_BF16X_PLANES)) {
     tbn_set_error("conv_pair: the bf16x kernels (flags 32 / 64, weight planes 128) are single launches");
     return TBN_ERR_UNSUPPORTED;
   }
-  if (rider != nullptr)
-    rd = *rider;
-  else
-    memset(&rd, 0, sizeof(rd));
+  RiderP& rd = rider_arg(rider);
   int sa = 0, sb = 0;
   int rc = conv_prepare(a, 0, &sa);
   if (rc != TBN_OK) return rc;
@@ -1716,17 +1613,13 @@ int tbn_launch_conv_pair(ConvP a, ConvP b, int variant, int mt, int nt, hipStrea
     TBN_REQUIRE(la > 0 && lb > 0 && la <= 160 * 1024 && lb <= 160 * 1024, "conv_pair: a member is not an LDS-halo shape");
     lds_bytes = la > lb ? la : lb;
   }
-  // the member with the longer K loop first: its workgroups are the long ones, and the dispatcher hands out workgroups in
-  // block order (a launch should not end with the long workgroups of the second member running alone)
   ConvP* ms[2] = {&a, &b};
-  static const int lpt = tbn_env_int("TBN_LPT", 1, 0, 1);   // A/B runs: 0 = caller's order
-  if (b.K > a.K && lpt) {
+  if (b.K > a.K && conv_longest_first()) {   // the member with the longer K loop first
     ms[0] = &b;
     ms[1] = &a;
   }
   for (int i = 0; i < 2; ++i) {
-    ms[i]->tiles_m = cdiv(ms[i]->M, 128 * mt);
-    ms[i]->tiles_n = cdiv(ms[i]->Cout, 32 * nt);
+    conv_set_tiles(*ms[i], 128, mt, nt);
     ms[i]->stages = variant == 2 ? 2 : 1;
     ms[i]->halo = variant == 0 ? 1 : 0;
     q.m[i] = *ms[i];
@@ -1758,6 +1651,20 @@ static void launch_wgrad(const WgradP& p, int blocks, hipStream_t st) {
   // (clamped to what still launches: 64 KB of dynamic LDS minus the kernel's 34 KB of static LDS)
   static const int pad = tbn_env_int("TBN_WGRAD_LDS_PAD", 0, 0, 64 * 1024 - 36 * 1024);
   TBN_LAUNCH((conv_wgrad_kernel<MT, NT, MODE>), dim3(blocks), dim3(256), (MT == 2 && NT == 2) ? pad : 0, st, p);
+}
+
+// f(integral_constant<int, MT>, integral_constant<int, NT>) for the weight-gradient tile (mt, nt): {1, 2, 3, 5} x {1, 2, 3}
+// without (5, 3), which does not fit the register file; any other tile is refused (I walks the admitted tiles in row order)
+template <int I = 0, class F>
+static int with_wgrad_tile(int mt, int nt, F&& f) {
+  if constexpr (I == 11) {
+    tbn_set_error("wgrad: unsupported tile");
+    return TBN_ERR_UNSUPPORTED;
+  } else {
+    constexpr int MT = I / 3 == 3 ? 5 : I / 3 + 1, NT = I % 3 + 1;
+    if (mt == MT && nt == NT) return f(std::integral_constant<int, MT>{}, std::integral_constant<int, NT>{});
+    return with_wgrad_tile<I + 1>(mt, nt, f);
+  }
 }
 
 // 32-column sub-tiles per workgroup along one dimension: 3 for 96 (and other odd multiples of 96), else 2 when the
@@ -1899,22 +1806,17 @@ int tbn_launch_wgrad(WgradP p, int rowmode, float* dw, float* workspace, hipStre
     tbn_prof_begin(nm, p.alg_flops, st,
                    4.0 * ((double)p.M * p.Cout + (double)p.N * p.H * p.W * (rowmode ? p.cp : p.Cin) + (double)p.Cout * p.K));
   }
-#define TBN_CASE(MTv, NTv)                                          \
-  if (mt == MTv && nt == NTv) {                                     \
-    if (mode == 1)                                                  \
-      launch_wgrad<MTv, NTv, 1>(p, blocks, st);                     \
-    else if (mode == 2)                                             \
-      launch_wgrad<MTv, NTv, 2>(p, blocks, st);                     \
-    else                                                            \
-      launch_wgrad<MTv, NTv, 0>(p, blocks, st);                     \
-  } else
-  TBN_CASE(1, 1) TBN_CASE(1, 2) TBN_CASE(1, 3) TBN_CASE(2, 1) TBN_CASE(2, 2) TBN_CASE(2, 3) TBN_CASE(3, 1) TBN_CASE(3, 2)
-  TBN_CASE(3, 3) TBN_CASE(5, 1) TBN_CASE(5, 2) {
-    tbn_set_error("wgrad: unsupported tile");
-    return TBN_ERR_UNSUPPORTED;
-  }
-#undef TBN_CASE
+  const int rc = with_wgrad_tile(mt, nt, [&](auto MT, auto NT) {
+    if (mode == 1)
+      launch_wgrad<MT, NT, 1>(p, blocks, st);
+    else if (mode == 2)
+      launch_wgrad<MT, NT, 2>(p, blocks, st);
+    else
+      launch_wgrad<MT, NT, 0>(p, blocks, st);
+    return TBN_OK;
+  });
   tbn_prof_end(st);
+  if (rc != TBN_OK) return rc;
   TBN_CHECK_LAUNCH("conv_wgrad");
   if (splits > 1) {
     const size_t n = (size_t)p.Cout * p.K;

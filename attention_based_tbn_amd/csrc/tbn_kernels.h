@@ -179,6 +179,25 @@ static int with_tile(int mt, int nt, F&& f) {
   }
 }
 
+// output tiles of a conv GEMM launch: `tile_rows` x mt rows (128; 32 for the split-K tile kernel) by 32 x nt columns
+static inline void conv_set_tiles(ConvP& p, int tile_rows, int mt, int nt) {
+  p.tiles_m = cdiv(p.M, tile_rows * mt);
+  p.tiles_n = cdiv(p.Cout, 32 * nt);
+}
+// A kernel with dynamic LDS may use 64 KB of it until the limit of THAT instantiation is raised (to the CU's 160 KB).
+// Raises it once, when a launch first needs more: `allowed` is a `static size_t allowed = TBN_DYN_LDS_DEFAULT` that the
+// launcher keeps per instantiation; `who` prefixes the error message.
+enum { TBN_DYN_LDS_DEFAULT = 64 * 1024, TBN_DYN_LDS_MAX = 160 * 1024 };
+static inline int tbn_raise_dyn_lds(const void* kernel, size_t need, size_t& allowed, const char* who) {
+  if (need <= allowed) return TBN_OK;
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TBN_DYN_LDS_MAX) != hipSuccess) {
+    tbn_set_error("%s: cannot raise the dynamic LDS limit", who);
+    return TBN_ERR_LAUNCH;
+  }
+  allowed = TBN_DYN_LDS_MAX;
+  return TBN_OK;
+}
+
 // conv_bf16x.hip: eval-forward convolutions on the bf16 MFMA (np = 6 | 3 plane products); tbn_launch_conv routes a launch
 // whose flags carry CONV_FLAG_BF16X6 / _BF16X3 there and refuses what those kernels do not cover.
 // THE SHAPE RULE -- which layer runs on which split-bf16 kernel, a function of the layer alone.  Everything that has to

@@ -295,6 +295,45 @@ def test_wgrad_many_splitk_slabs_deterministic():
     assert relerr(outs[0].permute(0, 3, 1, 2), wr.grad) < TOL
 
 
+_WGRAD_TILE_REF = {}
+
+
+def _wgrad_tile_ref(k, p):
+    """dy, x (widest channel counts, sliced per case) and the float64 weight gradient of the full problem, once per filter:
+    dW[co][ci] is a sum over pixels alone, so the gradient of a (cout, cin) sub-problem is a slice of it"""
+    if (k, p) not in _WGRAD_TILE_REF:
+        x = torch.randn(2, 96, 6, 6, generator=g(11))
+        dy = torch.randn(2, 160, 6, 6, generator=g(12))
+        wr = torch.zeros(160, 96, k, k, dtype=torch.float64, requires_grad=True)
+        F.conv2d(x.double(), wr, None, stride=1, padding=p).backward(dy.double())
+        _WGRAD_TILE_REF[(k, p)] = (x, dy, wr.grad.detach())
+    return _WGRAD_TILE_REF[(k, p)]
+
+
+@pytest.mark.parametrize("ksp", [(3, 1, 1), (1, 1, 0)])
+@pytest.mark.parametrize("cin", [32, 64, 96])
+@pytest.mark.parametrize("cout", [32, 64, 96, 160])
+def test_wgrad_every_heuristic_tile(cout, cin, ksp):
+    """tbn_conv2d_wgrad against F.conv2d's weight gradient in float64 on every tile the weight-gradient dispatcher admits.
+    n = 2 on a 6 x 6 map: M = 72 rows = one ragged 64-row step per wave (rows >= M are left to the hardware range check).
+    The heuristic tile (mt, nt) = 32-column sub-tiles of Cout / Cin per workgroup (pick_wtile, the Cout == 160 rule):
+        cout  32: cin 32 -> (1, 1)   cin 64 -> (1, 2)   cin 96 -> (1, 3)
+        cout  64: cin 32 -> (2, 1)   cin 64 -> (2, 2)   cin 96 -> (2, 3)
+        cout  96: cin 32 -> (3, 1)   cin 64 -> (3, 2)   cin 96 -> (3, 3)
+        cout 160: cin 32 -> (5, 1)   cin 64 -> (5, 2)   cin 96 -> (5, 2), the fall-back of (5, 3)
+    3x3 / stride 1 / pad 1 runs kernel mode 0 (general), 1x1 / stride 1 / pad 0 mode 2 (pointwise).  The kernel's tile
+    extent is a template argument and the tile counts come from the run-time tile: a wrong mapping is a wrong result."""
+    k, s, p = ksp
+    n, h, w = 2, 6, 6
+    x, dy, ref = _wgrad_tile_ref(k, p)
+    xd, dyd = nhwc(x[:, :cin]).to(DEV), nhwc(dy[:, :cout]).to(DEV)
+    nws = lib().tbn_conv2d_wgrad_workspace_floats(n, h, w, cin, cout, k, s, p)
+    ws = torch.empty(max(nws, 1), device=DEV)
+    dw = torch.full((cout, k, k, cin), float("nan"), device=DEV)
+    call("tbn_conv2d_wgrad", ptr(dyd), cout, ptr(xd), cin, ptr(dw), n, h, w, cin, cout, k, s, p, ptr(ws), st())
+    assert relerr(dw.permute(0, 3, 1, 2), ref[:cout, :cin]) < TOL
+
+
 @pytest.mark.parametrize("p_c", [(2 * 14 * 14, 96), (3 * 7 * 5, 384), (1000, 32), (48, 704), (48, 128), (192, 192),
                                  (5000, 736)])
 def test_bn_relu_train_fwd_bwd(p_c):
