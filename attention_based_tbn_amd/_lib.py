@@ -149,6 +149,10 @@ SIGNATURES = {
     "tbn_stft_twiddle_floats": (c_sz, []),
     "tbn_stft_make_twiddle": (c_i, [c_fp]),
     "tbn_stft_logpower": (c_i, [c_fp, c_i, c_i, c_fp, c_fp, c_f, c_fp]),
+    # reference core/dataset/dataset.py:421-459 (window cut) + :461-510 (stft / logms) in one entry
+    "tbn_stft_windows": (c_i, [c_fp, c_fp, c_i, c_i, c_fp, c_fp, c_f, c_i, c_fp, c_fp, c_fp]),
+    # reference core/dataset/dataset.py:534-575 (prior_type "loud")
+    "tbn_attn_prior_loud": (c_i, [c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp]),
     "tbn_opt_num_partials": (c_i, [C.POINTER(OptTensor), c_i]),
     "tbn_opt_sqnorm_partials": (c_i, [C.POINTER(OptTensor), c_i, c_fp, c_fp]),
     "tbn_opt_clip_coef": (c_i, [c_fp, c_i, c_f, c_fp, c_fp, c_fp]),

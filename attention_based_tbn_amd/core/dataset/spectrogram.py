@@ -7,6 +7,9 @@ import torch
 from ..._lib import call, lib, ptr, stream_ptr, TbnHipError
 
 
+STFT_LOGPOWER, STFT_LOGMEL = 0, 1      # include/tbn_hip.h TBN_STFT_*: the `mode` of tbn_stft_windows
+
+
 def trim_audio_window(num_samples, frame_idx, audio_length, sampling_rate=24000, vid_fps=60):
     """(start, length) of the `audio_length` s window centred on frame_idx / fps, clamped like the reference
     (dataset.py:439-451): `sample = aud_sample[start : start + length]`.
@@ -64,7 +67,8 @@ def mel_filterbank(sr=24000, n_fft=511, n_mels=128):
 class Spectrogram:
     """`spec = Spectrogram()(wave)`: wave (nseg, L) float32 on the GPU -> (nseg, 256, 1+(L-1)//120) log-power STFT
     (`spec_type="stft"`, the reference default) or (nseg, 128, T) log-mel dB (`spec_type="logms"`,
-    dataset.py:496-506: librosa melspectrogram + power_to_db(ref=max) of each segment)."""
+    dataset.py:496-506: librosa melspectrogram + power_to_db(ref=max) of each segment; two HIP launches, no torch op).
+    `AudioSegments` (audio.py) runs the same code on windows of untrimmed clips through `windows()`."""
 
     def __init__(self, eps=1e-6, spec_type="stft", sampling_rate=24000):
         if spec_type not in ("stft", "logms"):
@@ -88,26 +92,34 @@ class Spectrogram:
             self._tw[device] = torch.from_numpy(host).to(device)
         return self._tw[device]
 
+    def windows(self, window_ptrs, wave, nseg, L, device):
+        """The one code path of both representations: nseg windows of L samples, either `window_ptrs` (a device int64
+        tensor of nseg window addresses inside untrimmed clips, `core/dataset/audio.py`) or `wave`, a contiguous
+        (nseg, L) batch -- the special case "window s starts at wave + s * L"."""
+        if L < 1:       # librosa 0.7.2 (reference dataset.py:487-495) rejects it too: "Input is too short" (util.frame)
+            raise ValueError("Spectrogram: empty audio sample (a clip shorter than audio_length, reference dataset.py:441-451)")
+        W = 1 + (L - 1) // 120
+        tw = self._twiddle(device)
+        if self.spec_type == "stft":
+            spec = torch.empty(nseg, 256, W, device=device, dtype=torch.float32)
+            if window_ptrs is None:      # same kernel, same bits; this entry's launch stays outside the library profiler,
+                                         # whose entries bench.py sums up as the conv stage
+                call("tbn_stft_logpower", ptr(wave), nseg, L, ptr(tw), ptr(spec), float(self.eps), stream_ptr())
+            else:
+                call("tbn_stft_windows", ptr(window_ptrs), 0, nseg, L, ptr(tw), ptr(spec), float(self.eps), STFT_LOGPOWER, 0, 0,
+                     stream_ptr())
+            return spec
+        # log-mel: the STFT kernel writes |X|^2, one more kernel projects it onto the mel basis and converts to dB relative
+        # to each segment's own maximum (librosa.power_to_db(S, ref=np.max), top_db = 80)
+        power = torch.empty(nseg, 256, W, device=device, dtype=torch.float32)
+        spec = torch.empty(nseg, 128, W, device=device, dtype=torch.float32)
+        call("tbn_stft_windows", ptr(window_ptrs), ptr(wave), nseg, L, ptr(tw), ptr(spec), 0.0, STFT_LOGMEL,
+             ptr(self._melbasis(device)), ptr(power), stream_ptr())
+        return spec
+
     def __call__(self, wave):
         if not wave.is_cuda:
             raise TbnHipError("Spectrogram: the STFT kernel needs the waveform on the GPU (no CPU fallback)")
         wave = wave.contiguous().float()
         nseg, L = wave.shape
-        if L < 1:       # librosa 0.7.2 (reference dataset.py:487-495) rejects it too: "Input is too short" (util.frame)
-            raise ValueError("Spectrogram: empty audio sample (a clip shorter than audio_length, reference dataset.py:441-451)")
-        W = 1 + (L - 1) // 120
-        spec = torch.empty(nseg, 256, W, device=wave.device, dtype=torch.float32)
-        eps = float(self.eps) if self.spec_type == "stft" else 0.0
-        call("tbn_stft_logpower", ptr(wave), nseg, L, ptr(self._twiddle(wave.device)), ptr(spec), eps, stream_ptr())
-        if self.spec_type == "stft":
-            return spec
-        # log-mel: the 128 x 256 mel projection of the power spectrum is a (tiny) HIP GEMM, the dB conversion is
-        # relative to each segment's own maximum (librosa.power_to_db(S, ref=np.max), top_db = 80)
-        from ... import ops
-        power = torch.exp(spec)                                   # kernel returns log(power + 0)
-        rows = power.permute(0, 2, 1).reshape(nseg * W, 256)       # (segment, frame) rows x frequency
-        mel = ops.linear(rows, self._melbasis(wave.device), None).reshape(nseg, W, 128).permute(0, 2, 1)
-        amin = 1e-10
-        ref = mel.amax(dim=(1, 2), keepdim=True)
-        db = 10.0 * torch.log10(torch.clamp(mel, min=amin)) - 10.0 * torch.log10(torch.clamp(ref, min=amin))
-        return torch.maximum(db, db.amax(dim=(1, 2), keepdim=True) - 80.0).contiguous()
+        return self.windows(None, wave, nseg, L, wave.device)

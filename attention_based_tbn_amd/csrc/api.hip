@@ -272,7 +272,7 @@ extern "C" {
 
 int tbn_version(void) { return 102 | (TBN_EXPERIMENT ? 0x10000 : 0); }
 
-int tbn_capabilities(void) { return TBN_CAP_CONV_BF16X | TBN_CAP_CONV_BF16X_PLANES | TBN_CAP_FRAMES_CROPS | TBN_CAP_ATTN_GENERAL | TBN_CAP_ATTN_REG; }
+int tbn_capabilities(void) { return TBN_CAP_CONV_BF16X | TBN_CAP_CONV_BF16X_PLANES | TBN_CAP_FRAMES_CROPS | TBN_CAP_ATTN_GENERAL | TBN_CAP_ATTN_REG | TBN_CAP_AUDIO_LAYER; }
 
 int tbn_diag_mfma_burst(float* sink, int workgroups, int iters, double* flops, void* stream) {
   TBN_REQUIRE(sink != nullptr && workgroups > 0 && workgroups <= 65536 && iters > 0, "diag_mfma_burst: bad argument");

@@ -24,10 +24,14 @@
 //     feeds four MFMAs; accumulators put frames on lanes -> the (256, W) freq-major rows are written 128 B contiguous;
 //   * log(|X|^2 + eps) with the hardware logarithm (v_log_f32, 1 ulp): 3 VALU instructions per output instead of the
 //     ~20 of logf's software path (32 outputs per lane: the epilogue was 8 % of the kernel).
+//
+// The rest of the audio data layer lives here too (reference dataset.py:421-575): the audio window cut inside the launch
+// (tbn_stft_windows: a table of window addresses instead of a staged batch), the log-mel representation (the same kernel
+// writing |X|^2 + mel_db_kernel) and the "loud" attention prior (attn_prior_loud_kernel).
 #include <cmath>
 #include <cstring>
 
-#include "tbn_common.h"
+#include "tbn_kernels.h"
 #include "../../include/tbn_hip.h"
 
 #define STFT_TAPS 240
@@ -106,6 +110,8 @@ __device__ __forceinline__ void stft_ring_start(const float* __restrict__ tw, un
 // log(|X|^2 + eps) of a wave's 32 bins x 64 frames -> (256, W) freq-major rows of the segment, 128 B contiguous per store;
 // |X|^2 + eps >= 1e-6 is a normal number: v_log_f32 (log2, 1 ulp) * ln 2.  Raw-buffer stores: frames >= W get an offset
 // outside the segment's 256 x W floats and are dropped by the range check (no branch per store, 32-bit offsets).
+// POWER (the log-mel path, dataset.py:496-506): the plain power re^2 + im^2 instead, no log / exp round trip.
+template <bool POWER>
 __device__ __forceinline__ void stft_store(float* __restrict__ o, int W, int b0, int t0, int lrow, int lhalf, float eps,
                                            const StftAcc& a) {
   const float ln2 = 0.6931471805599453f;
@@ -130,14 +136,25 @@ __device__ __forceinline__ void stft_store(float* __restrict__ o, int W, int b0,
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const int soff = (8 * (e >> 2) + (e & 3)) * W * 4;   // the bin row of accumulator element e (wave-uniform)
+    if (POWER) {
+      stft_buffer_store_f32(fmaf(a.re0[e], a.re0[e], a.im0[e] * a.im0[e]), rs, oa + soff, 0, 0);
+      stft_buffer_store_f32(fmaf(a.re1[e], a.re1[e], a.im1[e] * a.im1[e]), rs, ob + soff, 0, 0);
+      continue;
+    }
     stft_buffer_store_f32(__builtin_amdgcn_logf(fmaf(a.re0[e], a.re0[e], fmaf(a.im0[e], a.im0[e], eps))) * ln2, rs, oa + soff, 0, 0);
     stft_buffer_store_f32(__builtin_amdgcn_logf(fmaf(a.re1[e], a.re1[e], fmaf(a.im1[e], a.im1[e], eps))) * ln2, rs, ob + soff, 0, 0);
   }
 }
 
 // a segment's samples as a raw buffer: offsets in front of sample 0 (negative -> huge unsigned) and behind sample len - 1
-// are out of range, per dword -> zeros (librosa's centre padding, reference dataset.py:487-489)
-__device__ __forceinline__ stft_i32x4 stft_segment_buffer(const float* wave, int seg, int len) {
+// are out of range, per dword -> zeros (librosa's centre padding, reference dataset.py:487-489).  The base is row `seg` of a
+// contiguous (nseg, len) batch, or -- `windows` non-null -- entry `seg` of a table of window addresses into untrimmed clips
+// (the trim of dataset.py:439-451 as a pointer): the range is the WINDOW's len samples either way, so the padding in front
+// of and behind a window is zeros, never the clip's neighbouring audio (librosa pads the trimmed sample).  A window's
+// address is only 4-byte aligned; offsets are still multiples of 16 B relative to it, and a multi-dword buffer load needs
+// dword alignment only (its range check is per dword, relative to the base) -- a 16-B group that straddles a cache line is
+// two requests, nothing else.
+__device__ __forceinline__ stft_i32x4 stft_segment_buffer(const float* wave, const float* const* windows, int seg, int len) {
   union {
     stft_i32x4 v;
     struct {
@@ -145,7 +162,7 @@ __device__ __forceinline__ stft_i32x4 stft_segment_buffer(const float* wave, int
       unsigned range, cfg;
     } d;
   } u;
-  u.d.p = wave + (size_t)seg * len;
+  u.d.p = windows ? windows[seg] : wave + (size_t)seg * len;
   u.d.range = (unsigned)len * 4u;
   u.d.cfg = 0x00020000u;
   stft_i32x4 rs;
@@ -156,8 +173,10 @@ __device__ __forceinline__ stft_i32x4 stft_segment_buffer(const float* wave, int
   return rs;
 }
 
-__global__ __launch_bounds__(256) void stft_logpower_kernel(const float* __restrict__ wave, int len, int W,
-                                                            const float* __restrict__ tw, float* __restrict__ spec, float eps) {
+template <bool POWER>
+__global__ __launch_bounds__(256) void stft_logpower_kernel(const float* __restrict__ wave, const float* const* __restrict__ windows,
+                                                            int len, int W, const float* __restrict__ tw,
+                                                            float* __restrict__ spec, float eps) {
   __shared__ __attribute__((aligned(16))) float fr[(STFT_FR + 1) * STFT_PITCH];
   const int seg = blockIdx.y, t0 = blockIdx.x * STFT_FR;
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -167,7 +186,7 @@ __global__ __launch_bounds__(256) void stft_logpower_kernel(const float* __restr
   StftRing<3> tr;
   stft_ring_start(tw, lane_byte, tr);
   {
-    const stft_i32x4 rs = stft_segment_buffer(wave, seg, len);
+    const stft_i32x4 rs = stft_segment_buffer(wave, windows, seg, len);
     const int g0 = (t0 - 1) * 120;     // first staged sample (a multiple of 4: a 16-B group never straddles sample 0)
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
@@ -188,7 +207,155 @@ __global__ __launch_bounds__(256) void stft_logpower_kernel(const float* __restr
   fa[0] = *reinterpret_cast<const float4*>(&fr[off]);
   fb[0] = *reinterpret_cast<const float4*>(&fr[off + 32 * STFT_PITCH]);
   stft_groups<3, 0, STFT_KG>(fr, off, tw, lane_byte, tr, fa, fb, a);
-  stft_store(spec + (size_t)seg * STFT_BINS * W, W, b0, t0, lrow, lhalf, eps, a);
+  stft_store<POWER>(spec + (size_t)seg * STFT_BINS * W, W, b0, t0, lrow, lhalf, eps, a);
+}
+
+// ---- log-mel (spec_type "logms", reference dataset.py:496-506: librosa melspectrogram + power_to_db(ref = np.max)) ----
+// One workgroup per segment: mel = basis (128 x 256) . power (256 x W), then 10 log10(max(amin, mel)) - 10 log10(max(amin,
+// max mel)), floored at -80 dB.  A Slaney mel filter is a triangle over a handful of neighbouring bins (about 500 non-zeros
+// in the 128 x 256 basis), so each output sums only its filter's [first, last] non-zero bin span, found here from the
+// caller's basis: 2 x ~500 x W FLOP per segment instead of the dense GEMM's 2 x 32768 x W -- VALU work, no MFMA needed.
+// Pass 1 leaves the mel power in `out` and reduces the segment maximum (each thread its own items in index order, then a
+// shuffle tree and 8 wave values read in order: no float atomics, and max is exact, so the same input gives the same bits);
+// pass 2 has each thread turn exactly the elements it wrote itself into dB.  The dB maximum of a segment is 0 by
+// construction (its largest element and `ref` go through the same log10f and the same rounded product: no fused
+// multiply-subtract in the conversion, fp contract off), so the top_db clip is max(db, -80) and silence is exactly 0 dB.
+#define MEL_N 128
+#define MEL_THREADS 512
+#define MEL_G 8   // mels per work item: item = (group of 8 filters, frame), frames fastest -> coalesced power / out rows
+
+__global__ __launch_bounds__(MEL_THREADS) void mel_db_kernel(const float* __restrict__ power, const float* __restrict__ basis,
+                                                              int W, float* __restrict__ out) {
+  __shared__ int lo[MEL_N], hi[MEL_N];
+  __shared__ float wmax[MEL_THREADS / 64];
+  const int tid = threadIdx.x;
+  const float* __restrict__ P = power + (size_t)blockIdx.x * STFT_BINS * W;
+  float* O = out + (size_t)blockIdx.x * MEL_N * W;
+  if (tid < MEL_N) {
+    int l = STFT_BINS, h = 0;
+    for (int k = 0; k < STFT_BINS; ++k)
+      if (basis[tid * STFT_BINS + k] != 0.f) {
+        l = min(l, k);
+        h = k + 1;
+      }
+    lo[tid] = l;
+    hi[tid] = h;
+  }
+  __syncthreads();
+  const int items = (MEL_N / MEL_G) * W;
+  float mx = -INFINITY;
+  for (int item = tid; item < items; item += MEL_THREADS) {
+    const int mg = item / W, t = item - mg * W;
+#pragma unroll 1
+    for (int j = 0; j < MEL_G; ++j) {
+      const int m = mg * MEL_G + j;
+      float acc = 0.f;
+      for (int k = lo[m]; k < hi[m]; ++k) acc = fmaf(basis[m * STFT_BINS + k], P[k * W + t], acc);
+      O[m * W + t] = acc;
+      mx = fmaxf(mx, acc);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+  if ((tid & 63) == 0) wmax[tid >> 6] = mx;
+  __syncthreads();
+  float ref = wmax[0];
+#pragma unroll
+  for (int w = 1; w < MEL_THREADS / 64; ++w) ref = fmaxf(ref, wmax[w]);
+  {
+#pragma clang fp contract(off)
+    const float amin = 1e-10f;
+    const float ref_db = 10.0f * log10f(fmaxf(amin, ref));
+    for (int item = tid; item < items; item += MEL_THREADS) {
+      const int mg = item / W, t = item - mg * W;
+#pragma unroll 1
+      for (int j = 0; j < MEL_G; ++j) {
+        const int i = (mg * MEL_G + j) * W + t;
+        const float db = 10.0f * log10f(fmaxf(amin, O[i]));
+        O[i] = fmaxf(db - ref_db, -80.0f);
+      }
+    }
+  }
+}
+
+// ---- the "loud" attention prior (reference dataset.py:534-575, `_get_attn_weights`) ----
+// One wave per segment.  Column maxima over all F rows of the nblk * T frames that lie in full blocks of T (lanes on
+// consecutive frames: coalesced rows) -> LDS; block maxima and their arg-max, ties to the HIGHEST block index; then the
+// reference's selection among the T host-computed Gaussian values and their minimum -- no arithmetic on them.
+#define PRIOR_MAX_W 4096
+
+__global__ __launch_bounds__(64) void attn_prior_loud_kernel(const float* __restrict__ spec, int F, int W, int T,
+                                                             const float* __restrict__ gauss, float* __restrict__ out) {
+  __shared__ float col[PRIOR_MAX_W];
+  const int lane = threadIdx.x;
+  const float* __restrict__ S = spec + (size_t)blockIdx.x * F * W;
+  const int nblk = W / T, ncol = nblk * T;
+  for (int c = lane; c < ncol; c += 64) {
+    float m0 = -INFINITY, m1 = -INFINITY, m2 = -INFINITY, m3 = -INFINITY;
+    int r = 0;
+    for (; r + 4 <= F; r += 4) {
+      m0 = fmaxf(m0, S[(r + 0) * W + c]);
+      m1 = fmaxf(m1, S[(r + 1) * W + c]);
+      m2 = fmaxf(m2, S[(r + 2) * W + c]);
+      m3 = fmaxf(m3, S[(r + 3) * W + c]);
+    }
+    for (; r < F; ++r) m0 = fmaxf(m0, S[r * W + c]);
+    col[c] = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
+  }
+  __syncthreads();
+  float best = -INFINITY;
+  int loc = -1;
+  for (int b = lane; b < nblk; b += 64) {
+    float v = col[b * T];
+    for (int i = 1; i < T; ++i) v = fmaxf(v, col[b * T + i]);
+    if (loc < 0 || v >= best) {
+      best = v;
+      loc = b;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(best, off);
+    const int ol = __shfl_xor(loc, off);
+    if (ol >= 0 && (loc < 0 || ov > best || (ov == best && ol > loc))) {
+      best = ov;
+      loc = ol;
+    }
+  }
+  float gmin = gauss[0];
+  for (int i = 1; i < T; ++i) gmin = fminf(gmin, gauss[i]);
+  const int mean = T / 2;
+  const bool roll = loc <= T && (loc < mean - 2 || loc > mean + 2);
+  for (int i = lane; i < T; i += 64) {
+    float v = gauss[i];
+    if (roll) {
+      v = gauss[(((i - (loc - mean)) % T) + T) % T];            // np.roll(wts, loc - mean)
+      if (loc - 4 > 0 && i < loc - 4) v = gmin;                  // wts[:loc - 4] = min
+      if (loc + 4 < T && i >= loc + 4) v = gmin;                 // wts[loc + 4:] = min
+    }
+    out[(size_t)blockIdx.x * T + i] = v;
+  }
+}
+
+// the one STFT launch behind tbn_stft_logpower and tbn_stft_windows; `what` names the entry in error messages
+template <bool POWER>
+static int stft_launch(const char* what, const float* wave, const float* const* windows, int nseg, int len,
+                       const float* twiddle, float* spec, float eps, bool profile, hipStream_t st) {
+  const int W = 1 + (len - 1) / 120;
+  // 32-bit byte offsets inside a segment's samples and inside its 256 x W spectrogram
+  TBN_REQUIRE(nseg <= 65535 && (size_t)len * 4 < (1ull << 31) && (size_t)STFT_BINS * W * 4 < (1ull << 31),
+              "%s: too many segments / too long a waveform per call", what);
+  const dim3 grid(cdiv(W, STFT_FR), nseg, 2);
+  if (profile) {
+    tbn_prof_begin(POWER ? "stft_logpower_kernel<power>" : "stft_logpower_kernel<log>",
+                   4.0 * STFT_BINS * STFT_TAPS * (double)W * nseg, st);
+    TBN_LAUNCH(stft_logpower_kernel<POWER>, grid, dim3(256), 0, st, wave, windows, len, W, twiddle, spec, eps);
+    tbn_prof_end(st);
+  } else {
+    TBN_KLAUNCH(stft_logpower_kernel<POWER>, grid, dim3(256), 0, st, wave, windows, len, W, twiddle, spec, eps);
+  }
+  TBN_CHECK_LAUNCH(what);
+  return TBN_OK;
 }
 
 extern "C" {
@@ -215,13 +382,37 @@ int tbn_stft_make_twiddle(float* host) {
 int tbn_stft_logpower(const float* wave, int nseg, int len, const float* twiddle, float* spec, float eps,
                       void* stream) {
   TBN_REQUIRE(wave && twiddle && spec && nseg > 0 && len > 0, "stft_logpower: bad argument");
+  return stft_launch<false>("stft_logpower", wave, nullptr, nseg, len, twiddle, spec, eps, false, (hipStream_t)stream);
+}
+
+int tbn_stft_windows(const float* const* window_ptrs, const float* wave, int nseg, int len, const float* twiddle,
+                     float* out, float eps, int mode, const float* mel_basis, float* power, void* stream) {
+  TBN_REQUIRE((window_ptrs != nullptr) != (wave != nullptr), "stft_windows: give a window table or a contiguous batch, not both");
+  TBN_REQUIRE(twiddle && out && nseg > 0 && len > 0, "stft_windows: bad argument");
+  TBN_REQUIRE(mode == TBN_STFT_LOGPOWER || mode == TBN_STFT_LOGMEL, "stft_windows: unknown mode %d", mode);
+  hipStream_t st = (hipStream_t)stream;
+  if (mode == TBN_STFT_LOGPOWER)
+    return stft_launch<false>("stft_windows", wave, window_ptrs, nseg, len, twiddle, out, eps, true, st);
+  TBN_REQUIRE(mel_basis && power && power != out, "stft_windows: the log-mel mode needs the mel basis and a power workspace");
   const int W = 1 + (len - 1) / 120;
-  // 32-bit byte offsets inside a segment's samples and inside its 256 x W spectrogram
-  TBN_REQUIRE(nseg <= 65535 && (size_t)len * 4 < (1ull << 31) && (size_t)STFT_BINS * W * 4 < (1ull << 31),
-              "stft_logpower: too many segments / too long a waveform per call");
-  TBN_KLAUNCH(stft_logpower_kernel, dim3(cdiv(W, STFT_FR), nseg, 2), dim3(256), 0, (hipStream_t)stream, wave, len, W,
-                     twiddle, spec, eps);
-  TBN_CHECK_LAUNCH("stft_logpower");
+  const int rc = stft_launch<true>("stft_windows", wave, window_ptrs, nseg, len, twiddle, power, 0.f, true, st);
+  if (rc != TBN_OK) return rc;
+  tbn_prof_begin("mel_db_kernel", 0.0, st);
+  TBN_LAUNCH(mel_db_kernel, dim3(nseg), dim3(MEL_THREADS), 0, st, (const float*)power, mel_basis, W, out);
+  tbn_prof_end(st);
+  TBN_CHECK_LAUNCH("stft_windows (mel)");
+  return TBN_OK;
+}
+
+int tbn_attn_prior_loud(const float* spec, int nseg, int F, int W, int T, const float* gauss, float* out, void* stream) {
+  TBN_REQUIRE(spec && gauss && out && nseg > 0 && F > 0 && T > 0, "attn_prior_loud: bad argument");
+  TBN_REQUIRE(W >= T, "attn_prior_loud: no full block of %d frames in a spectrogram %d frames wide", T, W);
+  TBN_REQUIRE(W <= PRIOR_MAX_W && (size_t)F * W < (1ull << 31), "attn_prior_loud: spectrogram %d x %d too large", F, W);
+  hipStream_t st = (hipStream_t)stream;
+  tbn_prof_begin("attn_prior_loud_kernel", 0.0, st);
+  TBN_LAUNCH(attn_prior_loud_kernel, dim3(nseg), dim3(64), 0, st, spec, F, W, T, gauss, out);
+  tbn_prof_end(st);
+  TBN_CHECK_LAUNCH("attn_prior_loud");
   return TBN_OK;
 }
 

@@ -46,6 +46,8 @@ int tbn_version(void);
 #define TBN_CAP_ATTN_GENERAL 8
 /* bit 5: the attention-weight regularisers (tbn_attn_reg_fwd / tbn_attn_reg_bwd: prior, contrast and entropy losses) */
 #define TBN_CAP_ATTN_REG 16
+/* bit 6: the audio data layer (tbn_stft_windows: windows cut inside the STFT launch, log-mel mode; tbn_attn_prior_loud) */
+#define TBN_CAP_AUDIO_LAYER 32
 int tbn_capabilities(void);
 const char* tbn_last_error(void);
 
@@ -564,6 +566,32 @@ size_t tbn_stft_twiddle_floats(void);
 int tbn_stft_make_twiddle(float* host_buffer);
 int tbn_stft_logpower(const float* wave, int nseg, int len, const float* twiddle, float* spec, float eps,
                       void* stream);
+/* The same STFT kernel with the audio window cut inside the launch (reference core/dataset/dataset.py:421-459,
+ * `_get_audio_segment`: `sample = aud_sample[start : start + length]`, no copy here) and a choice of representation
+ * (dataset.py:461-510, `_get_spectrogram`).  Exactly one of `window_ptrs` / `wave` is non-NULL:
+ *   window_ptrs  DEVICE array of nseg device pointers, the first sample of each window inside its (untrimmed) clip; any
+ *                4-byte alignment.  Every window [ptr, ptr + len) must lie inside its clip -- the caller checks that, the
+ *                kernel reads nothing else: the centre padding in front of and behind a window is zeros from the hardware
+ *                range check, never the clip's neighbouring audio (librosa pads the trimmed sample);
+ *   wave         a contiguous (nseg, len) batch, i.e. window s starts at wave + s * len (what tbn_stft_logpower takes).
+ * mode TBN_STFT_LOGPOWER: out (nseg, 256, W) = log(|X|^2 + eps), W = 1 + (len - 1) / 120, bit-identical to
+ *   tbn_stft_logpower on the same samples; one launch; mel_basis / power are not read.
+ * mode TBN_STFT_LOGMEL (dataset.py:496-506, librosa melspectrogram + power_to_db(ref = np.max)): out (nseg, 128, W) dB =
+ *   10 log10(max(1e-10, mel)) - 10 log10(max(1e-10, max of the segment)), floored at -80; mel = mel_basis (128 x 256 floats
+ *   on the device, librosa.filters.mel) . |X|^2.  Two launches (the STFT writes |X|^2 into `power`, nseg * 256 * W floats
+ *   of workspace; one workgroup per segment projects, reduces the maximum in a fixed order and converts); eps is not used.
+ * The profiler (tbn_profile_*) counts these launches (stft_logpower_kernel<log|power>, mel_db_kernel). */
+#define TBN_STFT_LOGPOWER 0
+#define TBN_STFT_LOGMEL 1
+int tbn_stft_windows(const float* const* window_ptrs, const float* wave, int nseg, int len, const float* twiddle,
+                     float* out, float eps, int mode, const float* mel_basis, float* power, void* stream);
+/* prior_type "loud" of reference core/dataset/dataset.py:534-575 (`_get_attn_weights`) for nseg spectrograms (nseg, F, W) on
+ * the device, one launch, one wave per segment: the maxima of the W / T full blocks of T frames over all F rows (a partial
+ * last block is ignored), their arg-max `loc` (ties: the highest block index), then out (nseg, T) = the Gaussian `gauss`
+ * (T device floats, cv2.getGaussianKernel(T, 1) rounded to float32) -- as it is when loc > T or |loc - T/2| <= 2, else rolled
+ * by loc - T/2 with its minimum before index loc - 4 (if loc - 4 > 0) and from loc + 4 on (if loc + 4 < T).  A selection
+ * among the T values and their minimum, no arithmetic: bit-equal to the host function.  W >= T, W <= 4096. */
+int tbn_attn_prior_loud(const float* spec, int nseg, int F, int W, int T, const float* gauss, float* out, void* stream);
 
 /* ---- train-step shell and metrics (the steps right after the path) -- */
 /* Multi-tensor clip_grad_norm_ + SGD(momentum) of reference core/tools/train.py:82-94,190-202
