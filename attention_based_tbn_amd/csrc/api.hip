@@ -272,7 +272,7 @@ extern "C" {
 
 int tbn_version(void) { return 102 | (TBN_EXPERIMENT ? 0x10000 : 0); }
 
-int tbn_capabilities(void) { return TBN_CAP_CONV_BF16X | TBN_CAP_CONV_BF16X_PLANES | TBN_CAP_FRAMES_CROPS | TBN_CAP_ATTN_GENERAL | TBN_CAP_ATTN_REG | TBN_CAP_AUDIO_LAYER; }
+int tbn_capabilities(void) { return TBN_CAP_CONV_BF16X | TBN_CAP_CONV_BF16X_PLANES | TBN_CAP_FRAMES_CROPS | TBN_CAP_ATTN_GENERAL | TBN_CAP_ATTN_REG | TBN_CAP_AUDIO_LAYER | TBN_CAP_STEM_OPS; }
 
 int tbn_diag_mfma_burst(float* sink, int workgroups, int iters, double* flops, void* stream) {
   TBN_REQUIRE(sink != nullptr && workgroups > 0 && workgroups <= 65536 && iters > 0, "diag_mfma_burst: bad argument");
@@ -567,6 +567,153 @@ int tbn_conv2d_wgrad(const float* dout, int dout_ld, const float* in, int in_ld,
   wp.x = in;
   wp.x_ld = in_ld;
   return tbn_launch_wgrad(wp, 0, dweight, workspace, (hipStream_t)stream);
+}
+
+// ---- the 7x7 / stride 2 / pad 3 stem on its own (test / tuning aid): the launches the engine issues for conv1_7x7_s2, built
+// from stem_geom (tbn_kernels.h) as build_graph / fill_fwd / fill_wgrad build them from the plan
+// workspace regions (float offsets, 256-B aligned like the engine's): bordered image | packed weights | packed dW | split-K slabs
+struct StemWs {
+  size_t image, wpack, dwpack, wsplit, total;
+};
+static StemWs stem_ws(const StemGeom& g, int n, int cout) {
+  StemWs s;
+  size_t off = 0;
+  auto take = [&](size_t f) {
+    const size_t o = off;
+    off += (f + 63) / 64 * 64;
+    return o;
+  };
+  s.image = take((size_t)n * g.H * g.W * g.cp);
+  s.wpack = take((size_t)cout * g.K);
+  s.dwpack = take((size_t)cout * g.rows * g.kw);
+  s.wsplit = take(tbn_wgrad_workspace_floats(n * g.OH * g.OW, cout, g.rows * g.kw, 1));
+  s.total = off;
+  return s;
+}
+// the argument checks the stem entries share; `who` prefixes the message
+static int stem_args_ok(const char* who, int n, int h, int w, int cin, int cout, int layout, const void* workspace) {
+  TBN_REQUIRE(cin >= 1 && cin <= 16, "%s: cin %d outside 1..16", who, cin);
+  TBN_REQUIRE(layout >= STEM_LAYOUT_RULE && layout <= STEM_LAYOUT_ROWS, "%s: layout %d (0 = the rule, 1 = space-to-depth, 2 = row runs)",
+              who, layout);
+  TBN_REQUIRE(n >= 1 && h >= 1 && w >= 1 && h <= (1 << 15) && w <= (1 << 15), "%s: bad shape (%d frames of %dx%d)", who, n, h, w);
+  TBN_REQUIRE(cout >= 32 && cout % 32 == 0, "%s: cout %d must be a multiple of 32", who, cout);
+  const StemGeom g = stem_geom(cin, h, w, layout);
+  TBN_REQUIRE((size_t)n * g.H * g.W * g.cp * sizeof(float) < (1ull << 31), "%s: the bordered image of %d frames exceeds 2 GiB", who, n);
+  TBN_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: the workspace must be 16-B aligned", who);
+  return TBN_OK;
+}
+static int stem_repack(const StemGeom& g, const float* x_nchw, float* image, int n, int cin, int h, int w, hipStream_t st) {
+  if (g.mode == 1) return tbn_launch_nchw_to_nhwc_pad(x_nchw, image, n, cin, h, w, g.H, g.W, st);
+  return tbn_launch_nchw_to_s2d_pad(x_nchw, image, n, cin, h, w, st);
+}
+
+int tbn_stem_geometry(int cin, int h, int w, int layout, int* out8) {
+  TBN_REQUIRE(out8 != nullptr, "stem_geometry: null out");
+  TBN_TRY(stem_args_ok("stem_geometry", 1, h, w, cin, 32, layout, nullptr));
+  const StemGeom g = stem_geom(cin, h, w, layout);
+  const int v[8] = {g.mode == 1 ? STEM_LAYOUT_ROWS : STEM_LAYOUT_S2D, g.H, g.W, g.cp, g.kw, g.K, g.rows * g.kw, g.H * g.W * g.cp};
+  memcpy(out8, v, sizeof(v));
+  return TBN_OK;
+}
+
+size_t tbn_stem_workspace_floats(int cin, int h, int w, int layout, int n, int cout) {
+  if (stem_args_ok("stem_workspace_floats", n, h, w, cin, cout, layout, nullptr) != TBN_OK) return 0;
+  return stem_ws(stem_geom(cin, h, w, layout), n, cout).total;
+}
+
+int tbn_stem_conv_fwd(const float* x_nchw, const float* weight, const float* bias, float* out, int out_ld, int n, int h, int w,
+                      int cin, int cout, int layout, int epilogue, const float* scale, const float* shift, float* stat_partial,
+                      int mt, int nt, int stages, float* workspace, void* stream) {
+  TBN_REQUIRE(x_nchw && weight && out && workspace, "stem_conv_fwd: null pointer");
+  TBN_REQUIRE(epilogue >= 0 && epilogue <= 2, "stem_conv_fwd: bad epilogue");
+  TBN_REQUIRE(epilogue != CONV_EPI_STATS || stat_partial, "stem_conv_fwd: stats epilogue needs stat_partial");
+  TBN_REQUIRE(epilogue != CONV_EPI_EVAL || (scale && shift), "stem_conv_fwd: eval epilogue needs scale/shift");
+  TBN_TRY(stem_args_ok("stem_conv_fwd", n, h, w, cin, cout, layout, workspace));
+  TBN_REQUIRE(out_ld >= cout, "stem_conv_fwd: out_ld %d below cout %d", out_ld, cout);
+  TBN_REQUIRE((mt == 0 && nt == 0) || (mt >= 1 && mt <= 2 && nt >= 1 && nt <= 4), "stem_conv_fwd: tile %dx%d (mt 1..2, nt 1..4, or 0x0)", mt, nt);
+  TBN_REQUIRE(stages >= 0 && stages <= 2, "stem_conv_fwd: stages %d (0 = default, 1, 2)", stages);
+  hipStream_t st = (hipStream_t)stream;
+  const StemGeom g = stem_geom(cin, h, w, layout);
+  const StemWs ws = stem_ws(g, n, cout);
+  float* image = workspace + ws.image;
+  float* wpack = workspace + ws.wpack;
+  TBN_TRY(stem_repack(g, x_nchw, image, n, cin, h, w, st));
+  if (g.mode == 1)
+    TBN_TRY(tbn_launch_pack_stem_weight_rows(weight, wpack, cout, cin, g.kw, g.K, st));
+  else
+    TBN_TRY(tbn_launch_pack_stem_weight_s2d(weight, wpack, cout, cin, st));
+  ConvP p;
+  memset(&p, 0, sizeof(p));
+  p.in = image;
+  p.wt = wpack;
+  p.bias = bias;
+  p.scale = scale;
+  p.shift = shift;
+  p.stat_partial = stat_partial;
+  p.N = n;
+  p.H = g.H;
+  p.W = g.W;
+  p.OH = g.OH;
+  p.OW = g.OW;
+  p.Cin = g.kw;
+  p.Cout = cout;
+  p.R = g.rows;
+  p.S = 1;
+  p.stride = g.stride;
+  p.pad = g.pad;
+  p.up = 1;
+  p.M = n * g.OH * g.OW;
+  p.K = g.K;
+  p.cp = p.in_ld = g.cp;
+  p.alg_flops = 2.0 * p.M * (double)cout * 49 * cin;
+  p.mode = epilogue;
+  p.stages = stages;
+  p.nseg = 1;
+  p.seg[0].ptr = out;
+  p.seg[0].ld = out_ld;
+  p.seg[0].col_begin = 0;
+  return tbn_launch_conv(p, 1, mt, nt, st);
+}
+
+int tbn_stem_conv_wgrad(const float* dy, int dy_ld, const float* x_nchw, float* dweight, int n, int h, int w, int cin, int cout,
+                        int layout, int mt, int nt, float* workspace, void* stream) {
+  TBN_REQUIRE(dy && x_nchw && dweight && workspace, "stem_conv_wgrad: null pointer");
+  TBN_TRY(stem_args_ok("stem_conv_wgrad", n, h, w, cin, cout, layout, workspace));
+  TBN_REQUIRE(dy_ld >= cout && dy_ld % 4 == 0, "stem_conv_wgrad: dy_ld %d (at least cout, a multiple of 4)", dy_ld);
+  TBN_REQUIRE((mt == 0 && nt == 0) || (((mt >= 1 && mt <= 3) || mt == 5) && nt >= 1 && nt <= 3 && !(mt == 5 && nt == 3)),
+              "stem_conv_wgrad: tile %dx%d (mt 1 | 2 | 3 | 5, nt 1..3 without 5x3, or 0x0)", mt, nt);
+  hipStream_t st = (hipStream_t)stream;
+  const StemGeom g = stem_geom(cin, h, w, layout);
+  const StemWs ws = stem_ws(g, n, cout);
+  float* image = workspace + ws.image;
+  float* dwpack = workspace + ws.dwpack;
+  TBN_TRY(stem_repack(g, x_nchw, image, n, cin, h, w, st));
+  WgradP wp;
+  memset(&wp, 0, sizeof(wp));
+  wp.dy = dy;
+  wp.dy_ld = dy_ld;
+  wp.x = image;
+  wp.N = n;
+  wp.H = g.H;
+  wp.W = g.W;
+  wp.OH = g.OH;
+  wp.OW = g.OW;
+  wp.Cin = g.rows * g.kw;
+  wp.Cout = cout;
+  wp.R = g.rows;
+  wp.S = 1;
+  wp.taps = 1;
+  wp.stride = g.stride;
+  wp.pad = g.pad;
+  wp.M = n * g.OH * g.OW;
+  wp.cp = wp.x_ld = g.cp;
+  wp.rl = g.kw;
+  wp.mt = mt;
+  wp.nt = nt;
+  wp.alg_flops = 2.0 * wp.M * (double)cout * 49 * cin;
+  TBN_TRY(tbn_launch_wgrad(wp, 1, dwpack, workspace + ws.wsplit, st));
+  if (g.mode == 1) return tbn_launch_unpack_stem_wgrad_rows(dwpack, dweight, cout, cin, g.kw, st);
+  return tbn_launch_unpack_stem_wgrad_s2d(dwpack, dweight, cout, cin, st);
 }
 
 // ---- linear = 1x1 conv over an (m,1,1,k) "image"

@@ -141,6 +141,7 @@ int pool_out(int in, int k, int stride, int pad, bool ceil_mode) {
 
 struct tbn_backbone_plan {
   int cin0, frames, H, W;
+  // (the fields below are filled from stem_geom, tbn_kernels.h: the one statement of these numbers)
   // stem conv as executed: 4 rows / stride 1 of the zero-bordered 2x2 space-to-depth image (stem_H, stem_W, cp = 4*cin0),
   // a filter row = kw = 4 pixels * cp contiguous floats, K = 4 * kw packed (pool.hip, conv_igemm.hip ROWMODE)
   int cp, kw;
@@ -300,31 +301,19 @@ inline int tile_rows(int variant, int mt) { return (variant == 3 ? 32 : 128) * m
 // ceil-mode pass-through max pool raises)
 bool build_graph(tbn_backbone_plan* P) {
   const int cin0 = P->cin0;
-  P->cp = 4 * cin0;
-  P->kw = 4 * P->cp;
-  P->stem_rows = 4;
-  P->stem_stride = 1;
-  P->stem_pad = 0;
-  P->stem_H = (P->H + 1) / 2 + 3;
-  P->stem_W = (P->W + 1) / 2 + 3;
-  P->stem_mode = 0;
-  P->stem_K = P->stem_rows * P->kw;
   {
-    // row runs on the bordered NHWC image when that multiplies fewer K columns (flow: 512 instead of 640; RGB / audio:
-    // the same 192 / 64 -> they keep the space-to-depth form and its 16-B aligned loads)
-    const int rl = (7 * cin0 + 3) / 4 * 4, krows = (7 * rl + 31) / 32 * 32;
+    // the stem as executed: stem_geom (tbn_kernels.h) states the two layouts and the rule that picks one
     static const int use_rows = tbn_env_int("TBN_STEM_ROWS", 1, 0, 1);   // A/B runs: 0 = always s2d
-    if (krows < P->stem_K && use_rows) {
-      const int oh = (P->H + 6 - 7) / 2 + 1, ow = (P->W + 6 - 7) / 2 + 1;
-      P->stem_mode = 1;
-      P->cp = cin0;
-      P->kw = rl;
-      P->stem_rows = 7;
-      P->stem_stride = 2;
-      P->stem_H = 2 * (oh - 1) + 8;
-      P->stem_W = 2 * (ow - 1) + 8;
-      P->stem_K = krows;
-    }
+    const StemGeom sg = stem_geom(cin0, P->H, P->W, use_rows ? STEM_LAYOUT_RULE : STEM_LAYOUT_S2D);
+    P->cp = sg.cp;
+    P->kw = sg.kw;
+    P->stem_rows = sg.rows;
+    P->stem_stride = sg.stride;
+    P->stem_pad = sg.pad;
+    P->stem_H = sg.H;
+    P->stem_W = sg.W;
+    P->stem_mode = sg.mode;
+    P->stem_K = sg.K;
   }
   P->weight_floats = P->chan_floats = 0;
   const int x0 = add_buf(P, P->H, P->W, cin0);   // logical extent (the stored image is the bordered s2d form: plan_memory)

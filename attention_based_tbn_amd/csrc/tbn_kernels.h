@@ -141,6 +141,52 @@ struct WgradP {
   int ablate;             // timing ablations, honoured by -DTBN_ABLATE=1 builds only (scripts/wgrad_ablate.py)
 };
 
+// THE GEOMETRY OF THE STEM -- the 7x7 / stride 2 / pad 3 conv1 as the packed-row (ROWMODE) launches execute it, a function
+// of the input alone.  Stated here only: the engine's plan (engine.hip build_graph, layout 0) and the stem entries of the
+// C-ABI (api.hip tbn_stem_*) read it.  Two input-image layouts (pool.hip):
+//   mode 0, space-to-depth: 4 rows / stride 1 of the zero-bordered 2x2 space-to-depth image [N][ceil(H/2)+3][ceil(W/2)+3]
+//           [4*cin]; a filter row = kw = 4 pixels * cp contiguous floats, K = 4 * kw = 64 * cin;
+//   mode 1, row runs: 7 rows / stride 2 of the zero-bordered NHWC image [N][2(OH-1)+8][2(OW-1)+8][cin]; a filter row = a run
+//           of kw = 7 * cin floats rounded up to x4, K = 7 * kw rounded up to x32 (the padding meets zero weights).
+// THE LAYOUT RULE (layout 0): row runs when they multiply fewer K columns (flow: 512 instead of 640; RGB / audio: the same
+// 192 / 64 either way -- they keep the space-to-depth form and its 16-B aligned loads), i.e. from 4 input channels on.
+enum { STEM_LAYOUT_RULE = 0, STEM_LAYOUT_S2D = 1, STEM_LAYOUT_ROWS = 2 };
+struct StemGeom {
+  int mode;                // 0 space-to-depth, 1 row runs
+  int cp, kw;              // floats per pixel of the bordered image / per filter-row run
+  int rows, stride, pad;   // the conv the GEMM kernels see: `rows` runs per output pixel, image steps per output step
+  int H, W;                // bordered image
+  int K;                   // multiplied K columns of the forward GEMM (a multiple of 32)
+  int OH, OW;              // output map
+};
+static inline StemGeom stem_geom(int cin, int H, int W, int layout) {
+  StemGeom g;
+  g.OH = (H + 6 - 7) / 2 + 1;
+  g.OW = (W + 6 - 7) / 2 + 1;
+  g.pad = 0;
+  const int rl = (7 * cin + 3) / 4 * 4, krows = (7 * rl + 31) / 32 * 32;
+  if (layout == STEM_LAYOUT_ROWS || (layout == STEM_LAYOUT_RULE && krows < 64 * cin)) {
+    g.mode = 1;
+    g.cp = cin;
+    g.kw = rl;
+    g.rows = 7;
+    g.stride = 2;
+    g.H = 2 * (g.OH - 1) + 8;
+    g.W = 2 * (g.OW - 1) + 8;
+    g.K = krows;
+  } else {
+    g.mode = 0;
+    g.cp = 4 * cin;
+    g.kw = 4 * g.cp;
+    g.rows = 4;
+    g.stride = 1;
+    g.H = (H + 1) / 2 + 3;
+    g.W = (W + 1) / 2 + 3;
+    g.K = g.rows * g.kw;
+  }
+  return g;
+}
+
 // optional in-process profiler: every conv-GEMM launch gets a pair of hipEvents on its stream.  The events ride ON the
 // kernel's dispatch packet (hipExtLaunchKernelGGL: begin / end timestamps of the kernel itself, what rocprofv3's kernel
 // trace reports); rounds 1-2 recorded two separate marker packets around the launch, whose processing sat inside the

@@ -48,6 +48,8 @@ int tbn_version(void);
 #define TBN_CAP_ATTN_REG 16
 /* bit 6: the audio data layer (tbn_stft_windows: windows cut inside the STFT launch, log-mel mode; tbn_attn_prior_loud) */
 #define TBN_CAP_AUDIO_LAYER 32
+/* bit 7: the stem entries (tbn_stem_geometry / tbn_stem_workspace_floats / tbn_stem_conv_fwd / tbn_stem_conv_wgrad) */
+#define TBN_CAP_STEM_OPS 64
 int tbn_capabilities(void);
 const char* tbn_last_error(void);
 
@@ -371,6 +373,34 @@ int tbn_conv_launch_pair(const tbn_conv_desc* a, const tbn_conv_desc* b, int var
 size_t tbn_conv2d_wgrad_workspace_floats(int n, int h, int w, int cin, int cout, int ksize, int stride, int pad);
 int tbn_conv2d_wgrad(const float* dout, int dout_ld, const float* in, int in_ld, float* dweight, int n, int h, int w,
                      int cin, int cout, int ksize, int stride, int pad, float* workspace, void* stream);
+
+/* ---- the 7x7 / stride 2 / pad 3 stem on its own (test / tuning aid) -----------------------------
+ * conv1_7x7_s2 exactly as the backbone engine executes it -- the same launch sequence, built from the same statement of the
+ * geometry -- for any cin in 1..16 and any h, w >= 1 (the engine itself needs 32 x 32).  x_nchw (n, cin, h, w) contiguous;
+ * weight / dweight [cout][7][7][cin]; cout a multiple of 32 (the engine: 64).
+ * layout: 0 = the engine's rule (space-to-depth for cin <= 3, row runs from cin = 4 on), 1 = the zero-bordered 2x2
+ * space-to-depth image [n][ceil(h/2)+3][ceil(w/2)+3][4 cin] (4 filter rows of 16 cin floats, K = 64 cin), 2 = the zero-bordered
+ * NHWC "row runs" image [n][2(oh-1)+8][2(ow-1)+8][cin] (7 runs of rl = 7 cin rounded up to x4 floats, K = 7 rl rounded up to x32).
+ * Both layouts serve every cin.
+ * tbn_stem_geometry: out8 = { layout as executed (1 | 2), image height, image width, floats per image pixel, run length,
+ *   K, floats of packed weight gradient per output channel, image floats per frame }.  Host only.
+ * tbn_stem_workspace_floats: floats of `workspace` (16-B aligned, caller-owned) for n frames: bordered image + packed weights
+ *   + packed weight gradient + split-K slabs, each region 256-B aligned; 0 for arguments the entries refuse.  Host only.
+ * tbn_stem_conv_fwd: repack, pack weights, the packed-row forward GEMM.  epilogue / bias / scale / shift / stat_partial as
+ *   tbn_conv2d_fwd; tile mt in {1,2} x nt in {1..4}, or 0 x 0 = the size heuristic (statistics rows are then per 128 * mt
+ *   output rows of a tile the caller does not know: size stat_partial for mt = 1, ceil(n oh ow / 128) rows, and pre-fill it);
+ *   stages 1 | 2 (0 = default).
+ * tbn_stem_conv_wgrad: repack, the packed-row weight gradient (+ split-K reduce), unpack.  Tile mt in {1,2,3,5} x nt in
+ *   {1,2,3} without 5 x 3, or 0 x 0 = the heuristic.  Deterministic.
+ * replaces: the forward / weight gradient of conv1_7x7_s2, nn.Conv2d(cin, 64, 7, stride 2, padding 3)
+ * (bn_inception.py:75-77; cuDNN there). */
+int tbn_stem_geometry(int cin, int h, int w, int layout, int* out8);
+size_t tbn_stem_workspace_floats(int cin, int h, int w, int layout, int n, int cout);
+int tbn_stem_conv_fwd(const float* x_nchw, const float* weight, const float* bias, float* out, int out_ld, int n, int h, int w,
+                      int cin, int cout, int layout, int epilogue, const float* scale, const float* shift, float* stat_partial,
+                      int mt, int nt, int stages, float* workspace, void* stream);
+int tbn_stem_conv_wgrad(const float* dy, int dy_ld, const float* x_nchw, float* dweight, int n, int h, int w, int cin, int cout,
+                        int layout, int mt, int nt, float* workspace, void* stream);
 
 /* nn.Linear / nn.Conv1d(k=1) (model.py:337-386 Fusion/Classifier, model.py:62-67 pe.1, the MHA
  * projections attention.py:48-57): out[m][n] = x[m][:] . w[n][:] + bias[n].  k % 32 == 0. */

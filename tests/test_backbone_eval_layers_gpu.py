@@ -59,7 +59,8 @@ def _oracle_activations(o64, x):
     return convs, acts
 
 
-@pytest.mark.parametrize("cin_hw", [(3, 64, 64), (3, 97, 97), (10, 70, 129), (1, 128, 256), (3, 224, 224)])
+@pytest.mark.parametrize("cin_hw", [(3, 64, 64), (3, 97, 97), (10, 70, 129), (1, 128, 256), (3, 224, 224),
+                                    (2, 64, 64), (6, 70, 129)])   # channel counts no modality uses: the runtime-channel stem repacks
 def test_every_layer_of_the_eval_forward_vs_fp64_oracle(cin_hw):
     from oracle.bninception import BNInception as OBN
     from oracle.fill import fill_state_dict

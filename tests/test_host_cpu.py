@@ -737,6 +737,48 @@ def test_c_abi_rejects_bad_arguments_before_touching_the_gpu():
     # conv: K not a multiple of 32 (cin = 10, 3x3)
     fails(L.tbn_conv2d_fwd(bad, 10, bad, bad, bad, 64, 2, 8, 8, 10, 64, 3, 1, 1, 0, 0, None, None, None, None),
           "multiples of 32")
+    # stem entries: null pointers, channel count, cout, layout, epilogue operands, tiles
+    geo = (C.c_int * 8)()
+    fails(L.tbn_stem_geometry(3, 32, 32, 0, None), "null out")
+    fails(L.tbn_stem_geometry(0, 32, 32, 0, geo), "outside 1..16")
+    fails(L.tbn_stem_geometry(17, 32, 32, 0, geo), "outside 1..16")
+    fails(L.tbn_stem_geometry(3, 32, 32, 3, geo), "layout 3")
+    fails(L.tbn_stem_geometry(3, 0, 32, 0, geo), "bad shape")
+    assert L.tbn_stem_workspace_floats(0, 32, 32, 0, 1, 64) == 0 and L.tbn_stem_workspace_floats(3, 32, 32, 0, 1, 40) == 0
+
+    def stem_fwd(x=bad, wt=bad, out=bad, out_ld=64, n=2, h=17, w=19, cin=3, cout=64, layout=0, epi=0, scale=None, shift=None,
+                 part=None, mt=0, nt=0, stages=0, ws=bad):
+        return L.tbn_stem_conv_fwd(x, wt, None, out, out_ld, n, h, w, cin, cout, layout, epi, scale, shift, part, mt, nt, stages,
+                                   ws, None)
+
+    def stem_wgrad(dy=bad, dy_ld=64, x=bad, dw=bad, n=2, h=17, w=19, cin=3, cout=64, layout=0, mt=0, nt=0, ws=bad):
+        return L.tbn_stem_conv_wgrad(dy, dy_ld, x, dw, n, h, w, cin, cout, layout, mt, nt, ws, None)
+    for kw in (dict(x=None), dict(wt=None), dict(out=None), dict(ws=None)):
+        fails(stem_fwd(**kw), "stem_conv_fwd: null pointer")
+    for kw in (dict(dy=None), dict(x=None), dict(dw=None), dict(ws=None)):
+        fails(stem_wgrad(**kw), "stem_conv_wgrad: null pointer")
+    for f, who in ((stem_fwd, "stem_conv_fwd"), (stem_wgrad, "stem_conv_wgrad")):
+        fails(f(cin=0), who + ": cin 0 outside 1..16")
+        fails(f(cin=17), who + ": cin 17 outside 1..16")
+        fails(f(cout=40), who + ": cout 40 must be a multiple of 32")
+        fails(f(layout=3), who + ": layout 3")
+        fails(f(layout=-1), who + ": layout -1")
+        fails(f(h=0), who + ": bad shape")
+        fails(f(n=0), who + ": bad shape")
+        fails(f(ws=bad + 4), who + ": the workspace must be 16-B aligned")
+        fails(f(n=1 << 20, h=224, w=224), "exceeds 2 GiB")
+    fails(stem_fwd(epi=1), "stats epilogue needs stat_partial")
+    fails(stem_fwd(epi=2), "eval epilogue needs scale/shift")
+    fails(stem_fwd(epi=2, scale=bad), "eval epilogue needs scale/shift")
+    fails(stem_fwd(epi=3), "bad epilogue")
+    fails(stem_fwd(out_ld=32), "out_ld 32 below cout 64")
+    fails(stem_fwd(mt=3, nt=1), "tile 3x1")
+    fails(stem_fwd(mt=1, nt=0), "tile 1x0")
+    fails(stem_fwd(stages=3), "stages 3")
+    fails(stem_wgrad(dy_ld=62), "dy_ld 62")
+    fails(stem_wgrad(mt=4, nt=1), "tile 4x1")
+    fails(stem_wgrad(mt=5, nt=3), "tile 5x3")
+    fails(stem_wgrad(mt=0, nt=2), "tile 0x2")
     # descriptor entry points (round 3): host-side validation of every form they can express
     from attention_based_tbn_amd._lib import ConvDesc
 
@@ -757,6 +799,45 @@ def test_c_abi_rejects_bad_arguments_before_touching_the_gpu():
     assert L.tbn_conv_partial_rows(C.byref(desc(n=3, h=14, w=14, flags=16)), 1, 0) == 19
     assert L.tbn_conv_partial_rows(C.byref(desc(n=3, h=14, w=14, flags=16)), 1, 1) == 5      # a pair uses 128-row tiles
     assert L.tbn_conv_partial_rows(C.byref(desc(n=2, h=15, w=15, stride=2, dgrad=1)), 1, 0) == 4   # 8x8, 8x7, 7x8, 7x7 phases
+
+
+def test_stem_geometry_matches_the_closed_forms():
+    """tbn_stem_geometry (host only) against the closed forms of the layout comments in csrc/pool.hip, for every channel
+    count the plan admits and sizes of every parity, down to maps smaller than the filter: the space-to-depth image is
+    (ceil(h/2)+3) x (ceil(w/2)+3) pixels of 4 cin floats with K = 64 cin; the row-runs image (2(oh-1)+8) x (2(ow-1)+8)
+    pixels of cin floats with runs of rl = 7 cin rounded up to x4 and K = 7 rl rounded up to x32.  The rule (layout 0)
+    takes row runs exactly when their K is the smaller one: from 4 channels on."""
+    import ctypes as C
+    from attention_based_tbn_amd._lib import lib
+    L = lib()
+    header = open(os.path.join(ROOT, "include", "tbn_hip.h")).read()
+    assert re.search(r"^#define TBN_CAP_STEM_OPS 64$", header, re.M)
+    assert L.tbn_capabilities() & 64 and (L.tbn_version() & 0xffff) == 102
+    up = lambda v, m: (v + m - 1) // m * m
+    out = (C.c_int * 8)()
+    residues, switch = set(), []
+    for cin in range(1, 17):
+        rl = up(7 * cin, 4)
+        residues.add(rl - 7 * cin)
+        want = {
+            1: lambda h, w: [1, (h + 1) // 2 + 3, (w + 1) // 2 + 3, 4 * cin, 16 * cin, 64 * cin, 64 * cin],
+            2: lambda h, w: [2, 2 * ((h - 1) // 2) + 8, 2 * ((w - 1) // 2) + 8, cin, rl, up(7 * rl, 32), 7 * rl],
+        }
+        rule = 2 if up(7 * rl, 32) < 64 * cin else 1
+        assert rule == (1 if cin <= 3 else 2)
+        switch.append(rule)
+        for h, w in ((17, 19), (16, 22), (15, 18), (18, 13), (7, 7), (32, 32), (1, 1), (2, 1), (224, 224), (70, 129)):
+            for layout in (0, 1, 2):
+                assert L.tbn_stem_geometry(cin, h, w, layout, out) == 0
+                exp = want[layout or rule](h, w)
+                exp.append(exp[1] * exp[2] * exp[3])
+                assert list(out) == exp, (cin, h, w, layout, list(out), exp)
+                assert exp[5] % 32 == 0 and exp[4] % 4 == 0 and exp[5] >= exp[6]
+                # the workspace holds the four regions (each rounded up to 256 B); the slabs are at least nothing
+                n, cout = 3, 64
+                floor = sum(up(v, 64) for v in (n * exp[7], cout * exp[5], cout * exp[6]))
+                assert L.tbn_stem_workspace_floats(cin, h, w, layout, n, cout) >= floor
+    assert residues == {0, 1, 2, 3} and switch == [1] * 3 + [2] * 13
 
 
 def test_launch_info_reports_the_plan_choices_per_mode():

@@ -277,7 +277,8 @@ def reference_named_grads(model):
     return out
 
 
-@pytest.mark.parametrize("cin_hw", [(3, 64, 64), (10, 96, 64), (1, 128, 256), (3, 224, 224), (3, 97, 97), (10, 70, 129)])
+@pytest.mark.parametrize("cin_hw", [(3, 64, 64), (10, 96, 64), (1, 128, 256), (3, 224, 224), (3, 97, 97), (10, 70, 129),
+                                    (2, 96, 64), (7, 70, 129)])   # channel counts no modality uses: the runtime-channel stem repacks
 def test_backbone_all_layer_grads_vs_oracle(cin_hw):
     """every conv / BN parameter gradient of one backbone + running stats, train mode.
     (audio uses H=128: with H=64 the last maps are 2 rows high, the 3x3/pad-1 average pool then
