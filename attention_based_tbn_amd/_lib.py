@@ -51,6 +51,25 @@ class ConvDesc(C.Structure):
                 ("red_stats_stride", c_i), ("out2", c_fp), ("out2_ld", c_i), ("out2_col_begin", c_i), ("out2_raw", c_i)]
 
 
+class BnSeg(C.Structure):
+    """include/tbn_hip.h tbn_bn_seg"""
+    _fields_ = [("ptr", c_fp), ("ld", c_i), ("col_begin", c_i)]
+
+
+class BnFwdDesc(C.Structure):
+    """include/tbn_hip.h tbn_bn_fwd_desc"""
+    _fields_ = [("y", c_fp), ("y_ld", c_i), ("p", c_i), ("c", c_i), ("partial", c_fp), ("pld", c_i), ("nparts", c_i),
+                ("gamma", c_fp), ("beta", c_fp), ("conv_bias", c_fp), ("running_mean", c_fp), ("running_var", c_fp),
+                ("save_mean", c_fp), ("save_rstd", c_fp), ("scale", c_fp), ("shift", c_fp), ("seg", BnSeg * 3), ("nseg", c_i)]
+
+
+class BnBwdDesc(C.Structure):
+    """include/tbn_hip.h tbn_bn_bwd_desc"""
+    _fields_ = [("dz", BnSeg * 3), ("nseg", c_i), ("y", c_fp), ("dy", c_fp), ("y_ld", c_i), ("p", c_i), ("c", c_i),
+                ("scale", c_fp), ("shift", c_fp), ("mean", c_fp), ("rstd", c_fp), ("partial", c_fp), ("ext_parts", c_i),
+                ("coef", c_fp), ("dgamma", c_fp), ("dbeta", c_fp), ("dbias", c_fp)]
+
+
 class OptTensor(C.Structure):
     _fields_ = [("param", c_fp), ("grad", c_fp), ("momentum", c_fp), ("count", c_sz)]
 
@@ -117,6 +136,10 @@ SIGNATURES = {
     "tbn_bn_relu_train_fwd": (c_i, [c_fp, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_f, c_f, c_fp, c_fp, c_fp, c_fp, c_fp,
                                     c_i, c_fp, c_fp]),
     "tbn_bn_relu_train_bwd": (c_i, [c_fp, c_i, c_fp, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "tbn_bn_stats_partials": (c_i, [c_fp, c_i, c_i, c_i, c_fp, C.POINTER(c_i), c_fp]),
+    "tbn_bn_fwd_batch": (c_i, [C.POINTER(BnFwdDesc), c_i, c_f, c_f, c_fp]),
+    "tbn_bn_bwd_partial_floats": (c_sz, [c_i, c_i]),
+    "tbn_bn_bwd_batch": (c_i, [C.POINTER(BnBwdDesc), c_i, c_fp]),
     "tbn_bn_relu_maxpool_train_fwd": (c_i, [c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_f, c_f, c_fp, c_fp, c_fp,
                                             c_fp, c_fp, c_i, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp]),
     "tbn_bn_relu_maxpool_train_bwd": (c_i, [c_fp, c_i, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp,

@@ -272,7 +272,7 @@ extern "C" {
 
 int tbn_version(void) { return 102 | (TBN_EXPERIMENT ? 0x10000 : 0); }
 
-int tbn_capabilities(void) { return TBN_CAP_CONV_BF16X | TBN_CAP_CONV_BF16X_PLANES | TBN_CAP_FRAMES_CROPS | TBN_CAP_ATTN_GENERAL | TBN_CAP_ATTN_REG | TBN_CAP_AUDIO_LAYER | TBN_CAP_STEM_OPS; }
+int tbn_capabilities(void) { return TBN_CAP_CONV_BF16X | TBN_CAP_CONV_BF16X_PLANES | TBN_CAP_FRAMES_CROPS | TBN_CAP_ATTN_GENERAL | TBN_CAP_ATTN_REG | TBN_CAP_AUDIO_LAYER | TBN_CAP_STEM_OPS | TBN_CAP_BN_BATCH_OPS; }
 
 int tbn_diag_mfma_burst(float* sink, int workgroups, int iters, double* flops, void* stream) {
   TBN_REQUIRE(sink != nullptr && workgroups > 0 && workgroups <= 65536 && iters > 0, "diag_mfma_burst: bad argument");
@@ -779,6 +779,67 @@ int tbn_bn_relu_train_bwd(const float* dz, int dz_ld, const float* y, int p, int
   TBN_TRY(tbn_launch_bn_bwd_finalize(workspace, parts, p, c, scale, save_mean, save_rstd, coef, dgamma, dbeta, nullptr,
                                      st));
   return tbn_launch_bn_bwd_apply(&s, 1, y, p, c, scale, shift, coef, dy, st);
+}
+
+// ---- the engine's batched training BN on its own (bn_multi.hip): descriptors in, the launchers' own rules decide
+int tbn_bn_stats_partials(const float* y, int y_ld, int p, int c, float* partial, int* nparts, void* stream) {
+  TBN_REQUIRE(y && partial && nparts, "bn_stats_partials: null pointer");
+  return tbn_launch_bn_stats(y, y_ld, p, c, partial, nparts, (hipStream_t)stream);
+}
+
+size_t tbn_bn_bwd_partial_floats(int p, int c) {
+  if (p < 1 || c < 4 || c > 1024 || c % 4 != 0) return 0;
+  return (size_t)tbn_bn_bwd_parts(p, c) * 2 * c;
+}
+
+int tbn_bn_fwd_batch(const tbn_bn_fwd_desc* members, int n, float momentum, float eps, void* stream) {
+  TBN_REQUIRE(members != nullptr, "bn_fwd_batch: null pointer");
+  static thread_local BnFwdBatch b;
+  memset(&b, 0, sizeof(b));
+  b.n = n;                       // outside 1..TBN_BN_MAXL: nothing is copied and the launcher refuses
+  b.momentum = momentum;
+  b.eps = eps;
+  for (int i = 0; i < n && n <= TBN_BN_MAXL; ++i) {
+    const tbn_bn_fwd_desc& d = members[i];
+    TBN_REQUIRE(d.y && d.partial && d.gamma && d.beta && d.save_mean && d.save_rstd && d.scale && d.shift,
+                "bn_fwd_batch: null pointer in member %d", i);
+    TBN_REQUIRE(d.running_mean == nullptr || d.running_var != nullptr, "bn_fwd_batch: member %d has running_mean without running_var", i);
+    BnFwdLayer& L = b.l[i];
+    L.y = d.y; L.y_ld = d.y_ld; L.P = d.p; L.C = d.c;
+    L.partial = d.partial; L.pld = d.pld; L.nparts = d.nparts;
+    L.gamma = d.gamma; L.beta = d.beta; L.conv_bias = d.conv_bias;
+    L.running_mean = d.running_mean; L.running_var = d.running_var;
+    L.save_mean = d.save_mean; L.save_rstd = d.save_rstd; L.scale = d.scale; L.shift = d.shift;
+    L.nseg = d.nseg;
+    for (int s = 0; s < 3 && s < d.nseg; ++s) {
+      TBN_REQUIRE(d.seg[s].ptr != nullptr, "bn_fwd_batch: null pointer in segment %d of member %d", s, i);
+      L.seg[s].ptr = d.seg[s].ptr; L.seg[s].ld = d.seg[s].ld; L.seg[s].col_begin = d.seg[s].col_begin;
+    }
+  }
+  return tbn_launch_bn_fwd_multi(b, (hipStream_t)stream);
+}
+
+int tbn_bn_bwd_batch(const tbn_bn_bwd_desc* members, int n, void* stream) {
+  TBN_REQUIRE(members != nullptr, "bn_bwd_batch: null pointer");
+  static thread_local BnBwdBatch b;
+  memset(&b, 0, sizeof(b));
+  b.n = n;
+  for (int i = 0; i < n && n <= TBN_BN_MAXL; ++i) {
+    const tbn_bn_bwd_desc& d = members[i];
+    TBN_REQUIRE(d.y && d.dy && d.scale && d.shift && d.mean && d.rstd && d.partial && d.coef,
+                "bn_bwd_batch: null pointer in member %d", i);
+    BnBwdLayer& L = b.l[i];
+    L.nseg = d.nseg;
+    for (int s = 0; s < 3 && s < d.nseg; ++s) {
+      TBN_REQUIRE(d.dz[s].ptr != nullptr, "bn_bwd_batch: null pointer in segment %d of member %d", s, i);
+      L.dz[s].ptr = d.dz[s].ptr; L.dz[s].ld = d.dz[s].ld; L.dz[s].col_begin = d.dz[s].col_begin;
+    }
+    L.y = d.y; L.dy = d.dy; L.y_ld = d.y_ld; L.P = d.p; L.C = d.c;
+    L.scale = d.scale; L.shift = d.shift; L.mean = d.mean; L.rstd = d.rstd;
+    L.partial = d.partial; L.ext_parts = d.ext_parts; L.coef = d.coef;
+    L.dgamma = d.dgamma; L.dbeta = d.dbeta; L.dbias = d.dbias;
+  }
+  return tbn_launch_bn_bwd_multi(b, (hipStream_t)stream);
 }
 
 // ---- training BN + ReLU + max pool in one pass (the fused stem form of the engine)

@@ -56,7 +56,8 @@ int tbn_bn_stats_parts(int P, int C) {
 }
 
 int tbn_launch_bn_stats(const float* y, int ld, int P, int C, float* partial, int* nparts, hipStream_t st) {
-  TBN_REQUIRE(C % 4 == 0 && C <= 1024 && ld % 4 == 0, "bn_stats: C must be a multiple of 4 and <= 1024");
+  TBN_REQUIRE(P >= 1 && C >= 4 && C % 4 == 0 && C <= 1024 && ld % 4 == 0 && ld >= C,
+              "bn_stats: P >= 1, C a multiple of 4 in 4..1024, pitch a multiple of 4 and at least C");
   const int rp = 256 / (C / 4), pch = pick_chunk(P, rp), parts = cdiv(P, pch);
   TBN_KLAUNCH(bn_stats_kernel, dim3(parts), dim3(256), 0, st, y, ld, P, C, pch, partial);
   TBN_CHECK_LAUNCH("bn_stats");

@@ -165,8 +165,8 @@ int tbn_launch_bn_fwd_multi_defer(BnFwdBatch& b, unsigned defer_mask, RiderP* ri
   b.fin_blk0[0] = b.app_blk0[0] = 0;
   for (int i = 0; i < b.n; ++i) {
     BnFwdLayer& L = b.l[i];
-    TBN_REQUIRE(L.C % 4 == 0 && L.C <= 1024 && L.y_ld % 4 == 0 && L.y_ld >= L.C && L.pld >= L.C && L.nseg >= 1 && L.nseg <= 3,
-                "bn_fwd_multi: bad C / pitch / nseg");
+    TBN_REQUIRE(L.P >= 1 && L.C >= 4 && L.C % 4 == 0 && L.C <= 1024 && L.y_ld % 4 == 0 && L.y_ld >= L.C && L.pld >= L.C &&
+                L.pld % 4 == 0 && L.nparts >= 1 && L.nseg >= 1 && L.nseg <= 3, "bn_fwd_multi: bad P / C / pitch / nparts / nseg");
     for (int s = 0; s < L.nseg; ++s)
       TBN_REQUIRE(L.seg[s].ld % 4 == 0 && L.seg[s].col_begin % 4 == 0, "bn_fwd_multi: segment pitch/offset must be x4");
     b.fin_blk0[i + 1] = b.fin_blk0[i] + cdiv(L.C, TBN_FIN_CH);
@@ -352,8 +352,8 @@ int tbn_launch_bn_bwd_multi_defer(BnBwdBatch& b, unsigned defer_mask, RiderP* ri
   b.red_blk0[0] = b.fin_blk0[0] = b.app_blk0[0] = 0;
   for (int i = 0; i < b.n; ++i) {
     BnBwdLayer& L = b.l[i];
-    TBN_REQUIRE(L.C % 4 == 0 && L.C <= 1024 && L.y_ld % 4 == 0 && L.y_ld >= L.C && L.nseg >= 1 && L.nseg <= 3,
-                "bn_bwd_multi: bad C / pitch / nseg");
+    TBN_REQUIRE(L.P >= 1 && L.C >= 4 && L.C % 4 == 0 && L.C <= 1024 && L.y_ld % 4 == 0 && L.y_ld >= L.C && L.ext_parts >= 0 &&
+                L.nseg >= 1 && L.nseg <= 3, "bn_bwd_multi: bad P / C / pitch / ext_parts / nseg");
     for (int s = 0; s < L.nseg; ++s)
       TBN_REQUIRE(L.dz[s].ld % 4 == 0 && L.dz[s].col_begin % 4 == 0, "bn_bwd_multi: segment pitch/offset must be x4");
     {  // same chunking as bn.hip's single-layer launch: rows per workgroup rounded to the row-lane count

@@ -50,6 +50,8 @@ int tbn_version(void);
 #define TBN_CAP_AUDIO_LAYER 32
 /* bit 7: the stem entries (tbn_stem_geometry / tbn_stem_workspace_floats / tbn_stem_conv_fwd / tbn_stem_conv_wgrad) */
 #define TBN_CAP_STEM_OPS 64
+/* bit 8: the batched training-BN entries (tbn_bn_stats_partials / tbn_bn_fwd_batch / tbn_bn_bwd_batch / tbn_bn_bwd_partial_floats) */
+#define TBN_CAP_BN_BATCH_OPS 128
 int tbn_capabilities(void);
 const char* tbn_last_error(void);
 
@@ -437,6 +439,74 @@ int tbn_bn_relu_maxpool_train_bwd(const float* dpooled, int dpooled_ld, const ui
                                   int w, int c, int oh, int ow, int stride, int pad, const float* save_mean,
                                   const float* save_rstd, const float* scale, const float* shift, float* dy,
                                   float* dgamma, float* dbeta, float* workspace, void* stream);
+
+/* ---- the batched training BN of the backbone engine on its own (test / tuning aid) -------------------
+ * The launch sequence the engine runs for the BN of every conv but the fused stem pools: statistics partials (from a conv
+ * epilogue, or from tbn_bn_stats_partials), then ONE finalize + ONE apply launch for up to 4 independent members (forward),
+ * ONE reduce + ONE finalize + ONE apply launch (backward).  Ask tbn_capabilities() & TBN_CAP_BN_BATCH_OPS.
+ * Every member: p rows x c channels, c a multiple of 4 in 4..1024; y has pitch y_ld >= c; all pitches and column offsets
+ * are multiples of 4 floats and every pointer is 16-B aligned.
+ * tbn_bn_stats_partials: partial[(i*2 + {0,1}) * c + ch] = sum | sum of squares of y over row chunk i; *nparts = chunks
+ *   written (partial: tbn_bn_workspace_floats floats are enough).
+ * tbn_bn_fwd_batch: statistics from partial[(i*2 + {0,1}) * pld + ch], i < nparts (pld >= c); writes save_mean, save_rstd,
+ *   scale = gamma * rstd, shift = beta - mean * scale and z = relu(y * scale + shift) into 1..3 column segments
+ *   (segment s takes the channels from seg[s].col_begin up to the next segment's col_begin; seg[s].ptr is the address of
+ *   channel col_begin of row 0, seg[0].col_begin = 0).  running_mean may be NULL (running_var is then not touched either);
+ *   otherwise running_mean takes mean + conv_bias (conv_bias may be NULL: y is the bias-free conv output, the reference's
+ *   BN sees conv + bias) and running_var the unbiased variance, both with `momentum`.
+ * tbn_bn_bwd_batch: dy = d loss / d y from dz = d loss / d z, written with pitch y_ld (dy may be y itself).  partial is
+ *   scratch of tbn_bn_bwd_partial_floats floats -- or, with ext_parts > 0, holds ext_parts rows
+ *   partial[(i*2 + {0,1}) * c + ch] = sum g | sum g * xhat (g = dz where z > 0, xhat = (y - mean) * rstd) made by the caller,
+ *   as a data-gradient epilogue does (tbn_conv_desc.red); no reduce pass runs for that member.  coef: scratch of 3 c floats.
+ *   dgamma / dbeta / dbias may be NULL; dbias receives zeros (a constant added in front of a batch-statistics BN has no
+ *   gradient).
+ * A batch gives every member the bits it gets as a batch of one.  Deterministic.
+ * replaces: nn.BatchNorm2d(...).train() + ReLU(inplace) of bn_inception_audio.py:24-401, forward and backward. */
+typedef struct {
+  float* ptr;             /* address of channel col_begin of row 0 */
+  int ld;                 /* floats between rows */
+  int col_begin;          /* first channel that goes through this segment */
+} tbn_bn_seg;
+typedef struct {
+  const float* y;
+  int y_ld;
+  int p, c;
+  const float* partial;
+  int pld, nparts;
+  const float* gamma;
+  const float* beta;
+  const float* conv_bias;     /* may be NULL */
+  float* running_mean;        /* may be NULL, with running_var */
+  float* running_var;
+  float* save_mean;
+  float* save_rstd;
+  float* scale;
+  float* shift;
+  tbn_bn_seg seg[3];          /* destinations of z */
+  int nseg;
+} tbn_bn_fwd_desc;
+typedef struct {
+  tbn_bn_seg dz[3];           /* gradient with respect to z, by column segment (read only) */
+  int nseg;
+  const float* y;
+  float* dy;
+  int y_ld;
+  int p, c;
+  const float* scale;         /* the four per-channel vectors tbn_bn_fwd_batch wrote */
+  const float* shift;
+  const float* mean;
+  const float* rstd;
+  float* partial;
+  int ext_parts;              /* 0: partial is scratch; > 0: rows of caller-made partials */
+  float* coef;
+  float* dgamma;              /* may be NULL */
+  float* dbeta;               /* may be NULL */
+  float* dbias;               /* may be NULL */
+} tbn_bn_bwd_desc;
+int tbn_bn_stats_partials(const float* y, int y_ld, int p, int c, float* partial, int* nparts, void* stream);
+int tbn_bn_fwd_batch(const tbn_bn_fwd_desc* members, int n, float momentum, float eps, void* stream);
+size_t tbn_bn_bwd_partial_floats(int p, int c);   /* 0 for a shape the entries refuse */
+int tbn_bn_bwd_batch(const tbn_bn_bwd_desc* members, int n, void* stream);
 
 /* pooling (bn_inception_audio.py:21-23,86-88,155-157,394-396; ceil_mode handled by oh/ow) */
 int tbn_maxpool3_fwd(const float* in, int in_ld, float* out, int out_ld, uint8_t* argmax, int n, int h, int w, int c,

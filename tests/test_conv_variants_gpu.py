@@ -15,6 +15,7 @@ Tolerance 1e-4 relative to the tensor's maximum (the north star allows 1e-3 end 
 """
 import ctypes as C
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -301,18 +302,21 @@ def test_bn_relu_maxpool_fused_fwd_bwd(case):
     select a window maximum of the fp64 z up to the fp32 error), and dy / dgamma / dbeta with the fp64 autograd routed
     through the product's arg-max"""
     n, h, w, c, s, p = case
+    from tests import bn_check as bc
     oh = -(-(h + 2 * p - 3) // s) + 1
     ow = -(-(w + 2 * p - 3) // s) + 1
     if (oh - 1) * s >= h + p:
         oh -= 1
     if (ow - 1) * s >= w + p:
         ow -= 1
-    y = torch.randn(n, h, w, c, generator=g(1)) * 2 + 0.5
-    gamma = torch.rand(c, generator=g(2)) + 0.5
-    beta = torch.randn(c, generator=g(3)) * 0.3
-    rm, rv = torch.randn(c, generator=g(4)), torch.rand(c, generator=g(5)) + 0.5
-    dpool = torch.randn(n, oh, ow, c, generator=g(6))
+    # the BN part on the multi-scale inputs of tests/bn_check.py (channel std over five decades, gamma of both signs and 0,
+    # constant channels) and judged per channel as well as over the whole tensor
     P = n * h * w
+    bn = bc.make_case(P, c, seed=17 * P + c)
+    bref = bc.reference(bn)
+    y = torch.from_numpy(bn["y"]).view(n, h, w, c)
+    gamma, beta, rm, rv = (torch.from_numpy(bn[k]) for k in ("gamma", "beta", "rm", "rv"))
+    dpool = torch.randn(n, oh, ow, c, generator=g(6)) * 10.0 ** (4 * torch.rand(c, generator=g(7)) - 2)
     ws = torch.empty(lib().tbn_bn_workspace_floats(P, c), device=DEV)
     yd, gd, bd, rmd, rvd = y.to(DEV), gamma.to(DEV), beta.to(DEV), rm.to(DEV), rv.to(DEV)
     mean, rstd, scale, shift = (torch.empty(c, device=DEV) for _ in range(4))
@@ -324,24 +328,40 @@ def test_bn_relu_maxpool_fused_fwd_bwd(case):
     yr = nchw(y).double().requires_grad_(True)
     gr, br = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
     rmr, rvr = rm.double().clone(), rv.double().clone()
-    z = F.relu(F.batch_norm(yr, rmr, rvr, gr, br, True, 0.1, 1e-5))
+    pre = F.batch_norm(yr, rmr, rvr, gr, br, True, 0.1, bc.EPS32)
+    z = F.relu(pre)
     pool_ref = F.max_pool2d(z, 3, s, p, ceil_mode=True)
     assert pool_ref.shape[2:] == (oh, ow)
     assert relerr(nchw(pooled[..., 4:4 + c]), pool_ref.detach()) < TOL
     assert float((pooled[..., :4] - 3).abs().max()) == 0 and float((pooled[..., 4 + c:] - 3).abs().max()) == 0
     assert relerr(rmd, rmr) < TOL and relerr(rvd, rvr) < TOL
+    bc.assert_chan(pooled[..., 4:4 + c].cpu().numpy(), nhwc(pool_ref.detach()).numpy(), bc.z_floor(bn), "pooled")
+    bc.assert_chan(mean.cpu().numpy(), bref["mean"], np.abs(bref["mean"]) + np.sqrt(bref["var"]), "save_mean")
+    bc.assert_chan(rstd.cpu().numpy(), bref["rstd"], 0.0, "save_rstd")
+    bc.check_running(bn, bref, rmd.cpu().numpy(), rvd.cpu().numpy(), 0.1)
     amc = am.cpu()
     assert int(amc.max()) < 9
     routed = _forced_pool(z, amc, s, p, oh, ow)
     # the selected entry IS a window maximum (up to fp32 rounding of z)
     assert float((routed.detach() - pool_ref.detach()).abs().max()) <= 1e-5 * float(pool_ref.detach().abs().max())
-    routed.backward(nchw(dpool).double())
+    # backward reference: the product's arg-max AND its ReLU decisions (z is never written: they are recomputed from y, scale
+    # and shift as every kernel does), which must be the reference's up to rounding
+    mask = bc.product_decisions(bn["y"], scale.cpu().numpy(), shift.cpu().numpy())
+    bc.assert_decisions(mask, bref["pre"], np.maximum(np.abs(bref["z"]).max(0), bc.z_floor(bn)))
+    zm = pre * nchw(torch.from_numpy(mask).view(n, h, w, c))
+    zm.retain_grad()
+    _forced_pool(zm, amc, s, p, oh, ow).backward(nchw(dpool).double())
     dpd = dpool.to(DEV)
     dy, dg, db = torch.empty(n, h, w, c, device=DEV), torch.empty(c, device=DEV), torch.empty(c, device=DEV)
     call("tbn_bn_relu_maxpool_train_bwd", ptr(dpd), c, ptr(am), ptr(yd), n, h, w, c, oh, ow, s, p, ptr(mean), ptr(rstd),
          ptr(scale), ptr(shift), ptr(dy), ptr(dg), ptr(db), ptr(ws), st())
     assert relerr(nchw(dy), yr.grad) < TOL
     assert relerr(dg, gr.grad) < TOL and relerr(db, br.grad) < TOL
+    gz = nhwc(zm.grad).reshape(P, c).numpy() * mask       # gradient reaching the pre-activation, (P, c)
+    bc.assert_chan(dy.cpu().numpy(), nhwc(yr.grad).numpy(),
+                   np.abs(bn["gamma"].astype(np.float64)) * bref["rstd"] * np.abs(gz).max(0), "dy")
+    bc.assert_chan(dg.cpu().numpy(), gr.grad.numpy(), np.sqrt(((gz * bref["xhat"]) ** 2).sum(0)), "dgamma")
+    bc.assert_chan(db.cpu().numpy(), br.grad.numpy(), np.sqrt((gz ** 2).sum(0)), "dbeta")
     # in place (the engine converts y to dy in place)
     y2 = yd.clone()
     call("tbn_bn_relu_maxpool_train_bwd", ptr(dpd), c, ptr(am), ptr(y2), n, h, w, c, oh, ow, s, p, ptr(mean), ptr(rstd),

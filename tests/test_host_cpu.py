@@ -27,6 +27,10 @@ def test_library_loads_and_exports_every_header_symbol():
     for name in declared:
         assert getattr(handle, name) is not None
     assert handle.tbn_version() >= 100
+    # every capability bit the header names is one this build reports
+    caps = {name: int(v) for name, v in re.findall(r"^#define (TBN_CAP_[A-Z0-9_]+) (\d+)$", header, re.M)}
+    assert caps["TBN_CAP_BN_BATCH_OPS"] == 128 and len(caps) == 8 and sum(caps.values()) == 255
+    assert handle.tbn_capabilities() == 255
 
 
 def test_engine_layer_table_matches_reference_graph():
@@ -285,6 +289,7 @@ dist.all_gather(both, mine)
 assert not torch.allclose(both[0], both[1]) and model._pending == [] and not model._callback_queued
 sd = model.state_dict(); assert all(k.startswith("module.") for k in sd)
 print("DP_OK", rank)
+dist.destroy_process_group()                        # orderly shutdown: a rank that just exits while c10d's threads still run can abort in teardown
 '''
 
 
@@ -375,6 +380,7 @@ for it in range(7):
         assert (mb is None) == (rb is None) and (mb is None or torch.allclose(mb, rb, rtol=1e-4, atol=2e-5)), (it, n)
 assert clip == 0 or clipped >= 3, clipped           # the clip really bit (also on re-clipped accumulated gradients)
 print("ACC_OK", rank)
+dist.destroy_process_group()                        # orderly shutdown: a rank that just exits while c10d's threads still run can abort in teardown
 '''
 
 
@@ -463,6 +469,7 @@ for it, dr in enumerate(drops):
     assert model._pending == [] and not model._callback_queued and (step.synced[-1] != model._unsynced)
 assert len(step.synced) == len(drops)
 print("ACCOPT_OK", rank)
+dist.destroy_process_group()                        # orderly shutdown: a rank that just exits while c10d's threads still run can abort in teardown
 '''
 
 
@@ -588,6 +595,7 @@ try:
 except RuntimeError as e:
     assert "different problems" in str(e), e
 print("BUCKET_OK", rank)
+dist.destroy_process_group()                        # orderly shutdown: a rank that just exits while c10d's threads still run can abort in teardown
 '''
 
 
@@ -779,6 +787,71 @@ def test_c_abi_rejects_bad_arguments_before_touching_the_gpu():
     fails(stem_wgrad(mt=4, nt=1), "tile 4x1")
     fails(stem_wgrad(mt=5, nt=3), "tile 5x3")
     fails(stem_wgrad(mt=0, nt=2), "tile 0x2")
+    # batched training BN: the launchers' shape rules (bn_multi.hip) and null pointers, before any launch
+    from attention_based_tbn_amd._lib import BnBwdDesc, BnFwdDesc, BnSeg
+
+    def bn_fwd(n=1, **kw):
+        d = BnFwdDesc()
+        for k in ("y", "partial", "gamma", "beta", "running_mean", "running_var", "save_mean", "save_rstd", "scale", "shift"):
+            setattr(d, k, bad)
+        d.y_ld, d.p, d.c, d.pld, d.nparts, d.nseg = 32, 8, 32, 32, 1, 1
+        d.seg[0] = BnSeg(bad, 32, 0)
+        seg = kw.pop("seg", None)
+        for k, v in kw.items():
+            setattr(d, k, v)
+        for i, sg in enumerate(seg or ()):
+            d.seg[i] = sg
+        arr = (BnFwdDesc * 5)(*[d] * 5)
+        return L.tbn_bn_fwd_batch(arr, n, 0.1, 1e-5, None)
+
+    def bn_bwd(n=1, **kw):
+        d = BnBwdDesc()
+        for k in ("y", "dy", "scale", "shift", "mean", "rstd", "partial", "coef", "dgamma", "dbeta", "dbias"):
+            setattr(d, k, bad)
+        d.y_ld, d.p, d.c, d.nseg = 32, 8, 32, 1
+        d.dz[0] = BnSeg(bad, 32, 0)
+        seg = kw.pop("seg", None)
+        for k, v in kw.items():
+            setattr(d, k, v)
+        for i, sg in enumerate(seg or ()):
+            d.dz[i] = sg
+        arr = (BnBwdDesc * 5)(*[d] * 5)
+        return L.tbn_bn_bwd_batch(arr, n, None)
+    for f, who in ((bn_fwd, "bn_fwd"), (bn_bwd, "bn_bwd")):
+        fails(f(n=0), who + "_multi: 0 layers")
+        fails(f(n=5), who + "_multi: 5 layers")
+        fails(f(n=-1), who + "_multi: -1 layers")
+        for kw in (dict(c=30), dict(c=1028, y_ld=1028, pld=1028), dict(c=0), dict(p=0), dict(y_ld=28), dict(y_ld=34), dict(nseg=0),
+                   dict(nseg=4, seg=[BnSeg(bad, 32, 0), BnSeg(bad, 32, 8), BnSeg(bad, 32, 16)])):
+            if who == "bn_bwd":
+                kw.pop("pld", None)
+            fails(f(**kw), who + "_multi: bad P / C / pitch")
+        fails(f(seg=[BnSeg(bad, 34, 0)]), who + "_multi: segment pitch/offset must be x4")
+        fails(f(nseg=2, seg=[BnSeg(bad, 32, 0), BnSeg(bad, 32, 18)]), who + "_multi: segment pitch/offset must be x4")
+        fails(f(seg=[BnSeg(0, 32, 0)]), who + "_batch: null pointer in segment 0 of member 0")
+        fails(f(nseg=3, seg=[BnSeg(bad, 32, 0), BnSeg(bad, 32, 8), BnSeg(0, 32, 16)]), who + "_batch: null pointer in segment 2")
+        fails(f(n=4, y=None), who + "_batch: null pointer in member 0")
+    fails(bn_fwd(pld=28), "bn_fwd_multi: bad P / C / pitch")
+    fails(bn_fwd(pld=34), "bn_fwd_multi: bad P / C / pitch")
+    fails(bn_fwd(nparts=0), "bn_fwd_multi: bad P / C / pitch")
+    fails(bn_bwd(ext_parts=-1), "bn_bwd_multi: bad P / C / pitch")
+    for k in ("partial", "gamma", "beta", "save_mean", "save_rstd", "scale", "shift"):
+        fails(bn_fwd(**{k: None}), "bn_fwd_batch: null pointer in member 0")
+    fails(bn_fwd(running_var=None), "running_mean without running_var")
+    for k in ("dy", "scale", "shift", "mean", "rstd", "partial", "coef"):
+        fails(bn_bwd(**{k: None}), "bn_bwd_batch: null pointer in member 0")
+    fails(L.tbn_bn_fwd_batch(None, 1, 0.1, 1e-5, None), "bn_fwd_batch: null pointer")
+    fails(L.tbn_bn_bwd_batch(None, 1, None), "bn_bwd_batch: null pointer")
+    nparts = C.c_int(0)
+    fails(L.tbn_bn_stats_partials(None, 32, 8, 32, bad, C.byref(nparts), None), "bn_stats_partials: null pointer")
+    fails(L.tbn_bn_stats_partials(bad, 32, 8, 32, bad, None, None), "bn_stats_partials: null pointer")
+    for y_ld, p_, c_ in ((28, 8, 32), (34, 8, 32), (32, 0, 32), (32, 8, 30), (1028, 8, 1028), (32, 8, 0)):
+        fails(L.tbn_bn_stats_partials(bad, y_ld, p_, c_, bad, C.byref(nparts), None), "bn_stats: P >= 1, C a multiple of 4")
+    assert L.tbn_bn_bwd_partial_floats(0, 32) == 0 and L.tbn_bn_bwd_partial_floats(8, 30) == 0
+    assert L.tbn_bn_bwd_partial_floats(8, 1028) == 0 and L.tbn_bn_bwd_partial_floats(8, 0) == 0
+    # rows per reduce workgroup: max(64, ceil(p / 512)) rounded up to the 256 / (c / 4) row lanes
+    assert L.tbn_bn_bwd_partial_floats(5000, 1024) == 79 * 2 * 1024 and L.tbn_bn_bwd_partial_floats(5000, 4) == 20 * 2 * 4
+    assert L.tbn_bn_bwd_partial_floats(100000, 32) == 447 * 2 * 32 and L.tbn_bn_bwd_partial_floats(1, 100) == 200
     # descriptor entry points (round 3): host-side validation of every form they can express
     from attention_based_tbn_amd._lib import ConvDesc
 

@@ -337,34 +337,37 @@ def test_wgrad_every_heuristic_tile(cout, cin, ksp):
 @pytest.mark.parametrize("p_c", [(2 * 14 * 14, 96), (3 * 7 * 5, 384), (1000, 32), (48, 704), (48, 128), (192, 192),
                                  (5000, 736)])
 def test_bn_relu_train_fwd_bwd(p_c):
+    """the stand-alone operator on the multi-scale inputs of tests/bn_check.py (channel std over five decades, gamma of both
+    signs and 0, constant channels), z and dz pitched: the whole-tensor bounds as before, and every channel on its own scale"""
+    from tests import bn_check as bc
     P, C = p_c
-    y = torch.randn(P, C, generator=g(1)) * 2 + 0.5
-    gamma = torch.rand(C, generator=g(2)) + 0.5
-    beta = torch.randn(C, generator=g(3)) * 0.3
-    rm, rv = torch.randn(C, generator=g(4)), torch.rand(C, generator=g(5)) + 0.5
-    dz = torch.randn(P, C, generator=g(6))
-    # reference: BatchNorm over the P rows
-    yr = y.double().t().reshape(1, C, P).requires_grad_(True)
-    gr, br = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
-    rmr, rvr = rm.double().clone(), rv.double().clone()
-    zr = F.relu(F.batch_norm(yr, rmr, rvr, gr, br, True, 0.1, 1e-5))
-    zr.backward(dz.double().t().reshape(1, C, P))
-
+    case = bc.make_case(P, C, seed=31 * P + C)
+    ref = bc.reference(case)
+    t = torch.from_numpy
     nws = lib().tbn_bn_workspace_floats(P, C)
     ws = torch.empty(nws, device=DEV)
-    yd, rmd, rvd = y.to(DEV), rm.to(DEV), rv.to(DEV)
+    yd, rmd, rvd = t(case["y"]).to(DEV), t(case["rm"]).to(DEV), t(case["rv"]).to(DEV)
     mean, rstd, scale, shift = (torch.empty(C, device=DEV) for _ in range(4))
-    z = torch.zeros(P, C + 8, device=DEV)
-    gd, btd, dzd = gamma.to(DEV), beta.to(DEV), dz.to(DEV)
+    z = torch.full((P, C + 8), float("nan"), device=DEV)
+    gd, btd = t(case["gamma"]).to(DEV), t(case["beta"]).to(DEV)
+    dzd = torch.full((P, C + 12), float("nan"), device=DEV)
+    dzd[:, 8:8 + C] = t(case["dz"]).to(DEV)
     call("tbn_bn_relu_train_fwd", ptr(yd), P, C, ptr(gd), ptr(btd), ptr(rmd), ptr(rvd), 0.1,
          1e-5, ptr(mean), ptr(rstd), ptr(scale), ptr(shift), z.data_ptr() + 16, C + 8, ptr(ws), st())
-    assert relerr(z[:, 4:4 + C], zr.detach()[0].t()) < TOL
-    assert relerr(rmd, rmr) < TOL and relerr(rvd, rvr) < TOL
+    assert relerr(z[:, 4:4 + C], t(ref["z"])) < TOL
+    assert bool(torch.isnan(z[:, :4]).all()) and bool(torch.isnan(z[:, 4 + C:]).all())
+    m = 0.1
+    rm_ref, rv_ref = (1 - m) * case["rm"] + m * ref["mean"], (1 - m) * case["rv"] + m * ref["unb"]
+    assert relerr(rmd, t(rm_ref)) < TOL and relerr(rvd, t(rv_ref)) < TOL
+    mask = bc.check_forward(case, ref, z[:, 4:4 + C].cpu().numpy(), mean.cpu().numpy(), rstd.cpu().numpy())
+    bc.check_running(case, ref, rmd.cpu().numpy(), rvd.cpu().numpy(), m)
+    bref = bc.reference_backward(case, ref, mask)      # the product's ReLU decisions, checked against the reference's
     dy, dg, db = torch.empty(P, C, device=DEV), torch.empty(C, device=DEV), torch.empty(C, device=DEV)
-    call("tbn_bn_relu_train_bwd", ptr(dzd), C, ptr(yd), P, C, ptr(mean), ptr(rstd), ptr(scale), ptr(shift),
+    call("tbn_bn_relu_train_bwd", dzd.data_ptr() + 32, C + 12, ptr(yd), P, C, ptr(mean), ptr(rstd), ptr(scale), ptr(shift),
          ptr(dy), ptr(dg), ptr(db), ptr(ws), st())
-    assert relerr(dy, yr.grad[0].t()) < TOL
-    assert relerr(dg, gr.grad) < TOL and relerr(db, br.grad) < TOL
+    assert relerr(dy, t(bref["dy"])) < TOL
+    assert relerr(dg, t(bref["dgamma"])) < TOL and relerr(db, t(bref["dbeta"])) < TOL
+    bc.check_backward(case, ref, bref, dy.cpu().numpy(), dg.cpu().numpy(), db.cpu().numpy())
 
 
 def _bn_fuzz(count, seed):
