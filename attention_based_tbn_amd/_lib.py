@@ -144,6 +144,12 @@ SIGNATURES = {
                                             c_fp, c_fp, c_i, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp]),
     "tbn_bn_relu_maxpool_train_bwd": (c_i, [c_fp, c_i, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp,
                                             c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "tbn_bn_res_apply": (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_i, c_fp, c_i, c_fp]),
+    "tbn_bn_res_fwd": (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_f, c_f, c_fp, c_fp, c_fp,
+                             c_fp, c_fp, c_i, c_i, c_fp, c_i, c_fp]),
+    "tbn_bn_res_bwd_workspace_floats": (c_sz, [c_i, c_i]),
+    "tbn_bn_res_bwd": (c_i, [c_fp, c_i, c_fp, c_i, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_fp, c_i, c_fp, c_i, c_i,
+                             c_fp, c_fp, c_fp, c_fp]),
     "tbn_maxpool3_fwd": (c_i, [c_fp, c_i, c_fp, c_i, c_fp] + [c_i] * 8 + [c_fp]),
     "tbn_maxpool3_bwd": (c_i, [c_fp, c_i, c_fp, c_fp, c_i] + [c_i] * 9 + [c_fp]),
     "tbn_avgpool3_fwd": (c_i, [c_fp, c_i, c_fp, c_i] + [c_i] * 5 + [c_fp]),

@@ -20,6 +20,7 @@ from ... import ops
 from .attention import MultiheadedAttention, PositionalEncoding, PrototypeAttention, UniModalAttention
 from .bn_inception import bninception
 from .contrast_loss import ContrastLoss
+from .resnet import Resnet
 
 
 class _ArenaCatFn(torch.autograd.Function):
@@ -125,6 +126,11 @@ class TBNModel(nn.Module):
         # the case (_fused_attention_losses); False keeps them on the torch ops -- the switch of an A/B script
         self.fused_attention_losses = True
         self.shared_streams = {}          # {"Flow": "RGB"}: Flow's backbone runs on RGB's stream (fewer concurrent chains)
+        if ("resnet" in self.base_model_name and self.use_attention and "Audio" in self.modality
+                and len(self.modality) > 1):
+            raise ValueError("arch 'resnet' with attention.enable and Audio among the modalities is not supported: the "
+                             "attention branches need the (R, 1024, 1, T) sequence that only BN-Inception's audio trunk "
+                             "produces (the reference fails in its first forward, model.py:211-237)")
         if cfg.model.agg_type.lower() == "avg":
             self.agg_type = "avg"
         else:
@@ -170,9 +176,15 @@ class TBNModel(nn.Module):
             self.add_module("classifier", Classifier(self.num_classes, in_features))
 
     def _create_base_model(self, modality):
+        if "resnet" in self.base_model_name:
+            # reference model.py:133-134.  `pretrained=True` there downloads torchvision's ImageNet weights; here they come
+            # from `pretrained_state["imagenet"]` (a torchvision resnet state dict) when the caller supplies it, else random
+            # initialisation -- the rule the BN-Inception branch below follows for its `.pth` files
+            state = self._pretrained_state.get("imagenet") if self._pretrained_state is not None else None
+            return Resnet(self.cfg.model.resnet.depth, modality, self.IN_CHANNELS[modality], state_dict=state)
         if self.base_model_name != "bninception":
-            raise NotImplementedError("the MI355X hot path implements the BN-Inception backbone "
-                                      f"(north star); arch '{self.base_model_name}' is out of scope")
+            raise NotImplementedError("the MI355X hot path implements the BN-Inception and ResNet backbones; "
+                                      f"arch '{self.base_model_name}' is out of scope")
         pretrained = "kinetics" if modality == "Flow" else "imagenet"
         model_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(
             os.path.dirname(os.path.abspath(__file__))))), "weights")
@@ -249,7 +261,9 @@ class TBNModel(nn.Module):
         # of its backward are gone (forward() hands the buffer to the fusion layer when every feature really sits in it)
         self._arena = None
         first_in = input[self.modality[0]]
-        if len(self.modality) > 1 and first_in.is_cuda:
+        bases = [getattr(self, "Base_{}".format(m)) for m in self.modality]
+        # (only the BN-Inception engine writes into a slot; other backbones return their own tensor and torch.cat runs)
+        if len(self.modality) > 1 and first_in.is_cuda and all(hasattr(b, "_out_slot") for b in bases):
             R = first_in.shape[0] * first_in.shape[1]
             self._arena = torch.empty(R, 1024 * len(self.modality), device=first_in.device, dtype=torch.float32)
             for i, m in enumerate(self.modality):
@@ -257,8 +271,9 @@ class TBNModel(nn.Module):
         try:
             return self._run_backbones_inner(input)
         finally:
-            for m in self.modality:
-                getattr(self, "Base_{}".format(m))._out_slot = None
+            for b in bases:
+                if hasattr(b, "_out_slot"):
+                    b._out_slot = None
 
     def _run_backbones_inner(self, input):
         def run(m):

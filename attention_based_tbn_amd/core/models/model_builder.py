@@ -11,7 +11,7 @@ from .contrast_loss import ContrastLoss
 from .dataparallel import DataParallel
 from .model import TBNModel
 
-_MODEL_TYPES = {"bninception": TBNModel}
+_MODEL_TYPES = {"bninception": TBNModel, "resnet": TBNModel}
 
 _LOSS_TYPES = {
     "crossentropy": torch.nn.CrossEntropyLoss,
@@ -24,7 +24,7 @@ _LOSS_TYPES = {
 
 def build_model(cfg, modality, device, pretrained_state=None):
     assert cfg.model.arch in _MODEL_TYPES.keys(), \
-        "Model type '{}' not supported on the MI355X hot path (bninception only)".format(cfg.model.arch)
+        "Model type '{}' not supported on the MI355X hot path (bninception and resnet)".format(cfg.model.arch)
     assert cfg.model.loss_fn in _LOSS_TYPES.keys(), "Loss type '{}' not supported".format(cfg.model.loss_fn)
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     requested = len(cfg.gpu_ids) if len(cfg.gpu_ids) > 0 else (max(world, 1) if device.type == "cuda" else 0)

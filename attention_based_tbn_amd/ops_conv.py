@@ -1,0 +1,468 @@
+"""Operator-level autograd wrappers for conv / BatchNorm networks on NHWC tensors (HIP only -- no CPU fallback).
+
+The BN-Inception backbone is one engine call (core/models/bn_inception.py).  A network the engine does not know -- the
+ResNets of core/models/resnet.py -- is composed here from the stand-alone C-ABI operators instead:
+
+  conv_bn_act     conv (1x1 / 3x3, stride 1 / 2, cin a multiple of 32) + BatchNorm + optional residual + optional ReLU
+  residual_block  a whole BasicBlock / Bottleneck as ONE autograd node: its backward pass lets the identity path and
+                  conv1's data gradient meet in the block input's gradient buffer through the `accumulate` arguments of
+                  tbn_bn_res_bwd / tbn_conv2d_dgrad instead of a separate add
+  stem_bn_pool    the 7x7 / stride 2 / pad 3 stem straight from NCHW frames + BatchNorm + ReLU + MaxPool(3, 2, 1)
+
+Training: tbn_conv2d_fwd epilogue 1 (bias-free output + statistics partials), then tbn_bn_fwd_batch (no residual, ReLU,
+at most 1024 channels) or tbn_bn_res_fwd (the join: residual and / or no ReLU and / or more channels).  Eval: running
+statistics folded into the conv's epilogue 2, the join through epilogue 0 + tbn_bn_res_apply.  Everything launches on the
+current stream.  Parameters keep torch's OIHW shape (checkpoints interchange); the kernels read [cout][k][k][cin], a copy
+cached on the parameter's `_version`.
+"""
+import ctypes as C
+
+import torch
+
+from ._lib import BnBwdDesc, BnFwdDesc, BnSeg, call, lib, ptr, stream_ptr, TbnHipError
+
+MOMENTUM = 0.1
+EPS = 1e-5
+
+
+class BnState:
+    """what a unit needs beside its parameters: geometry, the BatchNorm buffers, and the two caches of the unit"""
+    __slots__ = ("stride", "pad", "running_mean", "running_var", "wcache", "fcache")
+
+    def __init__(self, stride, pad, running_mean, running_var):
+        self.stride, self.pad = stride, pad
+        self.running_mean, self.running_var = running_mean, running_var
+        self.wcache, self.fcache = {}, {}      # kernel_weight / folded_bn
+
+
+def _need_cuda(t, what):
+    if not t.is_cuda:
+        raise TbnHipError(f"{what}: tensor is on {t.device}; the TBN hot path only runs on an MI355X "
+                          "(HIP) device -- there is no CPU fallback")
+
+
+def _f32c(t):
+    t = t.contiguous()
+    return t if t.dtype == torch.float32 else t.float()
+
+
+def kernel_weight(weight, cache):
+    """an OIHW conv weight in the kernels' [cout][k][k][cin] order.  k = 1 or cin = 1: the same memory, no copy.
+    Otherwise a permuted copy kept in `cache` until the parameter changes (`_version`: optimiser steps bump it)."""
+    cout, cin, k, _ = weight.shape
+    w = weight.detach()
+    if (k == 1 or cin == 1) and w.is_contiguous() and w.dtype == torch.float32:
+        return w.view(cout, k, k, cin)
+    key = (weight.data_ptr(), weight._version)
+    if cache.get("key") != key:
+        buf = cache.get("buf")
+        if buf is None or tuple(buf.shape) != (cout, k, k, cin) or buf.device != w.device:
+            buf = cache["buf"] = torch.empty(cout, k, k, cin, device=w.device, dtype=torch.float32)
+        buf.copy_(w.permute(0, 2, 3, 1))
+        cache["key"] = key
+    return cache["buf"]
+
+
+def _oihw(dwk):
+    """weight gradient [cout][k][k][cin] -> the parameter's OIHW shape (a view)"""
+    return dwk.permute(0, 3, 1, 2)
+
+
+def folded_bn(gamma, beta, state):
+    """(2, c): scale = gamma / sqrt(var + eps) | shift = beta - mean * scale, folded once and kept until one of the four
+    tensors changes (`_version`)"""
+    rm, rv = state.running_mean, state.running_var
+    key = tuple((t.data_ptr(), t._version) for t in (gamma, beta, rm, rv))
+    cache = state.fcache
+    if cache.get("key") != key:
+        sc = gamma.detach().float() / torch.sqrt(rv.float() + EPS)
+        cache["ss"] = torch.stack([sc, beta.detach().float() - rm.float() * sc]).contiguous()
+        cache["key"] = key
+    return cache["ss"]
+
+
+def _out_size(h, w, k, stride, pad):
+    return (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+
+
+def _check_conv(x, wk, what):
+    cout, k, _, cin = wk.shape
+    if x.dim() != 4 or x.shape[3] != cin:
+        raise TbnHipError(f"{what}: input {tuple(x.shape)} is not NHWC with {cin} channels")
+    if cin % 32 or cout % 32 or k not in (1, 3):
+        raise TbnHipError(f"{what}: the HIP convolutions take 1x1 / 3x3 kernels with cin and cout multiples of 32 "
+                          f"(got k = {k}, cin = {cin}, cout = {cout})")
+
+
+# ---------------------------------------------------------------------------------------------- launches (no autograd)
+def _conv_fwd(x, wk, stride, pad, epilogue, ss=None, partial=None):
+    n, h, w, cin = x.shape
+    cout, k = wk.shape[0], wk.shape[1]
+    oh, ow = _out_size(h, w, k, stride, pad)
+    y = torch.empty(n, oh, ow, cout, device=x.device, dtype=torch.float32)
+    call("tbn_conv2d_fwd", ptr(x), cin, ptr(wk), 0, ptr(y), cout, n, h, w, cin, cout, k, stride, pad, epilogue, 0,
+         ss[0].data_ptr() if ss is not None else 0, ss[1].data_ptr() if ss is not None else 0, ptr(partial), stream_ptr())
+    return y
+
+
+def _unit_fwd_train(x, wk, gamma, beta, state, res, relu):
+    """-> (y, z, stats): bias-free conv output, block output, (4, c) rows batch mean | 1/std | scale | shift"""
+    n, h, w, cin = x.shape
+    cout, k = wk.shape[0], wk.shape[1]
+    tiles = lib().tbn_conv2d_stat_tiles(n, h, w, cin, cout, k, state.stride, state.pad)
+    partial = torch.empty(tiles * 2 * cout, device=x.device, dtype=torch.float32)
+    y = _conv_fwd(x, wk, state.stride, state.pad, 1, partial=partial)
+    p = y.numel() // cout
+    z = torch.empty_like(y)
+    stats = torch.empty(4, cout, device=x.device, dtype=torch.float32)
+    rm, rv = state.running_mean, state.running_var
+    if res is None and relu and cout <= 1024:
+        d = BnFwdDesc()
+        d.y, d.y_ld, d.p, d.c = y.data_ptr(), cout, p, cout
+        d.partial, d.pld, d.nparts = partial.data_ptr(), cout, tiles
+        d.gamma, d.beta, d.conv_bias = gamma.data_ptr(), beta.data_ptr(), 0
+        d.running_mean, d.running_var = ptr(rm), ptr(rv)
+        d.save_mean, d.save_rstd, d.scale, d.shift = (stats[i].data_ptr() for i in range(4))
+        d.seg[0] = BnSeg(z.data_ptr(), cout, 0)
+        d.nseg = 1
+        call("tbn_bn_fwd_batch", C.byref(d), 1, MOMENTUM, EPS, stream_ptr())
+    else:
+        call("tbn_bn_res_fwd", ptr(y), cout, p, cout, ptr(partial), cout, tiles, ptr(gamma), ptr(beta), ptr(rm), ptr(rv),
+             MOMENTUM, EPS, stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(),
+             ptr(res), cout, int(relu), ptr(z), cout, stream_ptr())
+    if rm is not None:
+        # the kernels wrote the buffers behind autograd's back: tell the caches keyed on `_version` (folded_bn)
+        torch.autograd.graph.increment_version((rm, rv))
+    return y, z, stats
+
+
+def _unit_fwd_eval(x, wk, gamma, beta, state, res, relu):
+    ss = folded_bn(gamma, beta, state)
+    if res is None and relu:
+        return _conv_fwd(x, wk, state.stride, state.pad, 2, ss=ss)
+    z = _conv_fwd(x, wk, state.stride, state.pad, 0)
+    cout = wk.shape[0]
+    call("tbn_bn_res_apply", ptr(z), cout, z.numel() // cout, cout, ss[0].data_ptr(), ss[1].data_ptr(), ptr(res), cout,
+         int(relu), ptr(z), cout, stream_ptr())
+    return z
+
+
+def _bn_bwd(dz, y, z, stats, had_res, relu, dres, need_affine):
+    """-> (dy, dgamma, dbeta); `dres` (a (p, c) buffer or None) receives the gradient of the residual"""
+    cout = y.shape[-1]
+    p = y.numel() // cout
+    dy = torch.empty_like(y)
+    dgb = torch.empty(2, cout, device=y.device, dtype=torch.float32) if need_affine else None
+    dg, db = (dgb[0].data_ptr(), dgb[1].data_ptr()) if need_affine else (0, 0)
+    if not had_res and relu and cout <= 1024:
+        scratch = torch.empty(lib().tbn_bn_bwd_partial_floats(p, cout) + 3 * cout, device=y.device, dtype=torch.float32)
+        d = BnBwdDesc()
+        d.dz[0] = BnSeg(dz.data_ptr(), cout, 0)
+        d.nseg = 1
+        d.y, d.dy, d.y_ld, d.p, d.c = y.data_ptr(), dy.data_ptr(), cout, p, cout
+        d.mean, d.rstd, d.scale, d.shift = (stats[i].data_ptr() for i in range(4))
+        d.partial, d.ext_parts, d.coef = scratch.data_ptr(), 0, scratch.data_ptr() + 4 * (scratch.numel() - 3 * cout)
+        d.dgamma, d.dbeta, d.dbias = dg, db, 0
+        call("tbn_bn_bwd_batch", C.byref(d), 1, stream_ptr())
+    else:
+        ws = torch.empty(lib().tbn_bn_res_bwd_workspace_floats(p, cout), device=y.device, dtype=torch.float32)
+        call("tbn_bn_res_bwd", ptr(dz), cout, ptr(z) if relu else 0, cout, ptr(y), cout, p, cout, stats[0].data_ptr(),
+             stats[1].data_ptr(), stats[2].data_ptr(), int(relu), ptr(dy), cout, ptr(dres), cout, 0, dg, db,
+             ptr(ws), stream_ptr())
+    return dy, (dgb[0] if need_affine else None), (dgb[1] if need_affine else None)
+
+
+def _conv_wgrad(dy, x, wk, state):
+    n, h, w, cin = x.shape
+    cout, k = wk.shape[0], wk.shape[1]
+    dwk = torch.empty_like(wk)
+    nws = lib().tbn_conv2d_wgrad_workspace_floats(n, h, w, cin, cout, k, state.stride, state.pad)
+    ws = torch.empty(max(nws, 1), device=x.device, dtype=torch.float32)
+    call("tbn_conv2d_wgrad", ptr(dy), cout, ptr(x), cin, ptr(dwk), n, h, w, cin, cout, k, state.stride, state.pad,
+         ptr(ws), stream_ptr())
+    return _oihw(dwk)
+
+
+def _conv_dgrad(dy, wk, x_shape, state, dx=None):
+    """data gradient into `dx`: a fresh buffer, or ADDED to the one given"""
+    n, h, w, cin = x_shape
+    cout, k = wk.shape[0], wk.shape[1]
+    acc = dx is not None
+    if dx is None:
+        dx = torch.empty(x_shape, device=dy.device, dtype=torch.float32)
+    ws = torch.empty(wk.numel(), device=dy.device, dtype=torch.float32)
+    call("tbn_conv2d_dgrad", ptr(dy), cout, ptr(wk), ptr(dx), cin, n, h, w, cin, cout, k, state.stride, state.pad,
+         int(acc), ptr(ws), stream_ptr())
+    return dx
+
+
+_EVAL_BACKWARD = ("{}: backward through an eval-mode backbone (running-statistics BN) is not implemented; call .train() "
+                  "for fine-tuning or wrap inference in torch.no_grad()")
+
+
+# ---------------------------------------------------------------------------------------------- one fused unit
+class _ConvBnActFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, residual, state, relu, training):
+        _need_cuda(x, "conv_bn_act")
+        x = _f32c(x)
+        wk = kernel_weight(weight, state.wcache)
+        _check_conv(x, wk, "conv_bn_act")
+        res = _f32c(residual) if residual is not None else None
+        ctx.eval_mode = not training
+        ctx.live = training and any(ctx.needs_input_grad[:5])
+        if not training:
+            return _unit_fwd_eval(x, wk, gamma, beta, state, res, relu)
+        y, z, stats = _unit_fwd_train(x, wk, gamma, beta, state, res, relu)
+        if ctx.live:
+            ctx.state, ctx.relu, ctx.had_res = state, relu, res is not None
+            ctx.save_for_backward(x, wk, y, z, stats)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        need = ctx.needs_input_grad
+        if not ctx.live:
+            if ctx.eval_mode and any(need[:5]):
+                raise TbnHipError(_EVAL_BACKWARD.format("conv_bn_act"))
+            return (None,) * 8
+        x, wk, y, z, stats = ctx.saved_tensors
+        dz = _f32c(dz)
+        dres = torch.empty_like(y) if (ctx.had_res and need[4]) else None
+        dy, dg, db = _bn_bwd(dz, y, z, stats, ctx.had_res, ctx.relu, dres, need[2] or need[3])
+        dw = _conv_wgrad(dy, x, wk, ctx.state) if need[1] else None
+        dx = _conv_dgrad(dy, wk, x.shape, ctx.state) if need[0] else None
+        return dx, dw, dg if need[2] else None, db if need[3] else None, dres, None, None, None
+
+
+def conv_bn_act(x, weight, gamma, beta, running_mean, running_var, stride, pad, residual=None, relu=True,
+                training=True, state=None):
+    """act(bn(conv(x)) + residual) on NHWC tensors: x (n, h, w, cin), weight OIHW (no conv bias), residual (n, oh, ow,
+    cout) or None, act = ReLU or identity.  training: batch statistics, running_mean / running_var (may be None) updated
+    with momentum 0.1; else the running statistics.  `state` (a BnState the caller keeps) carries the weight and fold
+    caches from call to call; without one they are rebuilt per call."""
+    if state is None:
+        state = BnState(stride, pad, running_mean, running_var)
+    else:
+        state.stride, state.pad, state.running_mean, state.running_var = stride, pad, running_mean, running_var
+    return _ConvBnActFn.apply(x, weight, gamma, beta, residual, state, bool(relu), bool(training))
+
+
+# ---------------------------------------------------------------------------------------------- a residual block
+class _ResidualBlockFn(torch.autograd.Function):
+    """x -> relu(bn_K(conv_K(... relu(bn_1(conv_1(x))))) + shortcut(x)), shortcut = identity or bn_d(conv_d(x)).
+    params: (weight, gamma, beta) of the K main units, then of the downsample unit when `states` has K + 1 entries."""
+
+    @staticmethod
+    def forward(ctx, x, states, nmain, training, *params):
+        _need_cuda(x, "residual_block")
+        x = _f32c(x)
+        units = [(kernel_weight(params[3 * i], s.wcache), params[3 * i + 1], params[3 * i + 2], s)
+                 for i, s in enumerate(states)]
+        has_ds = len(states) == nmain + 1
+        _check_conv(x, units[0][0], "residual_block")
+        fwd = _unit_fwd_train if training else _unit_fwd_eval
+        ctx.eval_mode = not training
+        ctx.live = training and (ctx.needs_input_grad[0] or any(ctx.needs_input_grad[4:]))
+        saved = [x]
+        res = x
+        if has_ds:
+            out = fwd(x, *units[nmain], None, False)
+            res = out[1] if training else out
+            if ctx.live:
+                saved += [units[nmain][0], out[0], out[2]]        # wk, y, stats
+        cur = x
+        for i in range(nmain):
+            last = i == nmain - 1
+            out = fwd(cur, *units[i], res if last else None, True)
+            cur = out[1] if training else out
+            if ctx.live:
+                saved += [units[i][0], out[0], out[1], out[2]]    # wk, y, z, stats
+        if ctx.live:
+            ctx.states, ctx.nmain, ctx.has_ds = states, nmain, has_ds
+            ctx.save_for_backward(*saved)
+        return cur
+
+    @staticmethod
+    def backward(ctx, dout):
+        need = ctx.needs_input_grad
+        if not ctx.live:
+            if ctx.eval_mode and (need[0] or any(need[4:])):
+                raise TbnHipError(_EVAL_BACKWARD.format("residual_block"))
+            return (None,) * len(need)
+        saved = list(ctx.saved_tensors)
+        states, nmain, has_ds = ctx.states, ctx.nmain, ctx.has_ds
+        x = saved.pop(0)
+        ds = None
+        if has_ds:
+            ds, saved = saved[:3], saved[3:]
+        main = [saved[4 * i:4 * i + 4] for i in range(nmain)]
+        grads = [None] * (3 * len(states))
+
+        def pneed(u, j):                 # weight / gamma / beta of unit u
+            return need[4 + 3 * u + j]
+
+        dz = _f32c(dout)
+        dx = None
+        # the join: dres goes to the block input's gradient (identity shortcut) or to the downsample unit
+        ds_live = has_ds and (need[0] or any(pneed(nmain, j) for j in range(3)))
+        wk, y, z, stats = main[-1]
+        if has_ds:
+            dres = torch.empty_like(y) if ds_live else None
+        else:
+            dres = dx = torch.empty_like(x) if need[0] else None
+        dy, dg, db = _bn_bwd(dz, y, z, stats, True, True, dres, pneed(nmain - 1, 1) or pneed(nmain - 1, 2))
+        if ds_live:
+            dwk, dyy, dstats = ds
+            ddy, ddg, ddb = _bn_bwd(dres, dyy, None, dstats, True, False, None, pneed(nmain, 1) or pneed(nmain, 2))
+            if pneed(nmain, 0):
+                grads[3 * nmain] = _conv_wgrad(ddy, x, dwk, states[nmain])
+            grads[3 * nmain + 1] = ddg if pneed(nmain, 1) else None
+            grads[3 * nmain + 2] = ddb if pneed(nmain, 2) else None
+            if need[0]:
+                dx = _conv_dgrad(ddy, dwk, x.shape, states[nmain])
+        for i in range(nmain - 1, -1, -1):
+            wk = main[i][0]
+            inp = x if i == 0 else main[i - 1][2]
+            if i < nmain - 1:
+                if not (need[0] or any(pneed(u, j) for u in range(i + 1) for j in range(3))):
+                    break                # nothing from this unit down to the block input is differentiated
+                _, y, z, stats = main[i]
+                dy, dg, db = _bn_bwd(dz, y, z, stats, False, True, None, pneed(i, 1) or pneed(i, 2))
+            if pneed(i, 0):
+                grads[3 * i] = _conv_wgrad(dy, inp, wk, states[i])
+            grads[3 * i + 1] = dg if pneed(i, 1) else None
+            grads[3 * i + 2] = db if pneed(i, 2) else None
+            if i > 0:
+                if need[0] or any(pneed(u, j) for u in range(i) for j in range(3)):
+                    dz = _conv_dgrad(dy, wk, inp.shape, states[i])
+            elif need[0]:
+                # the shortcut's gradient is already in dx: conv1's data gradient is accumulated into it
+                dx = _conv_dgrad(dy, wk, x.shape, states[0], dx=dx)
+        return (dx, None, None, None) + tuple(grads)
+
+
+def residual_block(x, main, downsample=None, training=True):
+    """torchvision's BasicBlock (two units) / Bottleneck (three) on NHWC x.  `main`: [(weight, gamma, beta, BnState)] in
+    order, every unit followed by ReLU, the last one after the shortcut is added; `downsample`: the same tuple for the
+    1x1 conv + BN of the shortcut (no ReLU), or None for the identity."""
+    units = list(main) + ([downsample] if downsample is not None else [])
+    params = [t for u in units for t in u[:3]]
+    return _ResidualBlockFn.apply(x, [u[3] for u in units], len(main), bool(training), *params)
+
+
+# ---------------------------------------------------------------------------------------------- global average pool
+class _GlobalMeanFn(torch.autograd.Function):
+    """NHWC (n, h, w, c) -> (n, c).  tbn_spatial_mean_fwd takes at most 1024 channels per call: wider maps (the 2048 of
+    ResNet-50/101/152) go through it as column ranges of the same buffers (the entry reads and writes pitched rows)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        _need_cuda(x, "global_mean")
+        x = _f32c(x)
+        n, h, w, c = x.shape
+        out = torch.empty(n, c, device=x.device, dtype=torch.float32)
+        for c0 in range(0, c, 1024):
+            call("tbn_spatial_mean_fwd", x.data_ptr() + 4 * c0, c, out.data_ptr() + 4 * c0, c, n, h, w, min(1024, c - c0),
+                 0, stream_ptr())
+        ctx.shape = tuple(x.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        n, h, w, c = ctx.shape
+        dout = _f32c(dout)
+        dx = torch.empty(ctx.shape, device=dout.device, dtype=torch.float32)
+        call("tbn_spatial_mean_bwd", ptr(dout), c, ptr(dx), c, n, h, w, c, 0, stream_ptr())
+        return dx
+
+
+def global_mean(x_nhwc):
+    """AdaptiveAvgPool2d(1) + flatten on an NHWC map of any width that is a multiple of 4"""
+    return _GlobalMeanFn.apply(x_nhwc)
+
+
+# ---------------------------------------------------------------------------------------------- the stem
+_NO_INPUT_GRAD = ("{}: the gradient with respect to the input frames is not implemented (the first conv's data gradient "
+                  "is never formed); detach the input")
+
+
+class _StemFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, state, training, who):
+        _need_cuda(x, who)
+        x = _f32c(x)
+        n, cin, h, w = x.shape
+        cout = weight.shape[0]
+        if tuple(weight.shape[1:]) != (cin, 7, 7) or not 1 <= cin <= 16 or cout % 32:
+            raise TbnHipError(f"{who}: the stem is a 7x7 / stride 2 / pad 3 conv of 1..16 input channels, got weight "
+                              f"{tuple(weight.shape)} for input {tuple(x.shape)}")
+        wk = kernel_weight(weight, state.wcache)
+        st = stream_ptr()
+        oh, ow = _out_size(h, w, 7, 2, 3)
+        ph, pw = _out_size(oh, ow, 3, 2, 1)           # MaxPool2d(3, 2, 1), ceil_mode off
+        ws = torch.empty(lib().tbn_stem_workspace_floats(cin, h, w, 0, n, cout), device=x.device, dtype=torch.float32)
+        y = torch.empty(n, oh, ow, cout, device=x.device, dtype=torch.float32)
+        pooled = torch.empty(n, ph, pw, cout, device=x.device, dtype=torch.float32)
+        argmax = torch.empty(n, ph, pw, cout, device=x.device, dtype=torch.uint8)
+        ctx.eval_mode = not training
+        ctx.live = training and any(ctx.needs_input_grad[1:4])
+        ctx.who = who
+        if not training:
+            ss = folded_bn(gamma, beta, state)
+            call("tbn_stem_conv_fwd", ptr(x), ptr(wk), 0, ptr(y), cout, n, h, w, cin, cout, 0, 2, ss[0].data_ptr(),
+                 ss[1].data_ptr(), 0, 0, 0, 0, ptr(ws), st)
+            call("tbn_maxpool3_fwd", ptr(y), cout, ptr(pooled), cout, ptr(argmax), n, oh, ow, cout, ph, pw, 2, 1, st)
+            return pooled
+        # the heuristic picks the tile: statistics rows are per 128 * mt output rows, unwritten rows must read as zero
+        m = n * oh * ow
+        partial = torch.zeros((m + 127) // 128 * 2 * cout, device=x.device, dtype=torch.float32)
+        call("tbn_stem_conv_fwd", ptr(x), ptr(wk), 0, ptr(y), cout, n, h, w, cin, cout, 0, 1, 0, 0, ptr(partial), 0, 0, 0,
+             ptr(ws), st)
+        stats = torch.empty(4, cout, device=x.device, dtype=torch.float32)
+        bnws = torch.empty(lib().tbn_bn_workspace_floats(m, cout), device=x.device, dtype=torch.float32)
+        rm, rv = state.running_mean, state.running_var
+        call("tbn_bn_relu_maxpool_train_fwd", ptr(y), n, oh, ow, cout, ptr(gamma), ptr(beta), ptr(rm), ptr(rv), MOMENTUM,
+             EPS, stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), ptr(pooled), cout,
+             ptr(argmax), ph, pw, 2, 1, ptr(bnws), st)
+        if rm is not None:
+            torch.autograd.graph.increment_version((rm, rv))
+        if ctx.live:
+            ctx.save_for_backward(x, y, argmax, stats)
+        return pooled
+
+    @staticmethod
+    def backward(ctx, dpooled):
+        need = ctx.needs_input_grad
+        if need[0]:
+            raise TbnHipError(_NO_INPUT_GRAD.format(ctx.who))
+        if not ctx.live:
+            if ctx.eval_mode and any(need[1:4]):
+                raise TbnHipError(_EVAL_BACKWARD.format(ctx.who))
+            return (None,) * 7
+        x, y, argmax, stats = ctx.saved_tensors
+        n, cin, h, w = x.shape
+        _, oh, ow, cout = y.shape
+        ph, pw = argmax.shape[1], argmax.shape[2]
+        st = stream_ptr()
+        dpooled = _f32c(dpooled)
+        m = n * oh * ow
+        dy = torch.empty_like(y)
+        dgb = torch.empty(2, cout, device=x.device, dtype=torch.float32)
+        bnws = torch.empty(lib().tbn_bn_workspace_floats(m, cout), device=x.device, dtype=torch.float32)
+        call("tbn_bn_relu_maxpool_train_bwd", ptr(dpooled), cout, ptr(argmax), ptr(y), n, oh, ow, cout, ph, pw, 2, 1,
+             stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), ptr(dy),
+             dgb[0].data_ptr(), dgb[1].data_ptr(), ptr(bnws), st)
+        dw = None
+        if need[1]:
+            ws = torch.empty(lib().tbn_stem_workspace_floats(cin, h, w, 0, n, cout), device=x.device, dtype=torch.float32)
+            dwk = torch.empty(cout, 7, 7, cin, device=x.device, dtype=torch.float32)
+            call("tbn_stem_conv_wgrad", ptr(dy), cout, ptr(x), ptr(dwk), n, h, w, cin, cout, 0, 0, 0, ptr(ws), st)
+            dw = _oihw(dwk)
+        return None, dw, dgb[0] if need[2] else None, dgb[1] if need[3] else None, None, None, None
+
+
+def stem_bn_pool(x_nchw, weight, gamma, beta, state, training=True, who="stem_bn_pool"):
+    """MaxPool2d(3, 2, 1)(relu(bn(conv7x7_s2_p3(x)))): NCHW frames (n, cin <= 16, h, w) -> NHWC (n, ph, pw, cout).  No
+    input gradient is formed: asking for one raises TbnHipError in backward."""
+    return _StemFn.apply(x_nchw, weight, gamma, beta, state, bool(training), who)

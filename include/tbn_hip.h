@@ -508,6 +508,40 @@ int tbn_bn_fwd_batch(const tbn_bn_fwd_desc* members, int n, float momentum, floa
 size_t tbn_bn_bwd_partial_floats(int p, int c);   /* 0 for a shape the entries refuse */
 int tbn_bn_bwd_batch(const tbn_bn_bwd_desc* members, int n, void* stream);
 
+/* ---- BatchNorm with an optional residual and an optional ReLU: the join of a residual block ------------
+ * z = act(y * scale + shift + res), act = ReLU (relu = 1) or identity (relu = 0), res may be NULL.  p rows x c channels,
+ * c a multiple of 4 in 4..2048 (the batched entries above stop at 1024; ResNet-50/101/152 join at 2048); every tensor has its
+ * own pitch (floats between rows, a multiple of 4 and at least c) and every pointer is 16-B aligned.  No capability bit and no
+ * version step go with these entries (the low 16 bits of tbn_version() name the plan-cache format): callers that bind the
+ * C-ABI directly detect them by symbol (dlsym of tbn_bn_res_fwd).
+ * tbn_bn_res_apply: the apply pass alone with caller-given scale / shift -- the eval-mode join (scale / shift folded from the
+ *   running statistics) behind a tbn_conv2d_fwd with epilogue 0 and a NULL bias.  z may be y itself.
+ * tbn_bn_res_fwd: training mode.  y is the bias-free conv output, partial[(i*2 + {0,1}) * pld + ch], i < nparts, its sum |
+ *   sum of squares per row chunk -- what tbn_conv2d_fwd epilogue 1 and tbn_bn_stats_partials write and tbn_bn_fwd_batch
+ *   reads.  Writes save_mean, save_rstd, scale = gamma * rstd, shift = beta - mean * scale, updates running_mean /
+ *   running_var (NULL: not touched) with `momentum` and the unbiased variance, then applies.  z may be y itself.
+ * tbn_bn_res_bwd: with g = relu ? (z > 0 ? dz : 0) : dz -- the mask is read from the forward's STORED output z (NULL with
+ *   relu = 0), so it is bit-consistent with the forward whatever was added in front of the ReLU --
+ *   dres (+)= g (dres NULL: no residual; accumulate = 1 adds into it, which is how the identity path and conv1's data gradient
+ *   meet at a block's input without a separate add), dy = scale * (g - mean_p(g) - xhat * mean_p(g * xhat)) with
+ *   xhat = (y - mean) * rstd, i.e. the gradient with respect to y, dgamma = sum g * xhat, dbeta = sum g (either may be NULL).
+ *   dy may be y itself.  workspace: tbn_bn_res_bwd_workspace_floats(p, c) floats (0 for a shape the entries refuse).
+ * Deterministic (fixed-order fp64 sums of per-workgroup partials, no atomics).
+ * replaces: nn.BatchNorm2d + `out += identity` + ReLU of torchvision's BasicBlock / Bottleneck and the ReLU-free
+ * nn.BatchNorm2d of their downsample path, forward and backward, which the reference reaches through
+ * core/models/resnet.py:15-24. */
+int tbn_bn_res_apply(const float* y, int y_ld, int p, int c, const float* scale, const float* shift, const float* res,
+                     int res_ld, int relu, float* z, int z_ld, void* stream);
+int tbn_bn_res_fwd(const float* y, int y_ld, int p, int c, const float* partial, int pld, int nparts, const float* gamma,
+                   const float* beta, float* running_mean, float* running_var, float momentum, float eps,
+                   float* save_mean, float* save_rstd, float* scale, float* shift, const float* res, int res_ld,
+                   int relu, float* z, int z_ld, void* stream);
+size_t tbn_bn_res_bwd_workspace_floats(int p, int c);
+int tbn_bn_res_bwd(const float* dz, int dz_ld, const float* z, int z_ld, const float* y, int y_ld, int p, int c,
+                   const float* save_mean, const float* save_rstd, const float* scale, int relu, float* dy, int dy_ld,
+                   float* dres, int dres_ld, int accumulate, float* dgamma, float* dbeta, float* workspace,
+                   void* stream);
+
 /* pooling (bn_inception_audio.py:21-23,86-88,155-157,394-396; ceil_mode handled by oh/ow) */
 int tbn_maxpool3_fwd(const float* in, int in_ld, float* out, int out_ld, uint8_t* argmax, int n, int h, int w, int c,
                      int oh, int ow, int stride, int pad, void* stream);
