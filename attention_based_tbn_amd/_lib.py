@@ -74,6 +74,11 @@ class OptTensor(C.Structure):
     _fields_ = [("param", c_fp), ("grad", c_fp), ("momentum", c_fp), ("count", c_sz)]
 
 
+class AdamTensor(C.Structure):
+    _fields_ = [("param", c_fp), ("grad", c_fp), ("exp_avg", c_fp), ("exp_avg_sq", c_fp), ("count", c_sz),
+                ("step_size", c_f), ("inv_sqrt_bc2", c_f)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/tbn_hip.h
 SIGNATURES = {
     "tbn_version": (c_i, []),
@@ -191,6 +196,8 @@ SIGNATURES = {
     "tbn_opt_clip_coef": (c_i, [c_fp, c_i, c_f, c_fp, c_fp, c_fp]),
     "tbn_opt_scale_grads": (c_i, [C.POINTER(OptTensor), c_i, c_fp, c_fp]),
     "tbn_opt_sgd_step": (c_i, [C.POINTER(OptTensor), c_i, c_f, c_f, c_f, c_fp, c_fp]),
+    # reference core/tools/train.py:202-208 (optim.Adam)
+    "tbn_opt_adam_step": (c_i, [C.POINTER(AdamTensor), c_i, c_f, c_f, c_f, c_f, c_fp, c_fp]),
     "tbn_topk_correct": (c_i, [c_fp, c_i, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp]),
     "tbn_frames_to_tensor": (c_i, [c_fp] + [c_i] * 16 + [c_fp, c_fp, c_i, c_i, c_fp, c_fp]),
     "tbn_frames_to_tensor_crops": (c_i, [c_fp] + [c_i] * 10 + [C.POINTER(c_i), C.POINTER(c_i)] + [c_i] * 5 +

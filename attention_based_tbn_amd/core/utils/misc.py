@@ -35,7 +35,8 @@ def save_checkpoint(model, optimizer, epoch, train_loss_hist, val_loss_hist, val
 
 def load_checkpoint(filename, model, optimizer=None, scheduler=None, num_gpus=1, map_location="cpu"):
     """Inverse of `save_checkpoint` (the reference inlines this in train.py:219-240 / test.py:60-66).  Accepts
-    checkpoints written by the reference: their per-layer momentum buffers are scattered into the flat ones."""
+    checkpoints written by the reference: their per-layer momentum buffers (SGD) or moments and `step` (Adam) are scattered
+    into the flat ones."""
     data = torch.load(filename, map_location=map_location)
     target = model.module if (num_gpus > 1 and hasattr(model, "module")) else model
     target.load_state_dict(data["model"])
@@ -76,33 +77,55 @@ def reference_parameter_names(model):
     return names
 
 
+# the per-parameter tensor states that travel through the flat <-> per-layer views: FusedSGD / optim.SGD keep
+# `momentum_buffer`, FusedAdam / optim.Adam `exp_avg` and `exp_avg_sq` (plus the scalar `step`, carried separately)
+STATE_TENSORS = ("momentum_buffer", "exp_avg", "exp_avg_sq")
+
+
 def optimizer_state_from_reference(model, optimizer, ref_state):
-    """Load a reference checkpoint's SGD state (one momentum buffer per per-layer parameter) into an optimiser
-    built over THIS model's parameters (flat backbone storage): buffers are scattered into flat ones."""
+    """Load a reference checkpoint's optimiser state (SGD: one momentum buffer per per-layer parameter; Adam: both moments
+    and `step`) into an optimiser built over THIS model's parameters (flat backbone storage): the tensors are scattered
+    into flat ones.  Adam's `step` is one number per flat tensor, so the per-layer slots that land in one flat tensor must
+    agree on it; a checkpoint in which they do not cannot be represented here and raises ValueError."""
     names = reference_parameter_names(model)
     ref_idx = [i for g in ref_state["param_groups"] for i in g["params"]]
     assert len(ref_idx) == len(names), f"reference optimizer has {len(ref_idx)} parameters, the model {len(names)}"
-    by_name = {n: ref_state["state"].get(i, {}).get("momentum_buffer") for n, i in zip(names, ref_idx)}
+    by_name = {n: ref_state["state"].get(i, {}) for n, i in zip(names, ref_idx)}
     own = {p: n for n, p in model.named_parameters()}
     bb = dict(_backbones(model))
     done = {}
     for pre, m in bb.items():
-        flat = {a: torch.zeros_like(getattr(m, a)) for a in FLAT_NAMES}
-        owner = {flat[a].untyped_storage().data_ptr(): a for a in FLAT_NAMES}
-        filled = set()
-        for key, view in m.reference_param_views(flat):
-            buf = by_name.get(pre + "." + key)
-            if buf is not None:
-                view.copy_(buf.to(view.device))
-                filled.add(owner[view.untyped_storage().data_ptr()])
-        for a in FLAT_NAMES:   # a flat tensor none of whose layers had a buffer (frozen BN affine) keeps none
-            done[getattr(m, a)] = flat[a] if a in filled else None
+        for a in FLAT_NAMES:
+            done[getattr(m, a)] = {}
+        for k in STATE_TENSORS:
+            flat = {a: torch.zeros_like(getattr(m, a)) for a in FLAT_NAMES}
+            owner = {flat[a].untyped_storage().data_ptr(): a for a in FLAT_NAMES}
+            filled = set()
+            for key, view in m.reference_param_views(flat):
+                buf = by_name.get(pre + "." + key, {}).get(k)
+                if buf is not None:
+                    view.copy_(buf.to(view.device))
+                    filled.add(owner[view.untyped_storage().data_ptr()])
+            for a in filled:   # a flat tensor none of whose layers had a buffer (frozen BN affine) keeps none
+                done[getattr(m, a)][k] = flat[a]
+        for key, view in m.reference_param_views(flat):   # (`flat` only says which flat tensor a layer lands in)
+            step = by_name.get(pre + "." + key, {}).get("step")
+            if step is None:
+                continue
+            st = done[getattr(m, owner[view.untyped_storage().data_ptr()])]
+            if "step" in st and float(st["step"]) != float(step):
+                raise ValueError(f"optimizer state of {pre}: the layers stored in one flat tensor disagree on `step` "
+                                 f"({float(st['step']):g} and {float(step):g} at {key}); no such state exists here")
+            st["step"] = step
     for group in optimizer.param_groups:
         for p in group["params"]:
-            buf = done[p] if p in done else by_name.get(own.get(p))
-            if buf is not None:
-                optimizer.state[p]["momentum_buffer"] = buf.to(p.device).clone()
-    for k in ("lr", "momentum", "weight_decay"):
+            st = done[p] if p in done else by_name.get(own.get(p), {})
+            for k in STATE_TENSORS:
+                if st.get(k) is not None:
+                    optimizer.state[p][k] = st[k].to(p.device).clone()
+            if st.get("step") is not None:   # torch keeps it as a 0-dim float32 tensor on the host
+                optimizer.state[p]["step"] = torch.tensor(float(st["step"]), dtype=torch.float32)
+    for k in ("lr", "momentum", "weight_decay", "betas", "eps"):
         if k in ref_state["param_groups"][0]:
             for g in optimizer.param_groups:
                 g[k] = ref_state["param_groups"][0][k]
@@ -110,29 +133,36 @@ def optimizer_state_from_reference(model, optimizer, ref_state):
 
 def optimizer_state_to_reference(model, optimizer):
     """`optimizer.state_dict()` re-expressed over the reference's per-layer parameter list (what the reference's
-    `optim.SGD.load_state_dict` expects)."""
+    `optim.SGD.load_state_dict` / `optim.Adam.load_state_dict` expects).  Every per-layer slot of a flat tensor gets that
+    tensor's `step`."""
     names = reference_parameter_names(model)
     own = dict(model.named_parameters())
     per_name = {}
     for pre, m in _backbones(model):
-        flat = {}
-        for a in FLAT_NAMES:
-            st = optimizer.state.get(getattr(m, a), {})
-            flat[a] = st.get("momentum_buffer")
-        if all(v is None for v in flat.values()):
-            continue
-        have = {a for a, v in flat.items() if v is not None}
-        flat = {a: (v if v is not None else torch.zeros_like(getattr(m, a))) for a, v in flat.items()}
-        owner = {flat[a].untyped_storage().data_ptr(): a for a in FLAT_NAMES}
-        for key, view in m.reference_param_views(flat):
-            if owner[view.untyped_storage().data_ptr()] in have:   # frozen tensors have no buffer, as in torch
-                per_name[pre + "." + key] = view.detach().clone(memory_format=torch.contiguous_format)
+        states = {a: optimizer.state.get(getattr(m, a), {}) for a in FLAT_NAMES}
+        for k in STATE_TENSORS:
+            flat = {a: states[a].get(k) for a in FLAT_NAMES}
+            if all(v is None for v in flat.values()):
+                continue
+            have = {a for a, v in flat.items() if v is not None}
+            flat = {a: (v if v is not None else torch.zeros_like(getattr(m, a))) for a, v in flat.items()}
+            owner = {flat[a].untyped_storage().data_ptr(): a for a in FLAT_NAMES}
+            for key, view in m.reference_param_views(flat):
+                a = owner[view.untyped_storage().data_ptr()]
+                if a in have:   # frozen tensors have no buffer, as in torch
+                    slot = per_name.setdefault(pre + "." + key, {})
+                    if "step" in states[a] and "step" not in slot:
+                        slot["step"] = states[a]["step"].detach().clone()
+                    slot[k] = view.detach().clone(memory_format=torch.contiguous_format)
     state = {}
     for i, n in enumerate(names):
         if n in per_name:
-            state[i] = {"momentum_buffer": per_name[n]}
-        elif n in own and optimizer.state.get(own[n], {}).get("momentum_buffer") is not None:
-            state[i] = {"momentum_buffer": optimizer.state[own[n]]["momentum_buffer"].detach().clone()}
+            state[i] = per_name[n]
+        elif n in own:
+            st = optimizer.state.get(own[n], {})
+            slot = {k: st[k].detach().clone() for k in ("step",) + STATE_TENSORS if torch.is_tensor(st.get(k))}
+            if slot:
+                state[i] = slot
     g0 = {k: v for k, v in optimizer.param_groups[0].items() if k != "params"}
     g0["params"] = list(range(len(names)))
     return {"state": state, "param_groups": [g0]}

@@ -1,4 +1,4 @@
-"""Train-step shell on the MI355X: multi-tensor gradient clipping + SGD(momentum) in three launches.
+"""Train-step shell on the MI355X: multi-tensor gradient clipping + SGD(momentum) or Adam in three launches.
 
 Mirrors the reference loop body (core/tools/train.py:82-94) and its optimiser construction
 (core/tools/train.py:190-202): `torch.nn.utils.clip_grad_norm_(model.parameters(), cfg.train.clip_grad)`
@@ -6,15 +6,26 @@ followed by `optim.SGD(lr, momentum, weight_decay).step()`.  `FusedSGD` is a `to
 `MultiStepLR` / the warm-up scheduler of the reference drive it unchanged, and its `state_dict()` has torch's
 layout (`momentum_buffer` per parameter).  No host synchronisation: the total norm and the clipping
 coefficient stay on the device (`clip_grad_norm_` returns the norm as a 0-dim device tensor, like torch).
-There is no CPU fallback: CPU tensors raise.
+`FusedAdam` is the `optim.Adam` of the reference's other branch (core/tools/train.py:202-208) on the same launch scheme.
+There is no CPU fallback: CPU tensors raise (`FusedAdam` over parameters that ALL live on the CPU is torch's Adam itself).
 """
 import ctypes as C
+import math
 
 import torch
 
-from ..._lib import OptTensor, TbnHipError, call, lib, ptr, stream_ptr
+from ..._lib import AdamTensor, OptTensor, TbnHipError, call, lib, ptr, stream_ptr
 
 MAX_TENSORS = 48   # TBN_OPT_MAX_TENSORS
+
+
+def _check(p, g):
+    if not (p.is_cuda and g.is_cuda):
+        raise TbnHipError("fused optimiser: parameters and gradients must live on the GPU (no CPU fallback)")
+    if p.dtype != torch.float32 or g.dtype != torch.float32 or not p.is_contiguous() or not g.is_contiguous():
+        raise TbnHipError("fused optimiser: contiguous fp32 parameters / gradients only")
+    if g.is_sparse:
+        raise TbnHipError("fused optimiser: sparse gradients are not supported")
 
 
 def _entries(params, with_param, bufs=None):
@@ -23,20 +34,15 @@ def _entries(params, with_param, bufs=None):
         g = p.grad
         if g is None:
             continue
-        if not (p.is_cuda and g.is_cuda):
-            raise TbnHipError("fused optimiser: parameters and gradients must live on the GPU (no CPU fallback)")
-        if p.dtype != torch.float32 or g.dtype != torch.float32 or not p.is_contiguous() or not g.is_contiguous():
-            raise TbnHipError("fused optimiser: contiguous fp32 parameters / gradients only")
-        if g.is_sparse:
-            raise TbnHipError("fused optimiser: sparse gradients are not supported")
+        _check(p, g)
         ents.append(OptTensor(ptr(p) if with_param else 0, ptr(g), ptr(bufs[i]) if bufs is not None else 0, p.numel()))
     return ents
 
 
-def _chunks(ents):
+def _chunks(ents, struct=OptTensor):
     for i in range(0, len(ents), MAX_TENSORS):
         part = ents[i:i + MAX_TENSORS]
-        yield (OptTensor * len(part))(*part), len(part)
+        yield (struct * len(part))(*part), len(part)
 
 
 def _sqnorm_coef(ents, max_norm, device):
@@ -129,4 +135,84 @@ class FusedSGD(torch.optim.Optimizer):
             torch.autograd.graph.increment_version(params)
             if bufs is not None:
                 torch.autograd.graph.increment_version(bufs)
+        return loss
+
+
+class FusedAdam(torch.optim.Adam):
+    """`torch.optim.Adam(params, lr, betas, eps, weight_decay)` (amsgrad off, coupled L2 decay: the reference's
+    core/tools/train.py:202-208) as one multi-tensor HIP launch per step.  It IS a `torch.optim.Adam`: the per-parameter
+    state is torch's (`step` a 0-dim float32 CPU tensor, `exp_avg` / `exp_avg_sq` zeros like the parameter), so
+    `state_dict()` / `load_state_dict()` interchange with torch's optimiser in both directions.  `step` is counted per
+    parameter as torch counts it: a parameter without a gradient is skipped and falls behind (Base_Audio under
+    data.audio.dropout), and the two bias-correction factors go to the kernel per tensor, formed here in double.
+    `step(clip_grad=, grads_consumed=)` has `FusedSGD.step`'s contract.  Nothing synchronises with the device: `step` lives
+    on the host, the clip coefficient on the device.
+
+    Parameters that ALL live on the CPU (the CPU rehearsals of `TrainStep`) take the base class's own step, after
+    `torch.nn.utils.clip_grad_norm_` when `clip_grad` is set: that is torch's Adam, which this class is -- not a fallback to
+    an oracle.  CPU parameters mixed with GPU ones raise, like every other tensor the kernel cannot take."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False):
+        if amsgrad:
+            raise ValueError("FusedAdam: amsgrad=True is not implemented on the HIP path")
+        if isinstance(lr, bool) or not isinstance(lr, (int, float)):
+            raise ValueError("FusedAdam: lr must be a Python float (a tensor lr would be read back every step)")
+        super().__init__(params, lr=float(lr), betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False)
+        self.last_total_norm = None
+
+    @torch.no_grad()
+    def step(self, closure=None, clip_grad=None, grads_consumed=False):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        allp = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        if not allp:
+            return loss
+        if not any(p.is_cuda or p.grad.is_cuda for p in allp):
+            if clip_grad:
+                self.last_total_norm = torch.nn.utils.clip_grad_norm_(allp, clip_grad)
+            super().step()
+            return loss
+        gscale = None
+        if clip_grad:
+            ents = _entries(allp, False)
+            self.last_total_norm, gscale = _sqnorm_coef(ents, clip_grad, allp[0].device)
+            if not grads_consumed:
+                for a, n in _chunks(ents):
+                    call("tbn_opt_scale_grads", a, n, ptr(gscale), stream_ptr())
+                gscale = None
+        for group in self.param_groups:
+            params = [p for p in group["params"] if p.grad is not None]
+            if not params:
+                continue
+            beta1, beta2 = (float(b) for b in group["betas"])
+            lr = float(group["lr"])
+            for p in params:      # refuse before any `step` advances
+                _check(p, p.grad)
+                st = self.state[p]
+                if len(st) == 0:
+                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                _check(st["exp_avg"], st["exp_avg_sq"])
+                if st["exp_avg"].shape != p.shape or st["exp_avg_sq"].shape != p.shape:
+                    raise TbnHipError("FusedAdam: a loaded exp_avg / exp_avg_sq does not have its parameter's shape")
+                if st["step"].is_cuda:
+                    raise TbnHipError("FusedAdam: `step` lives on the device (a capturable / fused torch.optim.Adam state); "
+                                      "reading it would synchronise every step")
+            ents, moments = [], []
+            for p in params:
+                st = self.state[p]
+                st["step"] += 1
+                t = float(st["step"])
+                ents.append(AdamTensor(ptr(p), ptr(p.grad), ptr(st["exp_avg"]), ptr(st["exp_avg_sq"]), p.numel(),
+                                       lr / (1.0 - beta1 ** t), 1.0 / math.sqrt(1.0 - beta2 ** t)))
+                moments += [st["exp_avg"], st["exp_avg_sq"]]
+            for a, n in _chunks(ents, AdamTensor):
+                call("tbn_opt_adam_step", a, n, beta1, beta2, float(group["eps"]), float(group["weight_decay"]),
+                     ptr(gscale), stream_ptr())
+            # raw-pointer writes: tell autograd, as FusedSGD.step does
+            torch.autograd.graph.increment_version(params)
+            torch.autograd.graph.increment_version(moments)
         return loss

@@ -16,8 +16,9 @@ so for k = 2 the optimiser steps after iterations 0, 2, 4, ... and the gradients
 iteration i is clipped AGAIN (together with what iteration i + 1 added) before the step.  `TrainStep` reproduces exactly
 that schedule; nothing is "fixed".
 
-MI355X side: for k == 1 the clip is folded into the fused SGD launch (`FusedSGD.step(clip_grad=)`: the gradients are read
-once and not rescaled in memory -- legal because the next thing that happens to them is `zero_grad`); for k > 1 the
+MI355X side: for k == 1 the clip is folded into the fused optimiser launch (`FusedSGD.step(clip_grad=)` and
+`FusedAdam.step(clip_grad=)` alike: the gradients are read once and not rescaled in memory -- legal because the next thing
+that happens to them is `zero_grad`); for k > 1 the
 clipped gradients must persist into the next iteration, so the in-place multi-tensor `clip_grad_norm_` runs every
 iteration and `step()` on the stepping ones.
 
@@ -38,7 +39,7 @@ import contextlib
 
 import torch
 
-from .optim import FusedSGD, clip_grad_norm_
+from .optim import FusedAdam, FusedSGD, clip_grad_norm_
 
 
 class TrainStep:
@@ -82,7 +83,7 @@ class TrainStep:
             loss, batch_size = self.model.get_loss(self.criterion, target, out, epoch)
             loss["total"] = loss["total"] / self.k
             loss["total"].backward()
-        fused = isinstance(self.optimizer, FusedSGD) and self.k == 1 and self.clip_grad is not None
+        fused = isinstance(self.optimizer, (FusedSGD, FusedAdam)) and self.k == 1 and self.clip_grad is not None
         if self.clip_grad is not None and not fused:
             params = [p for p in self.model.parameters() if p.grad is not None]
             if params and params[0].grad.is_cuda:

@@ -11,12 +11,13 @@ fixture exists; known-answer tests in tests/test_host_cpu.py):
                             lr = base_lr * ((multiplier - 1) * epoch / total_epoch + 1)   (multiplier > 1)
   * afterwards: the wrapped scheduler, whose base learning rates become base_lr * multiplier and which is stepped with
     (epoch - total_epoch).
-Host arithmetic only: it drives `FusedSGD` (a torch.optim.Optimizer) unchanged.
+Host arithmetic only: it drives `FusedSGD` (a torch.optim.Optimizer) unchanged.  The Adam branch builds `FusedAdam` (a
+`torch.optim.Adam` on the same multi-tensor HIP launch) and, like the reference, no scheduler.
 """
 import torch
 from torch.optim.lr_scheduler import _LRScheduler
 
-from .optim import FusedSGD
+from .optim import FusedAdam, FusedSGD
 
 
 class GradualWarmupScheduler(_LRScheduler):
@@ -55,7 +56,8 @@ class GradualWarmupScheduler(_LRScheduler):
 def build_optimizer(cfg, model):
     """core/tools/train.py:190-217 -> (optimizer, lr_scheduler or None, scheduler_warmup or None).  "sgd": the fused
     multi-tensor HIP optimiser (`FusedSGD`: same update rule and state layout as `optim.SGD`) + `MultiStepLR`; "adam":
-    `torch.optim.Adam` (torch-ROCm; the reference's Adam branch has no scheduler)."""
+    `FusedAdam` (a `torch.optim.Adam` with torch's state layout, one HIP launch per step; the reference's Adam branch has no
+    scheduler)."""
     kind = cfg.train.optim.type.lower()
     lr_scheduler = scheduler_warmup = None
     if kind == "sgd":
@@ -64,8 +66,8 @@ def build_optimizer(cfg, model):
         lr_scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=list(cfg.train.scheduler.lr_steps),
                                                             gamma=cfg.train.scheduler.lr_decay)
     elif kind == "adam":
-        optimizer = torch.optim.Adam(model.parameters(), cfg.train.optim.lr, betas=(0.9, 0.999),
-                                     weight_decay=cfg.train.optim.weight_decay)
+        optimizer = FusedAdam(model.parameters(), cfg.train.optim.lr, betas=(0.9, 0.999),
+                              weight_decay=cfg.train.optim.weight_decay)
     else:
         raise ValueError(f"unknown optimiser '{cfg.train.optim.type}' (the reference knows 'sgd' and 'adam')")
     if lr_scheduler and cfg.train.warmup.enable:

@@ -3,12 +3,17 @@
 //
 //   core/tools/train.py:82-94   clip_grad_norm_(model.parameters(), cfg.train.clip_grad) ; optimizer.step()
 //   core/tools/train.py:190-202 optim.SGD(lr, momentum, weight_decay) (+ MultiStepLR: host arithmetic only)
+//   core/tools/train.py:202-208 optim.Adam(lr, betas=(0.9, 0.999), weight_decay) (no scheduler)
 //   core/utils/metric.py:137-157 top-k correctness + confusion matrix of one batch of class scores
 //
 // Multi-tensor: every parameter tensor of the model rides in ONE launch (the table is a kernel argument, a
 // workgroup finds its tensor with a scalar scan), 16 B per lane, HBM-bound: the update reads p, g, momentum and
-// writes p, momentum = 20 B per element.  The gradient-norm is a two-level fixed-order reduction (per-workgroup
-// partials, fp64 finalize), so the clipping coefficient never leaves the device and no float atomics are used.
+// writes p, momentum = 20 B per element (Adam: p, g and both moments, 28 B).  The gradient-norm is a two-level
+// fixed-order reduction (per-workgroup partials, fp64 finalize), so the clipping coefficient never leaves the device and
+// no float atomics are used.
+#include <cstdio>
+#include <cstdlib>
+
 #include "tbn_common.h"
 #include "../../include/tbn_hip.h"
 
@@ -57,7 +62,8 @@ static int fill_tab(OptTab* tab, const tbn_opt_tensor* t, int nt, bool need_p, b
   return TBN_OK;
 }
 
-__device__ __forceinline__ int find_tensor(const OptTab& tab, int b) {
+template <class Tab>
+__device__ __forceinline__ int find_tensor(const Tab& tab, int b) {
   int l = 0;
   while (l + 1 < tab.n && b >= tab.blk0[l + 1]) ++l;
   return l;
@@ -165,7 +171,132 @@ __global__ __launch_bounds__(256) void opt_sgd_kernel(OptTab tab, float lr, floa
   }
 }
 
+// ---------------------------------------------------------------- Adam (torch.optim.Adam, amsgrad off, coupled L2 decay)
+//   d = g * gscale + wd * p ; m += (1 - beta1) * (d - m) ; v = beta2 * v + (1 - beta2) * d * d
+//   p -= step_size * m / (sqrt(v) * inv_sqrt_bc2 + eps)          (both bias-correction factors per tensor, from the host)
+// reads p, g, m, v and writes p, m, v = 28 B per element; the access pattern is opt_sgd_kernel's
+struct AdamTab {
+  int n;
+  float* p[TBN_OPT_MAX_TENSORS];
+  const float* g[TBN_OPT_MAX_TENSORS];
+  float* m[TBN_OPT_MAX_TENSORS];
+  float* v[TBN_OPT_MAX_TENSORS];
+  unsigned long long len[TBN_OPT_MAX_TENSORS];
+  int blk0[TBN_OPT_MAX_TENSORS + 1];
+  float step_size[TBN_OPT_MAX_TENSORS];
+  float inv_sqrt_bc2[TBN_OPT_MAX_TENSORS];
+  unsigned char vec[TBN_OPT_MAX_TENSORS];   // all four pointers 16-byte aligned -> float4 path
+};
+// the table and the scalars behind it (5 floats, one pointer) travel as kernel arguments: 4 KB at most
+static_assert(sizeof(AdamTab) + 5 * sizeof(float) + sizeof(void*) + 8 <= 4096, "AdamTab exceeds the kernel-argument limit");
+
+static int fill_adam_tab(AdamTab* tab, const tbn_adam_tensor* t, int nt) {
+  if (nt < 0 || nt > TBN_OPT_MAX_TENSORS) {
+    tbn_set_error("optimizer: %d tensors per call (max %d)", nt, TBN_OPT_MAX_TENSORS);
+    return TBN_ERR_ARG;
+  }
+  tab->n = nt;
+  tab->blk0[0] = 0;
+  for (int i = 0; i < nt; ++i) {
+    if (t[i].grad == nullptr || t[i].param == nullptr || t[i].exp_avg == nullptr || t[i].exp_avg_sq == nullptr) {
+      tbn_set_error("optimizer: tensor %d has a null pointer", i);
+      return TBN_ERR_ARG;
+    }
+    const uintptr_t bits = (uintptr_t)t[i].grad | (uintptr_t)t[i].param | (uintptr_t)t[i].exp_avg | (uintptr_t)t[i].exp_avg_sq;
+    if (bits & 3u) {
+      tbn_set_error("optimizer: tensor %d is not 4-byte aligned", i);
+      return TBN_ERR_ARG;
+    }
+    tab->vec[i] = (bits & 15u) == 0 ? 1 : 0;   // gradient slices of a larger tensor: scalar path (see fill_tab)
+    tab->p[i] = (float*)t[i].param;
+    tab->g[i] = (const float*)t[i].grad;
+    tab->m[i] = (float*)t[i].exp_avg;
+    tab->v[i] = (float*)t[i].exp_avg_sq;
+    tab->len[i] = t[i].count;
+    tab->step_size[i] = t[i].step_size;
+    tab->inv_sqrt_bc2[i] = t[i].inv_sqrt_bc2;
+    const size_t blocks = (t[i].count + OPT_CHUNK - 1) / OPT_CHUNK;
+    if (blocks > (1u << 20) || tab->blk0[i] + (long)blocks > (1l << 30)) {
+      tbn_set_error("optimizer: tensor %d too large", i);
+      return TBN_ERR_ARG;
+    }
+    tab->blk0[i + 1] = tab->blk0[i] + (int)blocks;
+  }
+  return TBN_OK;
+}
+
+__global__ __launch_bounds__(256) void opt_adam_kernel(AdamTab tab, float beta2, float omb1, float omb2, float eps, float wd,
+                                                       const float* __restrict__ gscale) {
+  const float gs = gscale != nullptr ? gscale[0] : 1.f;
+  const int l = find_tensor(tab, blockIdx.x);
+  const size_t n = tab.len[l];
+  const size_t beg = (size_t)(blockIdx.x - tab.blk0[l]) * OPT_CHUNK;
+  const size_t end = beg + OPT_CHUNK < n ? beg + OPT_CHUNK : n;
+  float* p = tab.p[l];
+  const float* g = tab.g[l];
+  float* m = tab.m[l];
+  float* v = tab.v[l];
+  const float step_size = tab.step_size[l], isb2 = tab.inv_sqrt_bc2[l];
+  auto upd = [&](float pv, float gv, float mv, float vv, float& pn, float& mn, float& vn) {
+    float d = gs == 1.f ? gv : gv * gs;
+    if (wd != 0.f) d = fmaf(wd, pv, d);              // torch: grad.add(param, alpha=wd)
+    mn = fmaf(omb1, d - mv, mv);                     // torch: exp_avg.lerp_(grad, 1 - beta1)
+    vn = fmaf(omb2 * d, d, beta2 * vv);              // torch: exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+    const float denom = fmaf(sqrtf(vn), isb2, eps);  // torch: (exp_avg_sq.sqrt() / sqrt(bias_correction2)).add_(eps)
+    pn = fmaf(-step_size, mn / denom, pv);           // torch: param.addcdiv_(exp_avg, denom, value=-step_size)
+  };
+  const size_t end4 = tab.vec[l] ? beg + ((end - beg) & ~(size_t)3) : beg;
+  for (size_t i = beg + (size_t)threadIdx.x * 4; i < end4; i += 1024) {
+    const float4 pv = tbn_ld4<(TBN_BN_NT & 8) != 0>(p + i);
+    const float4 gv = tbn_ld4<(TBN_BN_NT & 8) != 0>(g + i);
+    const float4 mv = tbn_ld4<(TBN_BN_NT & 8) != 0>(m + i);
+    const float4 vv = tbn_ld4<(TBN_BN_NT & 8) != 0>(v + i);
+    float4 pn, mn, vn;
+    upd(pv.x, gv.x, mv.x, vv.x, pn.x, mn.x, vn.x);
+    upd(pv.y, gv.y, mv.y, vv.y, pn.y, mn.y, vn.y);
+    upd(pv.z, gv.z, mv.z, vv.z, pn.z, mn.z, vn.z);
+    upd(pv.w, gv.w, mv.w, vv.w, pn.w, mn.w, vn.w);
+    *reinterpret_cast<float4*>(p + i) = pn;
+    *reinterpret_cast<float4*>(m + i) = mn;
+    *reinterpret_cast<float4*>(v + i) = vn;
+  }
+  for (size_t i = end4 + threadIdx.x; i < end; i += 256) {
+    float pn, mn, vn;
+    upd(p[i], g[i], m[i], v[i], pn, mn, vn);
+    p[i] = pn;
+    m[i] = mn;
+    v[i] = vn;
+  }
+}
+
+// 1 - beta in double from the shortest decimal that rounds to the float `beta`: the float carries a rounding error of up to
+// 2^-25, which is 1.3e-5 of 1 - 0.999 -- exp_avg_sq would be that far from torch's, whose 1 - beta2 is formed in double.
+// For a beta written with up to 7 digits this is the caller's own number; for any other it is as exact as the float.
+static float one_minus_beta(float beta) {
+  char s[32];
+  for (int digits = 1; digits <= 9; ++digits) {
+    snprintf(s, sizeof(s), "%.*g", digits, (double)beta);
+    if (strtof(s, nullptr) == beta) break;
+  }
+  return (float)(1.0 - strtod(s, nullptr));
+}
+
 extern "C" {
+
+int tbn_opt_adam_step(const tbn_adam_tensor* tensors, int num_tensors, float beta1, float beta2, float eps,
+                      float weight_decay, const float* grad_scale, void* stream) {
+  TBN_REQUIRE(tensors != nullptr || num_tensors == 0, "opt_adam_step: null argument");
+  TBN_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f,
+              "opt_adam_step: betas must lie in [0, 1) and eps be non-negative");
+  AdamTab tab;
+  int rc = fill_adam_tab(&tab, tensors, num_tensors);
+  if (rc != TBN_OK) return rc;
+  if (tab.blk0[tab.n] == 0) return TBN_OK;
+  TBN_KLAUNCH(opt_adam_kernel, dim3(tab.blk0[tab.n]), dim3(256), 0, (hipStream_t)stream, tab, beta2,
+              one_minus_beta(beta1), one_minus_beta(beta2), eps, weight_decay, grad_scale);
+  TBN_CHECK_LAUNCH("opt_adam_step");
+  return TBN_OK;
+}
 
 int tbn_opt_num_partials(const tbn_opt_tensor* tensors, int num_tensors) {
   long b = 0;

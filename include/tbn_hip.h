@@ -751,6 +751,29 @@ int tbn_opt_scale_grads(const tbn_opt_tensor* tensors, int num_tensors, const fl
 /* d = grad * grad_scale[0] (1 if NULL) + weight_decay * p ; m = momentum * m + d ; p -= lr * m */
 int tbn_opt_sgd_step(const tbn_opt_tensor* tensors, int num_tensors, float lr, float momentum, float weight_decay,
                      const float* grad_scale, void* stream);
+/* Multi-tensor Adam: torch.optim.Adam(lr, betas, eps, weight_decay) with amsgrad=False, maximize=False and coupled L2
+ * decay, all tensors of a call in one launch (layout rules of tbn_opt_sgd_step; 28 B per element).  Per element
+ *   d = grad * grad_scale[0] (1 if NULL) + weight_decay * p
+ *   m = m + (1 - beta1) * (d - m)
+ *   v = beta2 * v + (1 - beta2) * d * d
+ *   p = p - step_size * m / (sqrt(v) * inv_sqrt_bc2 + eps)
+ * The bias correction is PER TENSOR: torch counts `step` per parameter, and a parameter that had no gradient in some
+ * iteration (Base_Audio under data.audio.dropout) falls behind the others; the caller forms both factors in double
+ * from each tensor's own count.  1 - beta is formed in double from the shortest decimal that rounds to the float
+ * argument (0.999f -> 0.999): 1 - 0.999f itself is 1.3e-5 off 1 - 0.999, which exp_avg_sq would carry.
+ * exp_avg / exp_avg_sq start as zeros.  count == 0 entries and num_tensors == 0 launch nothing.
+ * replaces: core/tools/train.py:202-208 (optim.Adam(model.parameters(), lr, betas=(0.9, 0.999), weight_decay)) */
+typedef struct tbn_adam_tensor {
+  void* param;          /* fp32 parameter */
+  const void* grad;     /* fp32 gradient */
+  void* exp_avg;        /* fp32 first moment */
+  void* exp_avg_sq;     /* fp32 second moment */
+  size_t count;         /* elements */
+  float step_size;      /* lr / (1 - beta1^step), step = this tensor's count AFTER the increment */
+  float inv_sqrt_bc2;   /* 1 / sqrt(1 - beta2^step) */
+} tbn_adam_tensor;
+int tbn_opt_adam_step(const tbn_adam_tensor* tensors, int num_tensors, float beta1, float beta2, float eps,
+                      float weight_decay, const float* grad_scale, void* stream);
 /* Metric._get_correct_score (core/utils/metric.py:137-157): scores (batch, classes) pitch scores_ld, target int64.
  * correct (k, batch) uint8 = [j-th ranked class == target]; pred (k, batch) int64 ranked classes (may be NULL);
  * conf_mat (classes, classes) float, conf_mat[target][top1] += 1 (may be NULL).  Ties rank the lower index first. */
