@@ -79,6 +79,12 @@ class AdamTensor(C.Structure):
                 ("step_size", c_f), ("inv_sqrt_bc2", c_f)]
 
 
+class JpegGeometry(C.Structure):
+    """include/tbn_hip.h tbn_jpeg_geometry"""
+    _fields_ = [("width", c_i), ("height", c_i), ("components", c_i), ("hsamp", c_i * 3), ("vsamp", c_i * 3),
+                ("blocks_w", c_i * 3), ("blocks_h", c_i * 3), ("restart_interval", c_i), ("coef_count", c_sz)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/tbn_hip.h
 SIGNATURES = {
     "tbn_version": (c_i, []),
@@ -202,6 +208,11 @@ SIGNATURES = {
     "tbn_frames_to_tensor": (c_i, [c_fp] + [c_i] * 16 + [c_fp, c_fp, c_i, c_i, c_fp, c_fp]),
     "tbn_frames_to_tensor_crops": (c_i, [c_fp] + [c_i] * 10 + [C.POINTER(c_i), C.POINTER(c_i)] + [c_i] * 5 +
                                    [c_fp, c_fp, c_i, c_i, c_fp, c_fp]),
+    # reference core/dataset/dataset.py:303-305, :355-370 (cv2.imread): host parse / Huffman, device IDCT / upsampling / colour
+    "tbn_jpeg_parse": (c_i, [C.c_char_p, c_sz, C.POINTER(JpegGeometry)]),
+    "tbn_jpeg_entropy_decode": (c_i, [C.c_char_p, c_sz, C.POINTER(JpegGeometry), c_fp, c_fp]),
+    "tbn_jpeg_workspace_bytes": (c_sz, [C.POINTER(JpegGeometry), c_i]),
+    "tbn_jpeg_reconstruct": (c_i, [c_fp, c_fp, c_i, C.POINTER(JpegGeometry), c_i, c_fp, c_fp, c_fp]),
 }
 
 _lib = None

@@ -4,3 +4,4 @@ from .prior import attention_prior, gaussian_kernel  # noqa: F401
 from .audio import AudioSegments, audio_windows, window_table  # noqa: F401
 from .transform import (CenterCrop, DevicePipeline, FixedCrop, MultiScaleCrop, Normalize, RandomCrop,  # noqa: F401
                         RandomHorizontalFlip, Rescale, Stack, ToTensor, TransferTensorDict, get_transforms)
+from .frames import FrameReader, decode_jpegs  # noqa: F401

@@ -813,6 +813,53 @@ int tbn_frames_to_tensor_crops(const unsigned char* frames, int n_img, int heigh
                                const float* mean, const float* std_dev, int n_stat, int div255, float* out,
                                void* stream);
 
+/* ---- baseline JPEG decode into device frames (the step in front of tbn_frames_to_tensor) ---------- */
+/* Replaces cv2.imread of reference core/dataset/dataset.py:303-305 (RGB: 3 channels B, G, R) and :355-370 (Flow:
+ * cv2.imread(path, 0), gray), i.e. libjpeg-turbo at its defaults -- ISLOW integer IDCT, "fancy" triangle upsampling,
+ * fixed-point YCbCr -> RGB -- byte for byte.  The serial half (markers, Huffman) is host code and needs no GPU; the
+ * half after the quantised coefficients is two kernels.  Supported: SOF0, 8-bit, Huffman, one interleaved scan; 1
+ * component, or 3 components YCbCr with luma 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0) and chroma 1x1; restart intervals,
+ * 0xFF00 stuffing and fill bytes before markers.  Refused with a message naming the reason (TBN_ERR_UNSUPPORTED:
+ * progressive and other SOFn, arithmetic coding, 12-bit, 4 components, other sampling, several scans; TBN_ERR_ARG: a
+ * missing table, a DC coefficient outside int16, a stream that ends early or meets a marker inside the scan data).
+ * There is no capability bit: callers detect the feature by the symbol. */
+#ifndef TBN_JPEG_GEOMETRY_DEFINED
+#define TBN_JPEG_GEOMETRY_DEFINED
+typedef struct tbn_jpeg_geometry {
+  int width, height;          /* true image size in pixels */
+  int components;             /* 1 (gray) or 3 (YCbCr) */
+  int hsamp[3], vsamp[3];     /* sampling factors per component (a 1-component file: 1 x 1) */
+  int blocks_w[3], blocks_h[3]; /* 8x8-block extents of each component plane, padded to whole MCUs */
+  int restart_interval;       /* MCUs between restart markers, 0: none (informational, not compared) */
+  size_t coef_count;          /* int16 coefficients of one image: 64 * sum(blocks_w * blocks_h) */
+} tbn_jpeg_geometry;
+#endif
+/* HOST.  Parses SOI, APPn / COM (skipped), DQT, SOF0, DHT, DRI and SOS of `size` untrusted bytes and fills `out`.
+ * replaces: the header half of cv2.imread, core/dataset/dataset.py:305, :360, :365 */
+int tbn_jpeg_parse(const unsigned char* data, size_t size, tbn_jpeg_geometry* out);
+/* HOST, thread-safe (no global state; the error string is thread-local).  Decodes the scan into
+ * coef[expect->coef_count]: QUANTISED coefficients in natural (de-zigzagged) order, per component plane
+ * [block_row][block_col][64], planes one after the other; and quant[components * 64]: the image's quantisation tables
+ * per component in natural order (per image: a batch may mix qualities).  Refuses an image whose size, component
+ * count or sampling differs from `expect`.  Writes nothing outside coef[0, coef_count) and quant[0, components * 64).
+ * replaces: the entropy-decoding half of cv2.imread, core/dataset/dataset.py:305, :360, :365 */
+int tbn_jpeg_entropy_decode(const unsigned char* data, size_t size, const tbn_jpeg_geometry* expect, int16_t* coef,
+                            uint16_t* quant);
+/* bytes of workspace tbn_jpeg_reconstruct needs for n_img images of this geometry (the uint8 component planes,
+ * block-padded: coef_count bytes per image); 0 for a geometry it would refuse */
+size_t tbn_jpeg_workspace_bytes(const tbn_jpeg_geometry* geometry, int n_img);
+/* DEVICE.  n_img images of ONE geometry: coef_dev (n_img, coef_count) int16 and quant_dev (n_img, components, 64)
+ * uint16 in the layouts of tbn_jpeg_entropy_decode, both and the workspace 16-byte aligned.  Kernel A: dequantisation
+ * and the ISLOW 8x8 IDCT into the workspace planes.  Kernel B: h2v1 / h2v2 fancy upsampling of the chroma's true
+ * downsampled extent, YCbCr -> B, G, R, interleaved and cropped: frames_dev (n_img, height, width, out_channels) uint8.
+ * out_channels 3: B, G, R; a 1-component file is replicated to the three channels (cv2.imread(path)).  out_channels
+ * 1: a 3-component file delivers its luma plane and its chroma is not reconstructed (cv2.imread(path, 0)).  Integer
+ * arithmetic that wraps: corrupt coefficients give garbage pixels, never a fault; every address depends on the
+ * geometry alone.  replaces: the reconstruction half of cv2.imread, core/dataset/dataset.py:305, :360, :365 */
+int tbn_jpeg_reconstruct(const int16_t* coef_dev, const uint16_t* quant_dev, int n_img,
+                         const tbn_jpeg_geometry* geometry, int out_channels, unsigned char* frames_dev,
+                         void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
