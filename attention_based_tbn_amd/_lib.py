@@ -213,6 +213,12 @@ SIGNATURES = {
     "tbn_jpeg_entropy_decode": (c_i, [C.c_char_p, c_sz, C.POINTER(JpegGeometry), c_fp, c_fp]),
     "tbn_jpeg_workspace_bytes": (c_sz, [C.POINTER(JpegGeometry), c_i]),
     "tbn_jpeg_reconstruct": (c_i, [c_fp, c_fp, c_i, C.POINTER(JpegGeometry), c_i, c_fp, c_fp, c_fp]),
+    # opt-in Huffman decoding on the device (csrc/jpeg_entropy.hip): host pack stage, then one workgroup per image
+    "tbn_jpeg_scan_pack_bytes": (c_sz, [c_sz, c_i]),
+    "tbn_jpeg_scan_pack": (c_i, [C.c_char_p, c_sz, C.POINTER(JpegGeometry), c_fp, c_sz, c_i, c_fp, C.POINTER(c_i),
+                                 C.POINTER(c_sz)]),
+    "tbn_jpeg_entropy_workspace_bytes": (c_sz, [C.POINTER(JpegGeometry), c_i]),
+    "tbn_jpeg_entropy_decode_dev": (c_i, [c_fp, c_sz, c_fp, c_i, C.POINTER(JpegGeometry), c_i, c_fp, c_fp, c_fp, c_fp, c_fp]),
 }
 
 _lib = None

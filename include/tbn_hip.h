@@ -860,6 +860,47 @@ int tbn_jpeg_reconstruct(const int16_t* coef_dev, const uint16_t* quant_dev, int
                          const tbn_jpeg_geometry* geometry, int out_channels, unsigned char* frames_dev,
                          void* workspace, void* stream);
 
+/* ---- JPEG Huffman decoding on the device (opt-in; the default is tbn_jpeg_entropy_decode on host threads) ---------- */
+/* A Huffman stream has no sync points but synchronises itself: a decoder started at a wrong bit usually falls onto true
+ * codeword boundaries after a few symbols (Weissenberger & Schmidt, ICPP 2018 and HiPC 2021).  The unstuffed scan is cut
+ * into intervals (the whole scan, or one restart interval) and every interval into subsequences of S bits, one lane
+ * each; every lane decodes from a guessed state (bit, block of the MCU, zigzag index), hands the state it ends in to
+ * the next lane, and the rounds repeat until no lane's start changes -- at most as many rounds as lanes, and at that
+ * fixed point the result IS the sequential decode.  csrc/tbn_jpeg_sync.h has the record layout and the decoder core.
+ * There is no capability bit: callers detect the feature by the symbol.
+ * bytes of the record of a file of `file_size` bytes with `n_intervals` intervals (ceil(MCUs / restart interval), or 1),
+ * a multiple of 16 */
+size_t tbn_jpeg_scan_pack_bytes(size_t file_size, int n_intervals);
+/* HOST, thread-safe.  Parses as tbn_jpeg_entropy_decode does and, instead of decoding, packs what the device decoder
+ * reads into record[0, record_bytes) (16-byte aligned; pinned memory if it is to be copied asynchronously): a header,
+ * the image's own Huffman tables in lookup form, the interval table (start bit, bit length), and the entropy-coded
+ * bytes with 0xFF00 stuffing, fill bytes and RSTn markers removed (the markers' order is checked; a missing EOI is
+ * refused).  quant[components * 64]: as tbn_jpeg_entropy_decode writes it.  *n_intervals: the image's interval count;
+ * *used: the bytes of the record written.  An image of more than `max_intervals` intervals (the device decoder takes at
+ * most 1024) is NOT packed: the return is 0 and *used is 0.  Refusals: the codes and the wording of
+ * tbn_jpeg_entropy_decode.  Writes nothing outside record[0, record_bytes) and quant[0, components * 64). */
+int tbn_jpeg_scan_pack(const unsigned char* data, size_t size, const tbn_jpeg_geometry* expect, void* record,
+                       size_t record_bytes, int max_intervals, uint16_t* quant, int* n_intervals, size_t* used);
+/* bytes of workspace tbn_jpeg_entropy_decode_dev needs (16 per image: the subsequence size it chose, lanes, rounds,
+ * whether the scan was staged in LDS, as uint32); 0 for a geometry it would refuse */
+size_t tbn_jpeg_entropy_workspace_bytes(const tbn_jpeg_geometry* geometry, int n_img);
+/* DEVICE.  n_img images of ONE geometry.  packed_dev[0, packed_bytes): the records (16-byte aligned);
+ * offsets_dev[n_img]: byte offset of each image's record, a multiple of 16, or 0xFFFFFFFF for an image without one
+ * (status 64, nothing written for it but zeros).  subseq_bits: S; 0 = 1024, else a multiple of 32, >= 64; it grows in
+ * steps of 32 for an image whose lanes would otherwise exceed 1024.  One workgroup per image, one launch (after a
+ * hipMemsetAsync of coef_dev): relaxation rounds, block-count scan, validation, the write pass, DC prefix sums.
+ * coef_dev (n_img, coef_count) int16, 16-byte aligned: the layout of tbn_jpeg_entropy_decode, what tbn_jpeg_reconstruct
+ * takes.  status_dev[n_img]: 0 = decoded, identical to tbn_jpeg_entropy_decode's coefficients; otherwise bits 1: invalid
+ * code, 2: AC run leaves the block, 4: an interval's block total differs from the geometry's, 8: an interval ends more
+ * than 7 bits after its last block or runs out of bits, 16: DC outside int16, 32: inconsistent record, 64: no record --
+ * such an image is for the host stage (its coefficients here are unspecified).  info_dev (n_img, 2): lanes, rounds.
+ * A corrupt stream costs a status, never an access outside the image's coefficients.  Strictness: stray bytes between
+ * the last block and the next marker are judged by the host stage according to its refill state; this path may accept
+ * such a file where the host stage refuses it, never the reverse without a non-zero status. */
+int tbn_jpeg_entropy_decode_dev(const void* packed_dev, size_t packed_bytes, const uint32_t* offsets_dev, int n_img,
+                                const tbn_jpeg_geometry* geometry, int subseq_bits, int16_t* coef_dev, int* status_dev,
+                                int* info_dev, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
