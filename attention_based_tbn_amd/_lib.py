@@ -85,6 +85,12 @@ class JpegGeometry(C.Structure):
                 ("blocks_w", c_i * 3), ("blocks_h", c_i * 3), ("restart_interval", c_i), ("coef_count", c_sz)]
 
 
+class FramesClip(C.Structure):
+    """include/tbn_hip.h tbn_frames_clip: one row of the geometry table of tbn_frames_to_tensor_batch"""
+    _fields_ = [("first_img", c_i), ("box_x", c_i), ("box_y", c_i), ("box_w", c_i), ("box_h", c_i), ("resized_w", c_i),
+                ("resized_h", c_i), ("crop_x", c_i), ("crop_y", c_i), ("flip", c_i), ("out_row", c_i), ("reserved", c_i)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/tbn_hip.h
 SIGNATURES = {
     "tbn_version": (c_i, []),
@@ -208,6 +214,9 @@ SIGNATURES = {
     "tbn_frames_to_tensor": (c_i, [c_fp] + [c_i] * 16 + [c_fp, c_fp, c_i, c_i, c_fp, c_fp]),
     "tbn_frames_to_tensor_crops": (c_i, [c_fp] + [c_i] * 10 + [C.POINTER(c_i), C.POINTER(c_i)] + [c_i] * 5 +
                                    [c_fp, c_fp, c_i, c_i, c_fp, c_fp]),
+    # reference core/dataset/dataset.py:512-532 (_transform_data, once per sample): a batch of clips, one geometry each
+    "tbn_frames_to_tensor_batch": (c_i, [c_fp] + [c_i] * 4 + [C.POINTER(FramesClip), c_fp] + [c_i] * 5 +
+                                   [c_fp, c_fp, c_i, c_i, c_fp, c_i, c_fp]),
     # reference core/dataset/dataset.py:303-305, :355-370 (cv2.imread): host parse / Huffman, device IDCT / upsampling / colour
     "tbn_jpeg_parse": (c_i, [C.c_char_p, c_sz, C.POINTER(JpegGeometry)]),
     "tbn_jpeg_entropy_decode": (c_i, [C.c_char_p, c_sz, C.POINTER(JpegGeometry), c_fp, c_fp]),

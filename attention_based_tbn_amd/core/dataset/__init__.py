@@ -4,4 +4,5 @@ from .prior import attention_prior, gaussian_kernel  # noqa: F401
 from .audio import AudioSegments, audio_windows, window_table  # noqa: F401
 from .transform import (CenterCrop, DevicePipeline, FixedCrop, MultiScaleCrop, Normalize, RandomCrop,  # noqa: F401
                         RandomHorizontalFlip, Rescale, Stack, ToTensor, TransferTensorDict, get_transforms)
-from .frames import FrameReader, decode_jpegs  # noqa: F401
+from .frames import FrameReader, decode_jpegs, jpeg_geometry  # noqa: F401
+from .dataset import EpicVideoRecord, Video_Dataset, read_wav  # noqa: F401

@@ -48,6 +48,21 @@ def _same(a, b):
            (b.width, b.height, b.components, list(b.hsamp), list(b.vsamp))
 
 
+def jpeg_geometry(blob):
+    """`tbn_jpeg_parse` of one file (host only, no GPU): the `JpegGeometry` `decode_jpegs` groups by -- files of one
+    width, height, component count and sampling decode in one call.  Raises the parser's refusal."""
+    blob = blob if isinstance(blob, bytes) else bytes(blob)
+    g = JpegGeometry()
+    if lib().tbn_jpeg_parse(blob, len(blob), ctypes.byref(g)) != 0:
+        raise TbnHipError(f"jpeg_geometry: {_last_error()}")
+    return g
+
+
+def geometry_key(geo):
+    """what makes two files one `decode_jpegs` batch: (width, height, components, hsamp, vsamp)"""
+    return (geo.width, geo.height, geo.components, tuple(geo.hsamp), tuple(geo.vsamp))
+
+
 def decode_jpegs(blobs, gray=False, device="cuda", threads=8, entropy="host"):
     """list of `bytes` (baseline JPEG files of ONE geometry) -> uint8 (n, H, W, 1 if gray else 3) on `device`.
 

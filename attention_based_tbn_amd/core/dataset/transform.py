@@ -6,7 +6,8 @@ stack, `/255`, normalise) and ships fp32 tensors to the GPU.  Here every transfo
 (same constructor arguments, same NumPy RNG draws in the same order, so a seeded run picks the same crop box and
 flip); the pixels move to the device as uint8 (4x fewer PCIe bytes) and ONE HIP kernel (`tbn_frames_to_tensor`)
 produces the normalised fp32 NCHW tensor.  `get_transforms(cfg, modality, mode)` returns the same dictionary of
-callables as the reference.  No CPU fallback: the pipeline raises without a GPU.
+callables as the reference.  No CPU fallback: the pipeline raises without a GPU.  `DevicePipeline.batch` does the
+same for every clip of a batch in one launch (`tbn_frames_to_tensor_batch`), one recorded geometry per clip.
 
 `FixedCrop` (the reference's multi-crop test-time augmentation) records a list of windows; the pipeline then calls
 `tbn_frames_to_tensor_crops`, one launch for all of them.  The reference's own compositions (`core/tools/test.py:136-171`:
@@ -20,7 +21,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from ..._lib import TbnHipError, call, ptr, stream_ptr
+from ..._lib import FramesClip, TbnHipError, call, ptr, stream_ptr
 
 
 class _Geometry:
@@ -319,6 +320,124 @@ class DevicePipeline(object):
         mean, std = self._stats()
         return _frames_to_tensor(img_list, geo, self.channels, self.stack, mean, std, True, self.device)
 
+    def _record(self, h, w):
+        """the recorded geometry of ONE clip of (h, w) frames: the NumPy draws of one `__call__`, no GPU"""
+        geo = _Geometry(h, w)
+        for t in self.geometry:
+            t(geo)
+        return geo
+
+    def _record_batch(self, sizes):
+        """sizes: (h, w) per clip, in batch order -> one `_Geometry` per clip, recorded clip after clip: the NumPy draws
+        of len(sizes) consecutive `__call__`s.  Host only."""
+        return [self._record(int(h), int(w)) for h, w in sizes]
+
+    def batch(self, frames, n_clips, clips=None):
+        """The clips of a whole batch in one launch (`tbn_frames_to_tensor_batch`): the reference applies
+        `_transform_data` once per sample (dataset.py:512-532), each with its own crop box and flip.
+
+        frames   a uint8 tensor (n_clips * imgs_per_clip, H, W, C), or a list of such tensors, one per GROUP of clips
+                 that share a source frame size (a batch with two frame sizes: two groups, two launches into the same
+                 output);
+        clips    with a list: per group, the batch positions of its clips (`[[0, 2], [1]]`), each clip's images
+                 consecutive in its group's tensor; default: the groups hold the clips in batch order.
+        Returns fp32 (n_clips, imgs_per_clip / stack, C * stack, h, w) on the device.  One geometry is recorded per clip,
+        clip after clip in batch order, so the NumPy draws are those of n_clips consecutive `__call__`s, and every row
+        equals what `__call__` returns for that clip, bit for bit.
+
+        A pipeline ending in `FixedCrop` (5 / 10-crop testing) has no batched kernel: it loops over the existing
+        `tbn_frames_to_tensor_crops` entry, one launch per clip, and stacks the results."""
+        groups = list(frames) if isinstance(frames, (list, tuple)) else [frames]
+        if n_clips < 1 or not groups:
+            raise TbnHipError(f"input pipeline: a batch of {n_clips} clips in {len(groups)} groups")
+        for g in groups:
+            if not isinstance(g, torch.Tensor) or g.dim() != 4:
+                raise TbnHipError("input pipeline: batch() takes uint8 tensors (n, H, W, C)")
+        total = sum(int(g.shape[0]) for g in groups)
+        if total % n_clips != 0:
+            raise TbnHipError(f"input pipeline: {total} frames do not divide into {n_clips} clips")
+        per_clip = total // n_clips
+        if clips is None:
+            clips, first = [], 0
+            for g in groups:
+                if int(g.shape[0]) % per_clip != 0:
+                    raise TbnHipError(f"input pipeline: a group of {int(g.shape[0])} frames for clips of {per_clip}")
+                clips.append(list(range(first, first + int(g.shape[0]) // per_clip)))
+                first += len(clips[-1])
+        if sorted(b for part in clips for b in part) != list(range(n_clips)) or len(clips) != len(groups) or \
+                any(len(part) * per_clip != int(g.shape[0]) for part, g in zip(clips, groups)):
+            raise TbnHipError(f"input pipeline: the groups {clips} do not hold each of the {n_clips} clips once")
+        sizes = [None] * n_clips
+        for part, g in zip(clips, groups):
+            for b in part:
+                sizes[b] = (int(g.shape[1]), int(g.shape[2]))
+        return self._run_batch(groups, clips, self._record_batch(sizes))
+
+    def _clip_table(self, geos, clips, per_clip):
+        """The geometry table of `tbn_frames_to_tensor_batch` (include/tbn_hip.h tbn_frames_clip), group after group:
+        row k is a clip's recorded geometry, its first image inside its group's tensor and its first output row.
+        Returns (table, first table row per group, (out_w, out_h)).  Host only."""
+        rows_per_clip = per_clip // self.stack
+        table = (FramesClip * len(geos))()
+        ow = oh = None
+        k, starts = 0, []
+        for part in clips:
+            starts.append(k)
+            for slot, b in enumerate(part):
+                geo = geos[b]
+                rw, rh = geo.resized if geo.resized is not None else (geo.box[2], geo.box[3])
+                cx, cy, w, h = geo.crop if geo.crop is not None else (0, 0, rw, rh)
+                if ow is None:
+                    ow, oh = w, h
+                if (w, h) != (ow, oh):
+                    raise TbnHipError(f"input pipeline: clip {b} comes out {w}x{h}, clip {clips[0][0]} {ow}x{oh}: the "
+                                      "clips of a batch must share one output size")
+                table[k] = FramesClip(slot * per_clip, geo.box[0], geo.box[1], geo.box[2], geo.box[3], rw, rh, cx, cy,
+                                      int(geo.flip), b * rows_per_clip, 0)
+                k += 1
+        return table, starts, (ow, oh)
+
+    def _run_batch(self, groups, clips, geos):
+        """groups / clips as in `batch`, geos: the recorded `_Geometry` per clip in batch order -> the batch tensor"""
+        if not torch.cuda.is_available():
+            raise TbnHipError("input pipeline: needs an MI355X (no CPU fallback)")
+        n_clips = len(geos)
+        per_clip = sum(int(g.shape[0]) for g in groups) // n_clips
+        mean, std = self._stats()
+        if any(geo.windows is not None for geo in geos):        # FixedCrop: the per-clip multi-window entry, stacked
+            rows = [None] * n_clips
+            for part, g in zip(clips, groups):
+                for slot, b in enumerate(part):
+                    rows[b] = _frames_to_tensor(g[slot * per_clip:(slot + 1) * per_clip], geos[b], self.channels,
+                                                self.stack, mean, std, True, self.device)
+            return torch.stack(rows, 0)
+        if per_clip % self.stack != 0:
+            raise TbnHipError(f"input pipeline: {per_clip} frames per clip is not a multiple of the stack length "
+                              f"{self.stack}")
+        rows_per_clip = per_clip // self.stack
+        for part, g in zip(clips, groups):
+            for b in part:
+                if (int(g.shape[1]), int(g.shape[2])) != (geos[b].src_h, geos[b].src_w):
+                    raise TbnHipError(f"input pipeline: geometry recorded for {geos[b].src_h}x{geos[b].src_w} frames, "
+                                      f"got {int(g.shape[1])}x{int(g.shape[2])}")
+        table, starts, (ow, oh) = self._clip_table(geos, clips, per_clip)
+        out = torch.empty((n_clips, rows_per_clip, self.channels * self.stack, oh, ow), dtype=torch.float32,
+                          device=self.device)
+        with torch.cuda.device(self.device):
+            # the one copy of the table; every group's launch reads its own rows of it
+            table_dev = torch.frombuffer(table, dtype=torch.uint8).to(self.device, non_blocking=False)
+            row = ctypes.sizeof(FramesClip)
+            for start, part, g in zip(starts, clips, groups):
+                if g.dtype != torch.uint8 or g.shape[3] != self.channels:
+                    raise TbnHipError(f"input pipeline: expected uint8 frames (n, H, W, {self.channels}), got "
+                                      f"{g.dtype} {tuple(g.shape)}")
+                g = g.to(self.device, non_blocking=True).contiguous()
+                host_rows = ctypes.cast(ctypes.addressof(table) + start * row, ctypes.POINTER(FramesClip))
+                call("tbn_frames_to_tensor_batch", ptr(g), int(g.shape[0]), int(g.shape[1]), int(g.shape[2]),
+                     self.channels, host_rows, ptr(table_dev) + start * row, len(part), per_clip, ow, oh, self.stack,
+                     ptr(mean), ptr(std), mean.numel(), 1, ptr(out), n_clips * rows_per_clip, stream_ptr())
+        return out
+
 
 class AudioToTensor(object):
     """Stack + ToTensor(is_audio=True) of the reference for spectrograms: list of (256, W) arrays -> (n, 1, 256, W)"""
@@ -412,10 +531,12 @@ class TransferTensorDict(object):
         return tensor_dict
 
 
-def get_transforms(cfg, modality, mode="test", device="cuda", test_crops=1):
+def get_transforms(cfg, modality, mode="test", device="cuda", test_crops=1, flow_length=10):
     """reference create_dataloader.py:19-81: the same compositions per modality and mode.  `test_crops` (modes other
     than train): 1 = CenterCrop, 5 = FixedCrop at the centre and the four corners, 10 = the same, each followed by
-    its mirror image (the block commented out at reference core/tools/test.py:142-146)"""
+    its mirror image (the block commented out at reference core/tools/test.py:142-146).  `flow_length`: the images
+    `Stack("Flow")` makes one sample of; the reference leaves it at Stack's default of 10 = 2 * win_length at the
+    default win_length of 5, `create_dataloader` here passes 2 * cfg.data.flow.win_length."""
     if mode != "train" and test_crops not in (1, 5, 10):
         raise TbnHipError(f"get_transforms: test_crops={test_crops!r}, expected 1, 5 or 10")
     transforms = OrderedDict()
@@ -430,7 +551,8 @@ def get_transforms(cfg, modality, mode="test", device="cuda", test_crops=1):
             else:
                 geometry = [Rescale(cfg.data.test_scale_size),
                             FixedCrop(cfg.data.test_crop_size, [0, 1, 2, 3, 4], horizontal_flip=test_crops == 10)]
-            transforms[m] = DevicePipeline(m, geometry, list(node.mean), list(node.std), device=device)
+            transforms[m] = DevicePipeline(m, geometry, list(node.mean), list(node.std), length=flow_length,
+                                           device=device)
         elif m == "Audio":
             transforms[m] = AudioToTensor(device)
     return transforms

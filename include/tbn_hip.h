@@ -812,6 +812,39 @@ int tbn_frames_to_tensor_crops(const unsigned char* frames, int n_img, int heigh
                                const int* crop_y, int n_crops, int out_w, int out_h, int mirror, int stack,
                                const float* mean, const float* std_dev, int n_stat, int div255, float* out,
                                void* stream);
+/* The same pass for a BATCH of clips in one launch, every clip with a geometry of its own.  Replaces reference
+ * core/dataset/dataset.py:512-532 `_transform_data`, which the DataLoader applies once per sample: MultiScaleCrop and
+ * RandomHorizontalFlip draw once per clip and modality, so a batch has one crop box and one flip per clip.  The
+ * geometries come as a table, one row per clip; every field but first_img / out_row means what the argument of the same
+ * name means to tbn_frames_to_tensor, and the result is bit-identical to that entry called once per clip with the clip's
+ * row (the scale factors are the same IEEE double expression, evaluated on the device).
+ *   frames       (n_img, height, width, channels) uint8 on the device; clip k owns the images
+ *                [first_img, first_img + imgs_per_clip), `stack` consecutive ones form one output sample;
+ *   clips_host   the table in HOST memory: everything is validated from it before any launch, because the kernel reads
+ *                `frames` and writes `out` unchecked;
+ *   clips_dev    the SAME bytes in device memory, the caller's own copy (as the address table of tbn_stft_windows): a
+ *                workgroup reads its clip's row from here.  The launch arguments cannot hold a table of 96 clips;
+ *   out          (out_rows, channels * stack, out_h, out_w) fp32; clip k writes the rows
+ *                [out_row, out_row + imgs_per_clip / stack).  Rows no clip names are not touched, so several launches
+ *                (one per source frame size) can fill one batch tensor.
+ * Refused before any launch, with a message naming the clip: a null pointer, imgs_per_clip not a positive multiple of
+ * stack, first_img < 0 or first_img + imgs_per_clip > n_img, whatever tbn_frames_to_tensor refuses for that geometry
+ * (box outside the frame, window outside the resized box, out_w > 1024, missing mean / std), out_row < 0 or
+ * out_row + imgs_per_clip / stack > out_rows, and two clips whose output rows overlap.  n_clips == 0 launches nothing
+ * and returns 0. */
+typedef struct tbn_frames_clip {
+  int first_img;                        /* the clip's first image in `frames`; the clip owns imgs_per_clip images from here */
+  int box_x, box_y, box_w, box_h;       /* source box, as in tbn_frames_to_tensor */
+  int resized_w, resized_h;             /* == box: no interpolation */
+  int crop_x, crop_y;                   /* window origin inside the resized box */
+  int flip;
+  int out_row;                          /* first output sample (row of `out`) this clip writes; it writes imgs_per_clip/stack rows */
+  int reserved;
+} tbn_frames_clip;
+int tbn_frames_to_tensor_batch(const unsigned char* frames, int n_img, int height, int width, int channels,
+                               const tbn_frames_clip* clips_host, const tbn_frames_clip* clips_dev, int n_clips,
+                               int imgs_per_clip, int out_w, int out_h, int stack, const float* mean,
+                               const float* std_dev, int n_stat, int div255, float* out, int out_rows, void* stream);
 
 /* ---- baseline JPEG decode into device frames (the step in front of tbn_frames_to_tensor) ---------- */
 /* Replaces cv2.imread of reference core/dataset/dataset.py:303-305 (RGB: 3 channels B, G, R) and :355-370 (Flow:
