@@ -6,7 +6,8 @@
 //   AvgPool2d(3, stride 1, pad 1, count_include_pad) inception_{3a,3b,4a-4d,5a}_pool (:86-88 ...)
 //   F.avg_pool2d over (H,1) or (H,W)                 BNInception.logits (core/models/bn_inception.py:16-35)
 // Max-pool forward also stores the in-window argmax (uint8, first maximum in scan order like
-// ATen) so the backward is a deterministic gather (no float atomics).
+// ATen, the first in-bounds tap where nothing compares greater than -inf) so the backward is a
+// deterministic gather (no float atomics).
 #include "tbn_common.h"
 #include "tbn_kernels.h"
 #include "tbn_pool_dev.h"
@@ -37,7 +38,10 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restric
     pix_decode(dec, i, g, ox, oy, n, opix);
     const int y0 = oy * stride - pad, x0 = ox * stride - pad;
     float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-    int bx = 0, by = 0, bz = 0, bw = 0;
+    // where nothing compares greater than -inf ATen keeps its start index, the first IN-BOUNDS tap: in a padded
+    // border window that is not tap 0, and the gather backward finds no owner for a tap outside the map
+    const int k0 = max(-y0, 0) * 3 + max(-x0, 0);
+    int bx = k0, by = k0, bz = k0, bw = k0;
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll

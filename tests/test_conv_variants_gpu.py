@@ -295,20 +295,26 @@ def _forced_pool(z, argmax, stride, pad, oh, ow):
 
 
 @pytest.mark.parametrize("case", [(2, 16, 16, 64, 2, 0), (2, 15, 13, 64, 2, 0), (1, 112, 5, 32, 2, 0), (3, 9, 9, 192, 2, 0),
-                                  (2, 7, 9, 64, 1, 1), (1, 56, 56, 192, 2, 0)])
+                                  (2, 7, 9, 64, 1, 1), (1, 56, 56, 192, 2, 0),
+                                  # the ResNet stem: stride 2 / pad 1 with floor-mode output sizes
+                                  (2, 16, 16, 64, 2, 1, "floor"), (2, 15, 13, 64, 2, 1, "floor"), (1, 9, 9, 192, 2, 1, "floor")])
 def test_bn_relu_maxpool_fused_fwd_bwd(case):
     """the stem's fused BN apply + ReLU + 3x3 max pool (z never written) and its backward on 2x2 input blocks, odd and
     even maps, against F.max_pool2d(F.relu(batch_norm(y))) in fp64: pooled values, running statistics, arg-max (must
     select a window maximum of the fp64 z up to the fp32 error), and dy / dgamma / dbeta with the fp64 autograd routed
     through the product's arg-max"""
-    n, h, w, c, s, p = case
+    n, h, w, c, s, p = case[:6]
+    floor = case[6:] == ("floor",)           # output-size mode; the cases without the field are ceil-mode
     from tests import bn_check as bc
-    oh = -(-(h + 2 * p - 3) // s) + 1
-    ow = -(-(w + 2 * p - 3) // s) + 1
-    if (oh - 1) * s >= h + p:
-        oh -= 1
-    if (ow - 1) * s >= w + p:
-        ow -= 1
+    if floor:
+        oh, ow = (h + 2 * p - 3) // s + 1, (w + 2 * p - 3) // s + 1
+    else:
+        oh = -(-(h + 2 * p - 3) // s) + 1
+        ow = -(-(w + 2 * p - 3) // s) + 1
+        if (oh - 1) * s >= h + p:
+            oh -= 1
+        if (ow - 1) * s >= w + p:
+            ow -= 1
     # the BN part on the multi-scale inputs of tests/bn_check.py (channel std over five decades, gamma of both signs and 0,
     # constant channels) and judged per channel as well as over the whole tensor
     P = n * h * w
@@ -330,7 +336,7 @@ def test_bn_relu_maxpool_fused_fwd_bwd(case):
     rmr, rvr = rm.double().clone(), rv.double().clone()
     pre = F.batch_norm(yr, rmr, rvr, gr, br, True, 0.1, bc.EPS32)
     z = F.relu(pre)
-    pool_ref = F.max_pool2d(z, 3, s, p, ceil_mode=True)
+    pool_ref = F.max_pool2d(z, 3, s, p, ceil_mode=not floor)
     assert pool_ref.shape[2:] == (oh, ow)
     assert relerr(nchw(pooled[..., 4:4 + c]), pool_ref.detach()) < TOL
     assert float((pooled[..., :4] - 3).abs().max()) == 0 and float((pooled[..., 4 + c:] - 3).abs().max()) == 0
