@@ -91,6 +91,11 @@ class FramesClip(C.Structure):
                 ("resized_h", c_i), ("crop_x", c_i), ("crop_y", c_i), ("flip", c_i), ("out_row", c_i), ("reserved", c_i)]
 
 
+class MetricHead(C.Structure):
+    """include/tbn_hip.h tbn_metric_head"""
+    _fields_ = [("scores", c_fp), ("scores_ld", c_i), ("classes", c_i), ("target", c_fp), ("conf_mat", c_fp)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/tbn_hip.h
 SIGNATURES = {
     "tbn_version": (c_i, []),
@@ -211,6 +216,9 @@ SIGNATURES = {
     # reference core/tools/train.py:202-208 (optim.Adam)
     "tbn_opt_adam_step": (c_i, [C.POINTER(AdamTensor), c_i, c_f, c_f, c_f, c_f, c_fp, c_fp]),
     "tbn_topk_correct": (c_i, [c_fp, c_i, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp]),
+    # reference core/utils/metric.py:50-106,137-157: a batch's hits, confusion matrices and losses in one launch
+    "tbn_metric_update": (c_i, [C.POINTER(MetricHead), c_i, c_i, C.POINTER(c_i), c_i, C.POINTER(C.c_void_p), c_i, c_fp,
+                                c_fp, c_fp]),
     "tbn_frames_to_tensor": (c_i, [c_fp] + [c_i] * 16 + [c_fp, c_fp, c_i, c_i, c_fp, c_fp]),
     "tbn_frames_to_tensor_crops": (c_i, [c_fp] + [c_i] * 10 + [C.POINTER(c_i), C.POINTER(c_i)] + [c_i] * 5 +
                                    [c_fp, c_fp, c_i, c_i, c_fp, c_fp]),

@@ -211,12 +211,14 @@ class Video_Dataset(object):
         hw = (keys[0][1], keys[0][0])
         return _Visual(paths, blobs, None, ("jpg",) + hw, hw, None, keys)
 
-    def plan(self, indices):
+    def plan(self, indices, rng=None):
         """The host half of `batch`: for every clip, in order, and every modality, in order, the segment indices (when
         that modality draws any) and THEN that modality's transform geometry -- the draw order of the reference's
         `__getitem__` (dataset.py:157-178) called clip after clip, under data.sampling "sync" and "async" alike.  Reads
         the frame files (the geometry needs the frame size) but touches no GPU.  Returns one record per clip with
-        `.indices[m]`, `.visual[m].paths` and `.visual[m].geo`."""
+        `.indices[m]`, `.visual[m].paths` and `.visual[m].geo`.  Every draw comes from `rng` (a `np.random.RandomState`);
+        None: from the global `np.random`, the same calls in the same order."""
+        draw = np.random if rng is None else rng
         clips = []
         for i in indices:
             clip = _Clip(EpicVideoRecord(self.annotations.iloc[int(i)]))
@@ -226,10 +228,11 @@ class Video_Dataset(object):
                     idx = clip.indices[self.modality[0]]
                     clip.indices[m] = (idx / 2).astype(np.int64) if m == "Flow" else idx
                 else:
-                    clip.indices[m] = get_offsets(first[m], num[m], m, self.mode, self.num_segments, self.frame_len[m])
+                    clip.indices[m] = get_offsets(first[m], num[m], m, self.mode, self.num_segments, self.frame_len[m],
+                                                  rng=draw)
                 if m != "Audio":
                     v = self._read_visual(m, clip.vid_id, clip.indices[m])
-                    v.geo = self.transform[m]._record(*v.hw)
+                    v.geo = self.transform[m]._record(*v.hw, rng=rng)
                     clip.visual[m] = v
             clips.append(clip)
         return clips
@@ -301,14 +304,15 @@ class Video_Dataset(object):
         waves = [self._waveform(clip.vid_id) for clip in clips]
         return self._audio(waves, np.stack([clip.indices["Audio"] for clip in clips], 0))
 
-    def batch(self, indices):
+    def batch(self, indices, rng=None):
         """`(data, target)` in train mode, `(data, target, action_id)` otherwise: what `default_collate` makes of the
         reference's items `[dataset[i] for i in indices]`, already on the device --
           data[m]            (B, n, C, H, W) fp32 per modality;
           data["indices"][m] (B, n) int64;  data["vid_id"], data["start_time"], data["stop_time"]: lists;
           data["weights"]    (B, n, T, 1) with attention and use_fixed; target["weights"] with attention and use_prior;
           target["class"]    {"verb", "noun"}: int64 (B,), or an int64 (B,) of -1 when the label columns are missing;
-          action_id          int64 (B,) when the uids are integers, else a list."""
+          action_id          int64 (B,) when the uids are integers, else a list.
+        `rng`: handed to `plan`."""
         indices = [int(i) for i in indices]
         if not indices:
             raise ValueError("Video_Dataset.batch: no indices")
@@ -316,7 +320,7 @@ class Video_Dataset(object):
         wants_weights = self.use_attention and (att.use_fixed or att.use_prior)
         if wants_weights and "Audio" not in self.modality:
             raise ValueError("Video_Dataset: the attention weights come from the Audio modality, which is not enabled")
-        clips = self.plan(indices)
+        clips = self.plan(indices, rng)
         data, target = OrderedDict(), OrderedDict()
         data["vid_id"] = [clip.vid_id for clip in clips]
         data["start_time"] = [clip.record.start_time for clip in clips]

@@ -4,7 +4,8 @@ Mirror of the index-selection part of reference `Video_Dataset.__getitem__`
 (core/dataset/dataset.py:155-172), `_get_offsets` (:194-239) and the per-modality frame
 arithmetic of `EpicVideoRecord` (core/dataset/epic_record.py:25-46).  Train-mode offsets come from
 NumPy's global legacy RandomState with one `randint` draw per call, in modality order, so a run
-seeded like the reference's `main.py:20` reproduces its indices bit for bit.
+seeded like the reference's `main.py:20` reproduces its indices bit for bit.  `get_offsets(..., rng=)` draws from
+another source with the same `randint` instead (a `np.random.RandomState`: the prefetching loader's per-epoch stream).
 """
 import numpy as np
 
@@ -18,13 +19,13 @@ def frame_span(start_frame, stop_frame):
     return first, {m: last[m] - first[m] for m in _MODALITIES}
 
 
-def get_offsets(first, num_frames, modality, mode, num_segments, frame_len):
+def get_offsets(first, num_frames, modality, mode, num_segments, frame_len, rng=np.random):
     span = num_frames - frame_len + 1 if mode == "train" else num_frames
     seg_len = span // num_segments
     if seg_len <= 0:
         return first + np.zeros((num_segments), dtype=np.int64)
     if mode == "train":
-        off = np.random.randint(seg_len, size=num_segments)
+        off = rng.randint(seg_len, size=num_segments)
     else:
         off = seg_len // 2
         if modality == "Flow":

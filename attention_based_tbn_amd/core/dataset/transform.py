@@ -25,9 +25,12 @@ from ..._lib import FramesClip, TbnHipError, call, ptr, stream_ptr
 
 
 class _Geometry:
-    """what the recorded transforms do to a frame of (h, w): source box -> resized size -> crop window -> flip"""
+    """what the recorded transforms do to a frame of (h, w): source box -> resized size -> crop window -> flip.
+    `rng` is what the random transforms recorded into it draw from (`randint`, `random`): the global `np.random` module,
+    or a `np.random.RandomState` of the caller's."""
 
-    def __init__(self, h, w):
+    def __init__(self, h, w, rng=None):
+        self.rng = np.random if rng is None else rng
         self.src_h, self.src_w = h, w   # the frames the geometry was recorded for
         self.h, self.w = h, w           # current logical size
         self.box = [0, 0, w, h]         # x, y, w, h in the SOURCE frame (only valid before a resize)
@@ -127,24 +130,24 @@ class MultiScaleCrop(_GeometryTransform):
         self.input_size = input_size if isinstance(input_size, tuple) else (input_size, input_size)
 
     def record(self, geo):
-        crop_w, crop_h, off_w, off_h = self._sample_crop_size((geo.h, geo.w))
+        crop_w, crop_h, off_w, off_h = self._sample_crop_size((geo.h, geo.w), geo.rng)
         geo.do_crop(off_w, off_h, crop_w, crop_h)
         Rescale(self.input_size).record(geo)
 
-    def _sample_crop_size(self, im_size):
+    def _sample_crop_size(self, im_size, rng=np.random):
         img_h, img_w = im_size[0], im_size[1]
         base_size = min(img_w, img_h)
         crop_sizes = [int(base_size * x) for x in self.scales]
         crop_h = [self.input_size[1] if abs(x - self.input_size[1]) < 3 else x for x in crop_sizes]
         crop_w = [self.input_size[0] if abs(x - self.input_size[0]) < 3 else x for x in crop_sizes]
         pairs = [(w, h) for i, h in enumerate(crop_h) for j, w in enumerate(crop_w) if abs(i - j) <= self.max_distort]
-        crop_pair = pairs[np.random.randint(len(pairs))]
+        crop_pair = pairs[rng.randint(len(pairs))]
         if not self.fix_crop:
-            w_offset = np.random.randint(0, img_w - crop_pair[0])
-            h_offset = np.random.randint(0, img_h - crop_pair[1])
+            w_offset = rng.randint(0, img_w - crop_pair[0])
+            h_offset = rng.randint(0, img_h - crop_pair[1])
         else:
             offsets = self.fill_fix_offset(self.more_fix_crop, img_w, img_h, crop_pair[0], crop_pair[1])
-            w_offset, h_offset = offsets[np.random.randint(len(offsets))]
+            w_offset, h_offset = offsets[rng.randint(len(offsets))]
         return crop_pair[0], crop_pair[1], int(w_offset), int(h_offset)
 
     @staticmethod
@@ -232,8 +235,8 @@ class RandomCrop(_GeometryTransform):
 
     def record(self, geo):
         th, tw = self.size
-        x1 = np.random.randint(0, geo.w - tw)
-        y1 = np.random.randint(0, geo.h - th)
+        x1 = geo.rng.randint(0, geo.w - tw)
+        y1 = geo.rng.randint(0, geo.h - th)
         if not (geo.w == tw and geo.h == th):
             geo.do_crop(x1, y1, tw, th)
 
@@ -245,7 +248,7 @@ class RandomHorizontalFlip(_GeometryTransform):
         self.prob = prob
 
     def record(self, geo):
-        if np.random.random() < self.prob:
+        if geo.rng.random() < self.prob:
             geo.do_flip()
         else:
             geo._open("a flip")
@@ -320,17 +323,18 @@ class DevicePipeline(object):
         mean, std = self._stats()
         return _frames_to_tensor(img_list, geo, self.channels, self.stack, mean, std, True, self.device)
 
-    def _record(self, h, w):
-        """the recorded geometry of ONE clip of (h, w) frames: the NumPy draws of one `__call__`, no GPU"""
-        geo = _Geometry(h, w)
+    def _record(self, h, w, rng=None):
+        """the recorded geometry of ONE clip of (h, w) frames: the NumPy draws of one `__call__`, no GPU; `rng`: where
+        they are drawn from (None: the global generator)"""
+        geo = _Geometry(h, w, rng)
         for t in self.geometry:
             t(geo)
         return geo
 
-    def _record_batch(self, sizes):
+    def _record_batch(self, sizes, rng=None):
         """sizes: (h, w) per clip, in batch order -> one `_Geometry` per clip, recorded clip after clip: the NumPy draws
         of len(sizes) consecutive `__call__`s.  Host only."""
-        return [self._record(int(h), int(w)) for h, w in sizes]
+        return [self._record(int(h), int(w), rng) for h, w in sizes]
 
     def batch(self, frames, n_clips, clips=None):
         """The clips of a whole batch in one launch (`tbn_frames_to_tensor_batch`): the reference applies

@@ -4,28 +4,180 @@
 What differs from the DataLoader, on purpose:
   * a batch is made at once by `Video_Dataset.batch` (one decode and one transform launch per modality), not item by item
     and collated;
-  * iteration is synchronous on the current stream: no background thread, no prefetch, no worker processes.  The decode
-    pool of `decode_jpegs` is the only host parallelism, so `cfg.num_workers` is accepted and ignored;
+  * by default iteration is synchronous on the current stream: no background thread, no prefetch, no worker processes.
+    The decode pool of `decode_jpegs` is the only host parallelism, so `cfg.num_workers` is accepted and ignored.
+    `prefetch=N` (opt-in) makes the batches on ONE producer thread and a side stream beside the consumer's work, at most N
+    finished batches ahead -- still no worker processes;
   * train order is `torch.randperm(N)`, drawn once per `__iter__` from the global torch generator.  That is a seeded,
     reproducible shuffle, but it is NOT pinned to the draw of `torch.utils.data.RandomSampler` (which seeds a generator
     of its own from the global one first): the same `torch.manual_seed` gives another order than the reference's loader.
 The last, shorter batch is kept, as with the DataLoader's default `drop_last=False`.
 """
 import os
+import queue
+import threading
+import weakref
 
+import numpy as np
 import torch
 
 from ..dataset.dataset import Video_Dataset
 from ..dataset.transform import get_transforms
 
+_DEFAULT_RNG = type("_DefaultRng", (str,), {})("global")    # tells the default apart from an explicit rng="global"
+_POLL = 0.1          # seconds: queue put / get time-out, after which the stop flag / the producer's life is looked at
+_JOIN = 5.0          # seconds: how long close() waits for the producer
+
+
+def _record_stream(x, stream):
+    """`record_stream` on every device tensor of a nested (tuple / list / dict) batch; anything else passes"""
+    if isinstance(x, torch.Tensor):
+        if x.is_cuda:
+            x.record_stream(stream)
+    elif isinstance(x, dict):
+        for v in x.values():
+            _record_stream(v, stream)
+    elif isinstance(x, (list, tuple)):
+        for v in x:
+            _record_stream(v, stream)
+
+
+def _put(q, item, stop):
+    """blocks while the queue is full, but never past the stop flag -> was the item queued?"""
+    while not stop.is_set():
+        try:
+            q.put(item, timeout=_POLL)
+            return True
+        except queue.Full:
+            pass
+    return False
+
+
+def _produce(dataset, parts, rng, q, stop, stream, device):
+    """the producer thread: `dataset.batch(part, rng=rng)` for every part, in order, on `stream`; each result is queued
+    with the event recorded behind it.  Holds no reference to the iterator, so that one can be collected."""
+    try:
+        if stream is None:
+            for part in parts:
+                if stop.is_set():
+                    return
+                if not _put(q, ("batch", dataset.batch(part, rng=rng), None), stop):
+                    return
+        else:
+            with torch.cuda.device(device), torch.cuda.stream(stream):
+                for part in parts:
+                    if stop.is_set():
+                        return
+                    item = dataset.batch(part, rng=rng)
+                    event = torch.cuda.Event()
+                    event.record(stream)
+                    if not _put(q, ("batch", item, event), stop):
+                        return
+        _put(q, ("end", None, None), stop)
+    except BaseException as e:      # delivered to the consumer at the __next__ that would have returned this batch
+        _put(q, ("error", e, None), stop)
+
+
+class _PrefetchIter(object):
+    """one pass of a `ClipLoader(prefetch > 0)`: owns the producer thread, its queue and its stop flag"""
+
+    def __init__(self, dataset, parts, rng, prefetch, stream, device):
+        self._q = queue.Queue(maxsize=prefetch)
+        self._stop = threading.Event()
+        self._stream, self._done = stream, False
+        self.thread = threading.Thread(target=_produce, name="ClipLoader-producer", daemon=True,
+                                       args=(dataset, parts, rng, self._q, self._stop, stream, device))
+        self.thread.start()
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._done:
+            raise StopIteration
+        while True:
+            try:
+                kind, item, event = self._q.get(timeout=_POLL)
+                break
+            except queue.Empty:
+                if self.thread.is_alive():
+                    continue
+                try:        # it may have queued its last word right before it ended
+                    kind, item, event = self._q.get_nowait()
+                    break
+                except queue.Empty:
+                    self.close()
+                    raise RuntimeError("ClipLoader: the producer thread ended without a batch, an end mark or an error")
+        if kind == "batch":
+            if event is not None:
+                current = torch.cuda.current_stream(self._stream.device)
+                current.wait_event(event)           # device-side wait: the host does not synchronise
+                _record_stream(item, current)       # allocated on the loader stream, used (and freed) on this one
+            return item
+        self.close()
+        if kind == "error":
+            raise item
+        raise StopIteration
+
+    def close(self):
+        """stops the producer between two batches and waits (bounded) for it; idempotent"""
+        self._done = True
+        self._stop.set()
+        try:
+            while True:         # a producer blocked in put() sees the flag at its next time-out; dropping is quicker
+                self._q.get_nowait()
+        except queue.Empty:
+            pass
+        if self.thread is not threading.current_thread():
+            self.thread.join(_JOIN)
+            if self._stream is not None and not self.thread.is_alive():
+                # what the producer left on its stream (cached waveforms, ...) is ordered before later work here
+                torch.cuda.current_stream(self._stream.device).wait_stream(self._stream)
+                self._stream = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 class ClipLoader(object):
-    """iterable over the batches of a `Video_Dataset`: `len()` = ceil(N / batch_size), `.dataset`, `.batch_size`"""
+    """iterable over the batches of a `Video_Dataset`: `len()` = ceil(N / batch_size), `.dataset`, `.batch_size`.
 
-    def __init__(self, dataset, batch_size, shuffle=False):
+    `prefetch=0, rng="global"` (the default): `dataset.batch(part)` on the calling thread and the current stream, every
+    random draw from the global NumPy / torch generators.
+
+    `rng="private"`: `__iter__` draws, on the calling thread, the shuffle and then ONE seed from torch's global generator
+    (`torch.randint(0, 2**31 - 1, (1,))`); the pass's plans draw from `np.random.RandomState(seed)`, handed to
+    `dataset.batch(part, rng=)`.  A whole pass is then a function of the torch generator state at `__iter__`.
+
+    `prefetch=N > 0` (implies and requires `rng="private"`): one daemon producer thread per `__iter__` makes the batches
+    in order on a side stream of the loader's, never more than N finished batches plus the one in progress ahead of the
+    consumer.  `__next__` makes the consumer's current stream wait for the batch's event and marks the batch's tensors
+    as used on it (`record_stream`); the host does not synchronise.  The batches equal those of
+    `ClipLoader(prefetch=0, rng="private")` under the same torch generator state.  An exception in the producer is
+    raised at the `__next__` that would have returned its batch.  Leaving the loop early (`break`, an exception, the
+    iterator closed or collected) or `close()` stops the producer within a bounded time.  One live iterator per
+    loader: a second `__iter__` closes the first.
+
+    While an iterator is live the dataset object must not be used by another thread: its waveform cache is mutated by
+    the producer only."""
+
+    def __init__(self, dataset, batch_size, shuffle=False, *, prefetch=0, rng=_DEFAULT_RNG):
         if batch_size < 1:
             raise ValueError(f"ClipLoader: batch_size {batch_size}")
+        if int(prefetch) != prefetch or prefetch < 0:
+            raise ValueError(f"ClipLoader: prefetch {prefetch!r} is not a count >= 0")
+        if rng not in ("global", "private"):
+            raise ValueError(f"ClipLoader: rng={rng!r} is not 'global' or 'private'")
+        if prefetch > 0:
+            if rng is not _DEFAULT_RNG and rng == "global":
+                raise ValueError("ClipLoader: prefetch > 0 draws on another thread, which needs rng='private'")
+            rng = "private"
         self.dataset, self.batch_size, self.shuffle = dataset, int(batch_size), bool(shuffle)
+        self.prefetch, self.rng = int(prefetch), str(rng)
+        self._stream, self._live = None, None
 
     def __len__(self):
         return -(-len(self.dataset) // self.batch_size)
@@ -36,15 +188,54 @@ class ClipLoader(object):
         order = torch.randperm(n).tolist() if self.shuffle else list(range(n))
         return [order[i:i + self.batch_size] for i in range(0, n, self.batch_size)]
 
-    def __iter__(self):
+    def _global_pass(self):
         for part in self.batches():
             yield self.dataset.batch(part)
 
+    def _private_pass(self, parts, rng):
+        for part in parts:
+            yield self.dataset.batch(part, rng=rng)
 
-def create_dataloader(cfg, logger, modality, mode="test", device="cuda"):
+    def _loader_stream(self):
+        """(side stream, device), made on first use; (None, None) without CUDA"""
+        if not torch.cuda.is_available():
+            return None, None
+        if self._stream is None:
+            device = torch.device(getattr(self.dataset, "device", "cuda"))
+            if device.type != "cuda":
+                return None, None
+            if device.index is None:
+                device = torch.device("cuda", torch.cuda.current_device())
+            self._stream = torch.cuda.Stream(device=device)
+        return self._stream, self._stream.device
+
+    def __iter__(self):
+        if self.rng == "global":
+            return self._global_pass()
+        self.close()
+        parts = self.batches()
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)))
+        rng = np.random.RandomState(seed)
+        if self.prefetch == 0:
+            return self._private_pass(parts, rng)
+        stream, device = self._loader_stream()
+        if stream is not None:
+            stream.wait_stream(torch.cuda.current_stream(device))    # e.g. waveforms cached by a synchronous pass
+        live = _PrefetchIter(self.dataset, parts, rng, self.prefetch, stream, device)
+        self._live = weakref.ref(live)      # weak: dropping the iterator (a `break`) collects it, which stops the producer
+        return live
+
+    def close(self):
+        """stops the live prefetching iterator, if there is one (bounded wait); the loader can be iterated again"""
+        live, self._live = (self._live() if self._live is not None else None), None
+        if live is not None:
+            live.close()
+
+
+def create_dataloader(cfg, logger, modality, mode="test", device="cuda", *, prefetch=0):
     """The annotation file, video list and batch size per mode follow the reference (:86-120); val reads the TRAIN
     annotation file filtered by the val video list, as there.  A relative `vid_list` path is taken from the directory
-    above the `core` package, like the reference's; an empty one keeps every video."""
+    above the `core` package, like the reference's; an empty one keeps every video.  `prefetch` is handed to `ClipLoader`."""
     logger.info(f"Creating {mode} Dataloader...")
     if mode == "train":
         vid_file, annotation_file, batch_size = cfg.train.vid_list, cfg.train.annotation_file, cfg.train.batch_size
@@ -64,7 +255,7 @@ def create_dataloader(cfg, logger, modality, mode="test", device="cuda"):
             vid_list = [x.strip() for x in f.readlines() if len(x.strip()) > 0]
     transforms = get_transforms(cfg, modality, mode, device=device, flow_length=2 * cfg.data.flow.win_length)
     dataset = Video_Dataset(cfg, vid_list, annotation_file, modality, transform=transforms, mode=mode, device=device)
-    loader = ClipLoader(dataset, batch_size, shuffle=(mode == "train"))
+    loader = ClipLoader(dataset, batch_size, shuffle=(mode == "train"), prefetch=prefetch)
     logger.info("Done.")
     logger.info("----------------------------------------------------------")
     return loader

@@ -52,6 +52,7 @@ class TrainStep:
         self.k = int(accumulator_step)
         self.clip_grad = clip_grad if clip_grad else None    # reference: `if cfg.train.clip_grad:`
         self.last_total_norm = None     # 0-dim device tensor of the last clip (None when clipping is off)
+        self.last_out = None            # the model's output dict of the last call (what a metric is fed with)
         # did the backward of the last iterations exchange gradients (data parallel only)?  Bounded: a run has millions
         self.synced = collections.deque(maxlen=64)
 
@@ -79,7 +80,7 @@ class TrainStep:
         if self.zeroes(iter_no):
             self.optimizer.zero_grad()
         with self._sync_context(iter_no):
-            out = self.model(data)
+            out = self.last_out = self.model(data)
             loss, batch_size = self.model.get_loss(self.criterion, target, out, epoch)
             loss["total"] = loss["total"] / self.k
             loss["total"].backward()

@@ -357,6 +357,10 @@ int tbn_opt_sgd_step(const tbn_opt_tensor* tensors, int num_tensors, float lr, f
 // torch.topk(sorted=True) returns for distinct scores; ties resolve to the lower class index).
 // correct[j][b] = (j-th prediction of sample b == target[b]);  conf[target][top-1] += 1 (integer-valued float
 // atomics: exact and order independent).
+// (value descending, class index ascending): does (v, c) come before (bv, bi)?  NaN never does.  Shared by both metric
+// kernels so that their top-1 cannot disagree.
+__device__ __forceinline__ bool score_before(float v, int c, float bv, int bi) { return v > bv || (v == bv && c < bi); }
+
 __global__ __launch_bounds__(256) void topk_correct_kernel(const float* __restrict__ scores, int ld,
                                                            const long long* __restrict__ target, int B, int C, int K,
                                                            unsigned char* __restrict__ correct,
@@ -375,7 +379,7 @@ __global__ __launch_bounds__(256) void topk_correct_kernel(const float* __restri
     for (int c = lane; c < C; c += 64) {
       const float v = row[c];
       const bool after = (v < prev_v) || (v == prev_v && c > prev_i);
-      if (after && (v > bv || (v == bv && c < bi))) {
+      if (after && score_before(v, c, bv, bi)) {
         bv = v;
         bi = c;
       }
@@ -384,7 +388,7 @@ __global__ __launch_bounds__(256) void topk_correct_kernel(const float* __restri
     for (int o = 32; o > 0; o >>= 1) {
       const float ov = __shfl_xor(bv, o);
       const int oi = __shfl_xor(bi, o);
-      if (ov > bv || (ov == bv && oi < bi)) {
+      if (score_before(ov, oi, bv, bi)) {
         bv = ov;
         bi = oi;
       }
@@ -408,5 +412,103 @@ extern "C" int tbn_topk_correct(const float* scores, int scores_ld, const long l
   TBN_KLAUNCH(topk_correct_kernel, dim3(cdiv(batch, 4)), dim3(256), 0, (hipStream_t)stream, scores, scores_ld,
                      target, batch, classes, k, correct, pred, conf_mat);
   TBN_CHECK_LAUNCH("topk_correct");
+  return TBN_OK;
+}
+
+// ---------------------------------------------------------------- metrics: a whole batch in one launch, no host round trip
+// One wave per sample, four samples per workgroup, as topk_correct_kernel; the wave walks every head of its sample.
+// Instead of k arg-max rounds it COUNTS the classes ranked before the target in (score descending, index ascending)
+// order -- the position topk_correct_kernel reports the target at, NaN scores never ranking -- so any k costs one pass.
+// hits[h][j] += [rank_h < topk[j]],  hits[H][j] += [every head hit within topk[j]]  (the reference's all_class),
+// conf_h[target][top-1] += 1, loss_row[i] = *loss[i].  Integer atomics and integer-valued float atomics: exact and
+// order independent.
+struct MetricArgs {
+  tbn_metric_head head[4];
+  const float* loss[8];
+  int topk[8];
+  int num_heads, batch, num_topk, num_losses;
+};
+
+__global__ __launch_bounds__(256) void metric_update_kernel(MetricArgs a, int* __restrict__ hits,
+                                                            float* __restrict__ loss_row) {
+  if (blockIdx.x == 0 && (int)threadIdx.x < a.num_losses) loss_row[threadIdx.x] = *a.loss[threadIdx.x];
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= a.batch) return;
+  unsigned joint = (1u << a.num_topk) - 1u;   // bit j: every head so far has its target within topk[j]
+  for (int h = 0; h < a.num_heads; ++h) {
+    const int C = a.head[h].classes;
+    const float* row = a.head[h].scores + (size_t)b * a.head[h].scores_ld;
+    const long long tgt = a.head[h].target[b];
+    const bool valid = tgt >= 0 && tgt < C;
+    const float st = valid ? row[tgt] : NAN;   // NaN compares false everywhere below: rank 0, and `hit` refuses it
+    const int t = valid ? (int)tgt : 0;
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    int rank = 0;
+    for (int c = lane; c < C; c += 64) {
+      const float v = row[c];
+      if (score_before(v, c, bv, bi)) {
+        bv = v;
+        bi = c;
+      }
+      rank += (int)score_before(v, c, st, t);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o);
+      const int oi = __shfl_xor(bi, o);
+      if (score_before(ov, oi, bv, bi)) {
+        bv = ov;
+        bi = oi;
+      }
+      rank += __shfl_xor(rank, o);
+    }
+    if (lane == 0) {
+      const bool hit = valid && st == st;
+      for (int j = 0; j < a.num_topk; ++j) {
+        if (hit && rank < a.topk[j])
+          atomicAdd(hits + h * a.num_topk + j, 1);
+        else
+          joint &= ~(1u << j);
+      }
+      float* conf = a.head[h].conf_mat;
+      if (conf != nullptr && valid && bi < C) atomicAdd(conf + (size_t)tgt * C + bi, 1.0f);
+    }
+  }
+  if (lane == 0)
+    for (int j = 0; j < a.num_topk; ++j)
+      if ((joint >> j) & 1u) atomicAdd(hits + a.num_heads * a.num_topk + j, 1);
+}
+
+extern "C" int tbn_metric_update(const tbn_metric_head* heads, int num_heads, int batch, const int* topk, int num_topk,
+                                 const float* const* loss_ptrs, int num_losses, int* hits_row, float* loss_row,
+                                 void* stream) {
+  TBN_REQUIRE(heads != nullptr && topk != nullptr && hits_row != nullptr, "metric_update: null argument");
+  TBN_REQUIRE(num_heads >= 1 && num_heads <= 4, "metric_update: num_heads %d outside 1..4", num_heads);
+  TBN_REQUIRE(num_topk >= 1 && num_topk <= 8, "metric_update: num_topk %d outside 1..8", num_topk);
+  TBN_REQUIRE(num_losses >= 0 && num_losses <= 8, "metric_update: num_losses %d outside 0..8", num_losses);
+  TBN_REQUIRE(num_losses == 0 || (loss_ptrs != nullptr && loss_row != nullptr), "metric_update: null loss argument");
+  TBN_REQUIRE(batch >= 0, "metric_update: batch %d", batch);
+  MetricArgs a = {};
+  a.num_heads = num_heads, a.batch = batch, a.num_topk = num_topk, a.num_losses = num_losses;
+  for (int h = 0; h < num_heads; ++h) {
+    TBN_REQUIRE(heads[h].scores != nullptr && heads[h].target != nullptr, "metric_update: null argument in head %d", h);
+    TBN_REQUIRE(heads[h].classes >= 1 && heads[h].scores_ld >= heads[h].classes,
+                "metric_update: bad shape of head %d (C=%d, ld=%d)", h, heads[h].classes, heads[h].scores_ld);
+    for (int j = 0; j < num_topk; ++j)
+      TBN_REQUIRE(topk[j] >= 1 && topk[j] <= heads[h].classes, "metric_update: k=%d outside 1..%d of head %d", topk[j],
+                  heads[h].classes, h);
+    a.head[h] = heads[h];
+  }
+  for (int j = 0; j < num_topk; ++j) a.topk[j] = topk[j];
+  for (int i = 0; i < num_losses; ++i) {
+    TBN_REQUIRE(loss_ptrs[i] != nullptr, "metric_update: null loss pointer %d", i);
+    a.loss[i] = loss_ptrs[i];
+  }
+  if (batch == 0 && num_losses == 0) return TBN_OK;
+  TBN_KLAUNCH(metric_update_kernel, dim3(batch > 0 ? cdiv(batch, 4) : 1), dim3(256), 0, (hipStream_t)stream, a,
+              hits_row, loss_row);
+  TBN_CHECK_LAUNCH("metric_update");
   return TBN_OK;
 }

@@ -779,6 +779,24 @@ int tbn_opt_adam_step(const tbn_adam_tensor* tensors, int num_tensors, float bet
  * conf_mat (classes, classes) float, conf_mat[target][top1] += 1 (may be NULL).  Ties rank the lower index first. */
 int tbn_topk_correct(const float* scores, int scores_ld, const long long* target, int batch, int classes, int k,
                      unsigned char* correct, long long* pred, float* conf_mat, void* stream);
+/* replaces: Metric.set_metrics + Metric._get_correct_score (core/utils/metric.py:50-106,137-157) for a whole batch in
+ * ONE launch that the host never waits for.  Per head the rank of the target class in (score descending, class index
+ * ascending) order -- the position tbn_topk_correct reports it at; NaN scores never rank -- decides a hit for each k of
+ * topk: target in [0, classes), its score not NaN, rank < k.  hits_row is (num_heads + 1, num_topk) int32 and is ADDED
+ * to: rows 0..num_heads-1 the heads, row num_heads the samples that hit in EVERY head (the reference's all_class).
+ * loss_row[i] = *loss_ptrs[i] (device scalars, copied by the same launch, also when batch == 0). */
+typedef struct {
+  const float* scores;        /* (batch, classes), pitch scores_ld >= classes */
+  int scores_ld, classes;
+  const long long* target;    /* (batch,) int64 */
+  float* conf_mat;            /* (classes, classes) float or NULL: conf_mat[target][top-1] += 1 */
+} tbn_metric_head;
+int tbn_metric_update(const tbn_metric_head* heads, int num_heads,      /* 1..4, host array, passed by value into the launch */
+                      int batch, const int* topk, int num_topk,          /* host array, 1..8 values, any order, each 1..min classes */
+                      const float* const* loss_ptrs, int num_losses,     /* host array of 0..8 DEVICE scalars */
+                      int* hits_row,    /* device, (num_heads + 1) * num_topk ints, ADDED to; group num_heads = joint */
+                      float* loss_row,  /* device, num_losses floats, written */
+                      void* stream);
 
 /* ---- on-device visual input pipeline (the step right before the path) ---- */
 /* MultiScaleCrop / Rescale (cv2.resize INTER_LINEAR, 8-bit fixed point) -> CenterCrop / crop -> RandomHorizontalFlip
