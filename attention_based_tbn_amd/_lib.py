@@ -208,7 +208,12 @@ SIGNATURES = {
     "tbn_stft_windows": (c_i, [c_fp, c_fp, c_i, c_i, c_fp, c_fp, c_f, c_i, c_fp, c_fp, c_fp]),
     # reference core/dataset/dataset.py:534-575 (prior_type "loud")
     "tbn_attn_prior_loud": (c_i, [c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp]),
-    "tbn_opt_num_partials": (c_i, [C.POINTER(OptTensor), c_i]),
+    # reference core/dataset/dataset.py:401-414, preprocessing/create_audio_pickle.py:47-49 (librosa.load): host bank, one launch
+    "tbn_audio_bank_geometry": (c_i, [c_i, c_i, C.POINTER(c_i), C.POINTER(c_i), C.POINTER(c_sz)]),
+    "tbn_audio_make_bank": (c_i, [c_i, c_i, c_fp, c_sz]),
+    "tbn_audio_tile": (c_i, []),
+    "tbn_audio_load": (c_i, [c_fp, c_sz, C.c_longlong, c_i, c_i, c_i, c_i, c_fp, c_fp, C.c_longlong, c_fp]),
+    "tbn_opt_num_partials":(c_i, [C.POINTER(OptTensor), c_i]),
     "tbn_opt_sqnorm_partials": (c_i, [C.POINTER(OptTensor), c_i, c_fp, c_fp]),
     "tbn_opt_clip_coef": (c_i, [c_fp, c_i, c_f, c_fp, c_fp, c_fp]),
     "tbn_opt_scale_grads": (c_i, [C.POINTER(OptTensor), c_i, c_fp, c_fp]),

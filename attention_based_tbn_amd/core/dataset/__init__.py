@@ -6,3 +6,4 @@ from .transform import (CenterCrop, DevicePipeline, FixedCrop, MultiScaleCrop, N
                         RandomHorizontalFlip, Rescale, Stack, ToTensor, TransferTensorDict, get_transforms)
 from .frames import FrameReader, decode_jpegs, jpeg_geometry  # noqa: F401
 from .dataset import EpicVideoRecord, Video_Dataset, read_wav  # noqa: F401
+from .audio_file import WavInfo, load_audio, wav_info  # noqa: F401

@@ -25,6 +25,7 @@ import torch
 
 from ..._lib import TbnHipError
 from .audio import AudioSegments
+from .audio_file import load_audio
 from .frames import FrameReader, decode_jpegs, geometry_key, jpeg_geometry
 from .sampler import frame_span, get_offsets
 from .transform import DevicePipeline
@@ -117,19 +118,25 @@ class _Clip(object):
 
 class Video_Dataset(object):
     """The reference's constructor `(cfg, vid_list, annotation_file, modality, transform, mode, action_list=None)` plus
-    keyword-only `device`, `threads` / `entropy` (handed to `decode_jpegs`) and `audio_cache_bytes` (cap of the device
-    waveform cache).  `transform` is the dictionary `get_transforms` returns: RGB / Flow need a `DevicePipeline`; the
-    Audio entry is not called, the spectrograms are born on the device as the fp32 tensor it would return.
+    keyword-only `device`, `threads` / `entropy` (handed to `decode_jpegs`), `audio_cache_bytes` (cap of the device
+    waveform cache) and `audio_load`: "host" (the default) reads a raw audio file with `read_wav` -- 16-bit PCM at
+    data.audio.sampling_rate, anything else raises; "device" sends the file through `audio_file.load_audio`, which decodes
+    any PCM width or float32, downmixes and resamples on the device like the reference's librosa.load (.wav files only;
+    audio pickles are read as before).  `transform` is the dictionary `get_transforms` returns: RGB / Flow need a
+    `DevicePipeline`; the Audio entry is not called, the spectrograms are born on the device as the fp32 tensor it would
+    return.
     `action_list` (the reference's `EpicClasses` filter) is out of scope and raises."""
 
     def __init__(self, cfg, vid_list, annotation_file, modality=["RGB"], transform=None, mode="train", action_list=None,
-                 *, device="cuda", threads=8, entropy="host", audio_cache_bytes=4 << 30):
+                 *, device="cuda", threads=8, entropy="host", audio_cache_bytes=4 << 30, audio_load="host"):
         import pandas as pd
         if action_list is not None and len(action_list) > 0:
             raise NotImplementedError("Video_Dataset: action_list needs the reference's EpicClasses verb / noun tables, "
                                       "which are out of scope here")
         if mode not in ("train", "val", "test"):
             raise ValueError(f"Video_Dataset: unknown mode {mode!r}")
+        if audio_load not in ("host", "device"):
+            raise ValueError(f"Video_Dataset: audio_load={audio_load!r} is not 'host' or 'device'")
         self.cfg = cfg
         self.root_dir = cfg.data_dir
         self.rgb_prefix, self.flow_prefix = cfg.data.rgb.dir_prefix, cfg.data.flow.dir_prefix
@@ -163,6 +170,11 @@ class Video_Dataset(object):
         if entropy not in ("host", "device"):
             raise ValueError(f"Video_Dataset: entropy={entropy!r} is not 'host' or 'device'")
         self.threads, self.entropy = threads, entropy
+        if audio_load == "device" and "Audio" in self.modality and not self.read_audio_pickle \
+                and str(self.aud_file_ext).lower() != "wav":
+            raise ValueError(f"Video_Dataset: audio_load='device' reads .wav files, data.audio.file_ext is "
+                             f"{self.aud_file_ext!r} (compressed audio is out of scope)")
+        self.audio_load = audio_load
         self.audio_cache_bytes = int(audio_cache_bytes)
         self._waves, self._wave_bytes = OrderedDict(), 0
         self._audio = None
@@ -285,10 +297,14 @@ class Video_Dataset(object):
         else:
             path = os.path.join(self.root_dir, self.audio_prefix, "{}.{}".format(vid_id, self.aud_file_ext))
             try:
-                sample = read_wav(path, self.aud_sampling_rate)
+                sample = (load_audio(path, self.aud_sampling_rate, device=self.device) if self.audio_load == "device"
+                          else read_wav(path, self.aud_sampling_rate))
             except Exception as e:
                 raise Exception("Failed to read audio sample {} with error {}".format(path, e))
-        wave_dev = torch.from_numpy(np.ascontiguousarray(sample, dtype=np.float32).reshape(-1)).to(self.device)
+        if torch.is_tensor(sample):
+            wave_dev = sample
+        else:
+            wave_dev = torch.from_numpy(np.ascontiguousarray(sample, dtype=np.float32).reshape(-1)).to(self.device)
         size = wave_dev.numel() * 4
         if size <= self.audio_cache_bytes:
             self._waves[vid_id] = wave_dev

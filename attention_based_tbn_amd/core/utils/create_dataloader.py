@@ -232,10 +232,11 @@ class ClipLoader(object):
             live.close()
 
 
-def create_dataloader(cfg, logger, modality, mode="test", device="cuda", *, prefetch=0):
+def create_dataloader(cfg, logger, modality, mode="test", device="cuda", *, prefetch=0, audio_load="host"):
     """The annotation file, video list and batch size per mode follow the reference (:86-120); val reads the TRAIN
     annotation file filtered by the val video list, as there.  A relative `vid_list` path is taken from the directory
-    above the `core` package, like the reference's; an empty one keeps every video.  `prefetch` is handed to `ClipLoader`."""
+    above the `core` package, like the reference's; an empty one keeps every video.  `prefetch` is handed to `ClipLoader`,
+    `audio_load` ("host" / "device": who reads raw audio files) to `Video_Dataset`."""
     logger.info(f"Creating {mode} Dataloader...")
     if mode == "train":
         vid_file, annotation_file, batch_size = cfg.train.vid_list, cfg.train.annotation_file, cfg.train.batch_size
@@ -254,7 +255,8 @@ def create_dataloader(cfg, logger, modality, mode="test", device="cuda", *, pref
         with open(os.path.join(file_dir, vid_file)) as f:
             vid_list = [x.strip() for x in f.readlines() if len(x.strip()) > 0]
     transforms = get_transforms(cfg, modality, mode, device=device, flow_length=2 * cfg.data.flow.win_length)
-    dataset = Video_Dataset(cfg, vid_list, annotation_file, modality, transform=transforms, mode=mode, device=device)
+    dataset = Video_Dataset(cfg, vid_list, annotation_file, modality, transform=transforms, mode=mode, device=device,
+                            audio_load=audio_load)
     loader = ClipLoader(dataset, batch_size, shuffle=(mode == "train"), prefetch=prefetch)
     logger.info("Done.")
     logger.info("----------------------------------------------------------")

@@ -727,6 +727,42 @@ int tbn_stft_windows(const float* const* window_ptrs, const float* wave, int nse
  * among the T values and their minimum, no arithmetic: bit-equal to the host function.  W >= T, W <= 4096. */
 int tbn_attn_prior_loud(const float* spec, int nseg, int F, int W, int T, const float* gauss, float* out, void* stream);
 
+/* ---- audio files: decode, downmix and resample ------------------------------------------------ */
+/* The waveform read of reference core/dataset/dataset.py:401-414 and preprocessing/create_audio_pickle.py:47-49,
+ * librosa.load(path, sr, mono=True), for the interleaved little-endian PCM bytes of a file's data chunk on the device:
+ *   decode    u8 (b - 128) / 128, s16 / 32768, s24 / 8388608, s32 / 2147483648, f32 as is (libsndfile's float32);
+ *   downmix   the float32 sum of the channels in channel order, divided by the channel count (librosa.to_mono);
+ *   resample  only when sr_orig != sr_new: resampy's `kaiser_best` windowed sinc (64 zero crossings, 512 table samples per
+ *             crossing, rolloff 0.9475937167399596, Kaiser beta 14.769656459379492, linear interpolation in the table,
+ *             step = int(min(1, sr_new / sr_orig) * 512) truncated as resampy truncates it, no gain correction), with the
+ *             position of output t taken EXACTLY (t * sr_orig / sr_new in 64-bit integers) where resampy accumulates a
+ *             floating-point time register; taps outside the clip are dropped;
+ *   length    out_len = ceil(frames * sr_new / sr_orig) (librosa's fix_length): the at most one sample past
+ *             floor(frames * sr_new / sr_orig) is exactly 0.
+ * The filter weights depend on t only through t mod phases: a bank of `phases` rows of `taps` float32 weights, laid out
+ * [tap][phase], computed on the host in float64 (Bessel I0 by its series) and rounded.  The two host entries below make no
+ * HIP call and need no GPU: the geometry query returns taps = 2 * ceil(32769 / step), phases = sr_new / gcd and
+ * floats = taps * phases (all 0 when sr_orig == sr_new: no bank), or TBN_ERR_UNSUPPORTED with a message when the bank would
+ * pass 64 MiB; the builder fills host_buffer, whose size `floats` must be the geometry's.  The caller copies the bank to the
+ * device.  The filter constants are restated from resampy 0.2.2 and were not checked against the library.
+ * The launch entry reads pcm (pcm_bytes = frames * channels * sample width, 4-byte aligned) and writes out (out_len floats)
+ * in ONE launch (profiler keys audio_load_kernel<uniform> for one phase, audio_load_kernel<phases> otherwise,
+ * audio_decode_kernel when sr_orig == sr_new, where bank may be NULL).  Everything is validated on the host before the
+ * launch: the format code, 1..8 channels, frames >= 1, pcm_bytes, out_len, 64-bit products, the bank pointer (TBN_ERR_ARG);
+ * a ratio whose tile of outputs spans more input than the kernel stages in LDS (down-sampling beyond about 12 : 1) is
+ * TBN_ERR_UNSUPPORTED.  The output-tile query is for tests: the seams of the kernel lie at its multiples.
+ * There is no capability bit: callers detect the feature by the symbol. */
+#define TBN_AUDIO_U8 0
+#define TBN_AUDIO_S16 1
+#define TBN_AUDIO_S24 2
+#define TBN_AUDIO_S32 3
+#define TBN_AUDIO_F32 4
+int tbn_audio_bank_geometry(int sr_orig, int sr_new, int* taps, int* phases, size_t* floats);
+int tbn_audio_make_bank(int sr_orig, int sr_new, float* host_buffer, size_t floats);
+int tbn_audio_tile(void);
+int tbn_audio_load(const void* pcm, size_t pcm_bytes, long long frames, int channels, int format, int sr_orig, int sr_new,
+                   const float* bank, float* out, long long out_len, void* stream);
+
 /* ---- train-step shell and metrics (the steps right after the path) -- */
 /* Multi-tensor clip_grad_norm_ + SGD(momentum) of reference core/tools/train.py:82-94,190-202
  * (torch.nn.utils.clip_grad_norm_ norm_type 2; torch.optim.SGD dampening 0, no nesterov).  All tensors of a
