@@ -91,6 +91,12 @@ class FramesClip(C.Structure):
                 ("resized_h", c_i), ("crop_x", c_i), ("crop_y", c_i), ("flip", c_i), ("out_row", c_i), ("reserved", c_i)]
 
 
+class InflateMember(C.Structure):
+    """include/tbn_hip.h tbn_inflate_member: one row of the member table of tbn_inflate_batch / tbn_inflate_host"""
+    _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("in_len", C.c_uint32), ("out_len", C.c_uint32),
+                ("crc", C.c_uint32), ("method", C.c_uint32), ("skip", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class MetricHead(C.Structure):
     """include/tbn_hip.h tbn_metric_head"""
     _fields_ = [("scores", c_fp), ("scores_ld", c_i), ("classes", c_i), ("target", c_fp), ("conf_mat", c_fp)]
@@ -241,6 +247,9 @@ SIGNATURES = {
                                  C.POINTER(c_sz)]),
     "tbn_jpeg_entropy_workspace_bytes": (c_sz, [C.POINTER(JpegGeometry), c_i]),
     "tbn_jpeg_entropy_decode_dev": (c_i, [c_fp, c_sz, c_fp, c_i, C.POINTER(JpegGeometry), c_i, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    # reference core/dataset/dataset.py:342-343 (np.load of a flow pickle): inflate + CRC-32 of zip members, one wavefront each
+    "tbn_inflate_batch": (c_i, [c_fp, c_sz, c_fp, c_i, c_fp, c_sz, c_fp, c_fp, c_fp]),
+    "tbn_inflate_host": (c_i, [c_fp, c_sz, c_fp, c_i, c_fp, c_sz, c_fp, c_fp]),
 }
 
 _lib = None

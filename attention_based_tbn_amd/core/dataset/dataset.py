@@ -27,6 +27,7 @@ from ..._lib import TbnHipError
 from .audio import AudioSegments
 from .audio_file import load_audio
 from .frames import FrameReader, decode_jpegs, geometry_key, jpeg_geometry
+from .npz_file import load_npz_arrays, npz_member
 from .sampler import frame_span, get_offsets
 from .transform import DevicePipeline
 
@@ -96,10 +97,11 @@ def read_wav(path, sampling_rate):
 class _Visual(object):
     """what `plan` records for one clip and one visual modality"""
 
-    def __init__(self, paths, blobs, arrays, key, hw, geo, file_keys):
+    def __init__(self, paths, blobs, arrays, key, hw, geo, file_keys, records=None):
         self.paths = paths      # the files, in frame order (Flow: x, y interleaved; pickles: one per segment)
-        self.blobs = blobs      # their bytes (JPEG), or None
-        self.arrays = arrays    # flow pickles: uint8 (n_img, H, W, 1), or None
+        self.blobs = blobs      # their bytes (JPEG; flow pickles with flow_load="device"), or None
+        self.arrays = arrays    # flow pickles read on the host: uint8 (n_img, H, W, 1), or None
+        self.records = records  # flow pickles with flow_load="device": the `npz_member` record of every file
         self.key = key          # clips of one key (kind, H, W) launch together
         self.file_keys = file_keys   # JPEG: per file, what makes files one `decode_jpegs` call (size, components, sampling)
         self.hw = hw            # source frame size
@@ -122,13 +124,17 @@ class Video_Dataset(object):
     waveform cache) and `audio_load`: "host" (the default) reads a raw audio file with `read_wav` -- 16-bit PCM at
     data.audio.sampling_rate, anything else raises; "device" sends the file through `audio_file.load_audio`, which decodes
     any PCM width or float32, downmixes and resamples on the device like the reference's librosa.load (.wav files only;
-    audio pickles are read as before).  `transform` is the dictionary `get_transforms` returns: RGB / Flow need a
+    audio pickles are read as before).  `flow_load` matters only with data.flow.read_flow_pickle: "host" (the default)
+    reads each frame_XXXXXXXXXX.npz with np.load inside `plan`; "device" keeps the files' bytes and inflates every pickle
+    of a batch with one `npz_file.load_npz_arrays` call (`flow_fallbacks` counts the members that still took np.load).
+    `transform` is the dictionary `get_transforms` returns: RGB / Flow need a
     `DevicePipeline`; the Audio entry is not called, the spectrograms are born on the device as the fp32 tensor it would
     return.
     `action_list` (the reference's `EpicClasses` filter) is out of scope and raises."""
 
     def __init__(self, cfg, vid_list, annotation_file, modality=["RGB"], transform=None, mode="train", action_list=None,
-                 *, device="cuda", threads=8, entropy="host", audio_cache_bytes=4 << 30, audio_load="host"):
+                 *, device="cuda", threads=8, entropy="host", audio_cache_bytes=4 << 30, audio_load="host",
+                 flow_load="host"):
         import pandas as pd
         if action_list is not None and len(action_list) > 0:
             raise NotImplementedError("Video_Dataset: action_list needs the reference's EpicClasses verb / noun tables, "
@@ -137,6 +143,9 @@ class Video_Dataset(object):
             raise ValueError(f"Video_Dataset: unknown mode {mode!r}")
         if audio_load not in ("host", "device"):
             raise ValueError(f"Video_Dataset: audio_load={audio_load!r} is not 'host' or 'device'")
+        if flow_load not in ("host", "device"):
+            raise ValueError(f"Video_Dataset: flow_load={flow_load!r} is not 'host' or 'device'")
+        self.flow_load, self.flow_fallbacks = flow_load, 0
         self.cfg = cfg
         self.root_dir = cfg.data_dir
         self.rgb_prefix, self.flow_prefix = cfg.data.rgb.dir_prefix, cfg.data.flow.dir_prefix
@@ -208,8 +217,61 @@ class Video_Dataset(object):
                             "uint8 (H, W, 2 * win_length).")
         return np.ascontiguousarray(flow.transpose(2, 0, 1))[:, :, :, None]      # channel c = gray frame c
 
+    def _read_flow_pickle_records(self, paths):
+        """flow_load="device": the bytes of every pickle and its `npz_member` record; nothing is inflated here.  The frame
+        size `plan` needs comes from the record; a member the record sends to the host is read by `_read_flow_pickle` at
+        once (its size has to come from somewhere, and whatever it raises is the host path's message)."""
+        blobs, records, shapes = [], [], []
+        for p in paths:
+            try:
+                with open(p, "rb") as f:
+                    blob = f.read()
+                record = npz_member(blob)
+            except Exception as e:
+                raise Exception("Failed to load flow file {} with error {}.".format(p, e))
+            if record.host:
+                planes = self._read_flow_pickle(p)                 # (C, H, W, 1)
+                shapes.append((int(planes.shape[1]), int(planes.shape[2]), int(planes.shape[0])))
+            else:
+                shapes.append(tuple(int(v) for v in record.shape))
+            blobs.append(blob)
+            records.append(record)
+        for p, shape in zip(paths, shapes):
+            if shape[:2] != shapes[0][:2]:
+                raise TbnHipError(f"Video_Dataset: the flow pickles of one clip differ in size: {paths[0]} is "
+                                  f"{shapes[0][1]}x{shapes[0][0]}, {p} is {shape[1]}x{shape[0]}")
+        hw = shapes[0][:2]
+        v = _Visual(paths, blobs, None, ("npz",) + hw, hw, None, None, records)
+        v.shapes = shapes
+        return v
+
+    def _inflate_pickles(self, visuals):
+        """every pickle of a launch group -> uint8 (n_img, H, W, 1) on the device: one `load_npz_arrays` call per run of
+        files of one (H, W, C) -- one call for a dataset written with one win_length"""
+        paths = [p for v in visuals for p in v.paths]
+        blobs = [b for v in visuals for b in v.blobs]
+        records = [r for v in visuals for r in v.records]
+        shapes = [s for v in visuals for s in v.shapes]
+        parts, first = [], 0
+        while first < len(paths):
+            last = first
+            while last < len(paths) and shapes[last] == shapes[first]:
+                last += 1
+
+            def host_read(i, first=first):
+                return self._read_flow_pickle(paths[first + i])[:, :, :, 0].transpose(1, 2, 0)
+
+            planes, statuses = load_npz_arrays(blobs[first:last], device=self.device, records=records[first:last], planes=True,
+                                               host_read=host_read)
+            self.flow_fallbacks += sum(1 for s in statuses if s != 0)
+            parts.append(planes)
+            first = last
+        return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+
     def _read_visual(self, m, vid_id, indices):
         paths = self._frame_files(m, vid_id, indices)
+        if m == "Flow" and self.read_flow_pickle and self.flow_load == "device":
+            return self._read_flow_pickle_records(paths)
         if m == "Flow" and self.read_flow_pickle:
             arrays = np.concatenate([self._read_flow_pickle(p) for p in paths], 0)
             hw = (int(arrays.shape[1]), int(arrays.shape[2]))
@@ -257,7 +319,9 @@ class Video_Dataset(object):
             order.setdefault(clip.visual[m].key, []).append(b)
         groups = []
         for key, part in order.items():
-            if key[0] == "npz":
+            if key[0] == "npz" and self.flow_load == "device":
+                groups.append(self._inflate_pickles([clips[b].visual[m] for b in part]))
+            elif key[0] == "npz":
                 arr = np.concatenate([clips[b].visual[m].arrays for b in part], 0)
                 groups.append(torch.from_numpy(arr).to(self.device, non_blocking=True))
             else:

@@ -1,0 +1,199 @@
+"""Flow pickles on the device: the `flow` member of the reference's frame_XXXXXXXXXX.npz stacks
+(preprocessing/create_epic_flow_pickle.py: np.savez_compressed(out_file, flow=img); read by np.load in
+core/dataset/dataset.py:336-352).
+
+The host keeps what is small and irregular -- the zip directory and the 128-byte .npy header (`npz_member`); the
+device does what is large: `load_npz_arrays` packs the members' compressed bytes of a whole batch into one pinned buffer,
+copies it once, and `tbn_inflate_batch` (csrc/inflate.hip) inflates every member and checks its CRC-32 in one call.  One
+small copy back of the status vector is the only synchronisation.  A member the record or the status sends to the host
+(anything np.load reads that this path does not: another dtype, Fortran order, a damaged stream, ...) is read by the
+host code into its slot, so a batch may mix both and error wording stays the host path's; those members are counted."""
+import ast
+import ctypes
+import io
+import struct
+import zipfile
+import zlib
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from ..._lib import InflateMember, TbnHipError, call, ptr, stream_ptr
+
+NpzMember = namedtuple("NpzMember", "method data_offset data_length size crc header_length shape host reason")
+NpzMember.__doc__ = """What `npz_member` reports: `method` 0 (stored) or 8 (deflate); the member's compressed bytes are
+blob[data_offset : data_offset + data_length]; `size`: its inflated size (the .npy header and the array); `crc`: the
+directory's CRC-32; `header_length`: bytes of the .npy header in front of the array; `shape`: (H, W, C).  `host` True:
+the member takes the host path (np.load), `reason` says why and the other fields are None where they are unknown."""
+
+STATUS_SKIPPED = 11        # include/tbn_hip.h: the row carried the skip marker
+_ALIGN = 16
+_PREFIX = 4096             # inflated bytes looked at for the .npy header
+_counts = {"members": 0, "fallbacks": 0}
+
+
+def fallback_count():
+    """members `load_npz_arrays` has sent through the host path so far (of `member_count()` in all)"""
+    return _counts["fallbacks"]
+
+
+def member_count():
+    return _counts["members"]
+
+
+def _host(reason, **known):
+    fields = dict(method=None, data_offset=None, data_length=None, size=None, crc=None, header_length=None, shape=None)
+    fields.update(known)
+    return NpzMember(host=True, reason=reason, **fields)
+
+
+def npz_member(blob, name="flow"):
+    """The record of member `name` (.npy is appended) of the .npz file `blob` (bytes).  Touches no GPU and inflates at
+    most the first 4096 bytes.  Sizes, method, CRC and the local header's offset come from the zip CENTRAL DIRECTORY: the
+    local header holds 0xFFFFFFFF or zeros there when the writer used zip64 extras (numpy >= 2.2 writes a 20-byte one in
+    every local header) or a data descriptor (a non-seekable stream); only its name and extra lengths are read.
+    Raises `zipfile.BadZipFile` on bytes that are not a zip file (or one cut short); everything else np.load might
+    still read, and everything it would refuse with its own message, comes back with `host=True`."""
+    zf = zipfile.ZipFile(io.BytesIO(blob))
+    try:
+        info = zf.getinfo(name + ".npy")
+    except KeyError:
+        return _host(f"no member {name}.npy")
+    known = dict(method=info.compress_type, size=info.file_size, crc=info.CRC, data_length=info.compress_size)
+    if info.flag_bits & 0x1:
+        return _host("the member is encrypted", **known)
+    if info.compress_type not in (zipfile.ZIP_STORED, zipfile.ZIP_DEFLATED):
+        return _host(f"compression method {info.compress_type}", **known)
+    if info.file_size >= 1 << 31 or info.compress_size >= 1 << 31:
+        return _host("a member of 2 GiB or more", **known)
+    at = info.header_offset
+    if at + 30 > len(blob) or blob[at:at + 4] != b"PK\x03\x04":
+        raise zipfile.BadZipFile(f"no local file header at offset {at}")
+    name_len, extra_len = struct.unpack_from("<HH", blob, at + 26)
+    start = at + 30 + name_len + extra_len
+    if start + info.compress_size > len(blob):
+        raise zipfile.BadZipFile("the member's data runs past the end of the file")
+    known["data_offset"] = start
+    data = memoryview(blob)[start:start + info.compress_size]
+    if info.compress_type == zipfile.ZIP_DEFLATED:
+        try:
+            head = zlib.decompressobj(-15).decompress(data, _PREFIX)
+        except zlib.error as e:
+            return _host(f"the .npy header does not inflate: {e}", **known)
+    else:
+        head = bytes(data[:_PREFIX])
+    if len(head) < 10 or head[:6] != b"\x93NUMPY":
+        return _host("no .npy magic", **known)
+    if (head[6], head[7]) != (1, 0):
+        return _host(f".npy header version {head[6]}.{head[7]}", **known)
+    header_length = 10 + struct.unpack_from("<H", head, 8)[0]
+    if header_length > len(head):
+        return _host("the .npy header is cut short", **known)
+    try:
+        fields = ast.literal_eval(head[10:header_length].decode("latin1"))
+        descr, fortran, shape = fields["descr"], fields["fortran_order"], tuple(fields["shape"])
+    except Exception as e:
+        return _host(f"the .npy header does not parse: {e}", **known)
+    known["header_length"] = header_length
+    if descr not in ("|u1", "u1"):
+        return _host(f"dtype {descr!r}", **known)
+    if fortran:
+        return _host("Fortran order", **known)
+    if len(shape) != 3 or not all(isinstance(v, int) and v >= 0 for v in shape):
+        return _host(f"shape {shape}", **known)
+    known["shape"] = shape
+    if info.file_size != header_length + shape[0] * shape[1] * shape[2]:
+        return _host("the member's size is not its header plus H * W * C", **known)
+    return NpzMember(host=False, reason=None, **known)
+
+
+def read_npz_host(blob, name="flow"):
+    """the host path of one member: np.load, with np.load's exceptions"""
+    with np.load(io.BytesIO(blob)) as z:
+        return np.asarray(z[name])
+
+
+def load_npz_arrays(blobs, name="flow", device="cuda", *, records=None, planes=False, host_read=None):
+    """Member `name` of every .npz file in `blobs` (bytes each), all of ONE shape (H, W, C) uint8, inflated on `device`
+    by one `tbn_inflate_batch` call on the current stream -> (tensor, statuses).
+
+    tensor     uint8 (n, H, W, C) in stream layout (a view into the staging buffer), or with `planes=True` the
+               de-interleaved (n * C, H, W, 1) the dataset wants (image c of file i is channel c of its array): one
+               permute(...).contiguous() pass on the device.
+    statuses   per member, 0: inflated and CRC-checked on the device; otherwise the status of tbn_inflate_batch
+               (include/tbn_hip.h; 11: the record said "host") -- that member was read by `host_read(i)` (default: np.load of
+               blobs[i]; returns uint8 (H, W, C)) into its slot, and counted (`fallback_count()`).  What the host path
+               raises for it propagates.
+    records    the `npz_member` records when the caller has them already."""
+    n = len(blobs)
+    if n == 0:
+        raise ValueError("load_npz_arrays: no files")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise TbnHipError(f"load_npz_arrays: device {device} is not a GPU; there is no host version of this path "
+                          "(np.load is the host path)")
+    if records is None:
+        records = [npz_member(b, name) for b in blobs]
+    if host_read is None:
+        def host_read(i):
+            return read_npz_host(blobs[i], name)
+    # the host members first: the shape may have to come from them, and what they raise should come before any launch
+    host_arrays = {}
+    for i, r in enumerate(records):
+        if r.host:
+            arr = np.asarray(host_read(i))
+            if arr.dtype != np.uint8 or arr.ndim != 3:
+                raise TbnHipError(f"load_npz_arrays: file {i}: {name!r} is {arr.dtype} {arr.shape}, expected uint8 (H, W, C)")
+            host_arrays[i] = arr
+    shapes = set(tuple(host_arrays[i].shape) if r.host else r.shape for i, r in enumerate(records))
+    if len(shapes) != 1:
+        raise TbnHipError(f"load_npz_arrays: the files of one call must share a shape, got {sorted(shapes)}")
+    H, W, Cn = shapes.pop()
+    payload = H * W * Cn
+    dev_rows = [r for r in records if not r.host]
+    header = dev_rows[0].header_length if dev_rows else 0
+    if any(r.header_length != header for r in dev_rows):
+        header = None                       # headers of several lengths: the arrays are gathered one by one below
+    slot = -(-(max([r.size for r in dev_rows] + [payload])) // _ALIGN) * _ALIGN
+
+    table = (InflateMember * n)()
+    total = 0
+    for i, r in enumerate(records):
+        row = table[i]
+        row.out_off, row.skip = i * slot, int(r.host)
+        if not r.host:
+            row.in_off, row.in_len, row.out_len, row.crc, row.method = total, r.data_length, r.size, r.crc, r.method
+            total += -(-r.data_length // _ALIGN) * _ALIGN
+    in_bytes = max(total, _ALIGN)
+    table_bytes = ctypes.sizeof(table)
+    staging = torch.empty(in_bytes + table_bytes, dtype=torch.uint8, pin_memory=True)   # ONE pinned buffer, ONE copy
+    flat = staging.numpy()
+    for i, r in enumerate(records):
+        if not r.host:
+            at = table[i].in_off
+            flat[at:at + r.data_length] = np.frombuffer(blobs[i], np.uint8, r.data_length, r.data_offset)
+    flat[in_bytes:] = np.frombuffer(table, np.uint8)
+    dev = staging.to(device, non_blocking=True)
+    out = torch.empty(n * slot, dtype=torch.uint8, device=device)
+    status = torch.empty(2 * n, dtype=torch.int32, device=device)          # status[n], then info[n]
+    call("tbn_inflate_batch", ptr(dev), in_bytes, ptr(dev) + in_bytes, n, ptr(out), n * slot, ptr(status), ptr(status) + 4 * n,
+         stream_ptr())
+    rows = out.view(n, slot)
+    if header is not None:
+        arrays = rows[:, header:header + payload].view(n, H, W, Cn)
+    else:
+        arrays = torch.stack([rows[i, (r.header_length or 0):(r.header_length or 0) + payload] for i, r in enumerate(records)]
+                             ).view(n, H, W, Cn)
+    statuses = status[:n].tolist()                                          # one small copy back: the only synchronisation
+    _counts["members"] += n
+    for i, s in enumerate(statuses):
+        if s != 0:
+            arr = host_arrays[i] if i in host_arrays else np.asarray(host_read(i))
+            if arr.dtype != np.uint8 or tuple(arr.shape) != (H, W, Cn):
+                raise TbnHipError(f"load_npz_arrays: file {i}: {name!r} is {arr.dtype} {arr.shape}, expected uint8 {(H, W, Cn)}")
+            arrays[i].copy_(torch.from_numpy(np.ascontiguousarray(arr)), non_blocking=False)
+            _counts["fallbacks"] += 1
+    if planes:
+        arrays = arrays.permute(0, 3, 1, 2).contiguous().view(n * Cn, H, W, 1)
+    return arrays, statuses

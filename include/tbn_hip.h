@@ -988,6 +988,46 @@ int tbn_jpeg_entropy_decode_dev(const void* packed_dev, size_t packed_bytes, con
                                 const tbn_jpeg_geometry* geometry, int subseq_bits, int16_t* coef_dev, int* status_dev,
                                 int* info_dev, void* workspace, void* stream);
 
+/* ---- flow pickles: zip members (stored or raw deflate, RFC 1951) inflated on the device (opt-in) ---------- */
+/* Replaces np.load of reference core/dataset/dataset.py:342-343 (the `flow` member of a frame_XXXXXXXXXX.npz written by
+ * np.savez / np.savez_compressed): the zlib inflate and the CRC-32 check.  The zip directory and the .npy header stay host
+ * work (core/dataset/npz_file.py).  The decoder core is csrc/tbn_inflate.h.  There is no capability bit: callers detect
+ * the feature by the symbol.
+ * One row of the member table (40 bytes):
+ *   in_off, in_len   the member's compressed bytes inside `in`; in_off is a multiple of 4
+ *   out_off, out_len where its inflated bytes go inside `out`, and the size the directory declares: exactly out_len
+ *                    bytes are produced or the status says why not.  Rows must not overlap in `out` (not checked).
+ *   crc              the directory's CRC-32 of the inflated bytes
+ *   method           0 (stored: a copy) or 8 (deflate); no zlib or gzip wrapper
+ *   skip             non-zero: the member takes the host path; nothing is read or written for it (status 11)
+ * Limits: in_len and out_len below 2^31 (no zip64 members).
+ * status[i]: 0 ok, the bytes are the member's and their CRC-32 matched; 1 reserved block type; 2 stored LEN != ~NLEN;
+ * 3 code lengths (HLIT > 286, HDIST > 30, a bad repeat, an over-subscribed code, or an incomplete one where zlib refuses
+ * it); 4 a symbol that does not exist (literal/length 286, 287, distance 30, 31, an unused code); 5 no end-of-block code;
+ * 6 distance before the start of the output; 7 input exhausted; 8 output would pass out_len; 9 output ends short of
+ * out_len; 10 CRC-32 mismatch; 11 skipped; 12 inconsistent row (a range outside the buffers, a misaligned in_off,
+ * another method, a size of 2^31 or more).  With a non-zero status the member's out bytes are unspecified, but nothing
+ * outside [out_off, out_off + out_len) is written and nothing outside [in_off, in_off + in_len) is read: a damaged file
+ * costs a status, never a fault or a hang.  info[i]: bytes produced. */
+typedef struct tbn_inflate_member {
+  uint64_t in_off, out_off;
+  uint32_t in_len, out_len;
+  uint32_t crc;
+  uint32_t method;
+  uint32_t skip;
+  uint32_t reserved;
+} tbn_inflate_member;
+/* DEVICE.  Two launches on `stream`: one wavefront per member inflates (or copies) it, then one workgroup per member
+ * computes the CRC-32 of the staged bytes and folds a mismatch into the status.  in_dev[0, in_bytes): the packed
+ * compressed bytes, 4-byte aligned; members_dev[n_members]: the table, in device memory, 8-byte aligned;
+ * out_dev[0, out_bytes): the staging buffer; status_dev / info_dev: n_members ints each.  n_members == 0 launches nothing. */
+int tbn_inflate_batch(const void* in_dev, size_t in_bytes, const tbn_inflate_member* members_dev, int n_members,
+                      void* out_dev, size_t out_bytes, int* status_dev, int* info_dev, void* stream);
+/* HOST, thread-safe, no GPU call: the same decoder core and the same chunked CRC run serially over the same table, all
+ * pointers host memory.  The test aid of tbn_inflate_batch. */
+int tbn_inflate_host(const void* in, size_t in_bytes, const tbn_inflate_member* members, int n_members, void* out,
+                     size_t out_bytes, int* status, int* info);
+
 #ifdef __cplusplus
 }
 #endif
