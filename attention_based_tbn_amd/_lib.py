@@ -152,6 +152,8 @@ SIGNATURES = {
     "tbn_conv_launch_pair": (c_i, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), c_i, c_i, c_i, c_fp, c_fp, c_fp]),
     "tbn_conv2d_wgrad_workspace_floats": (c_sz, [c_i] * 8),
     "tbn_conv2d_wgrad": (c_i, [c_fp, c_i, c_fp, c_i, c_fp] + [c_i] * 8 + [c_fp, c_fp]),
+    "tbn_conv2d_wgrad_tile": (c_i, [c_fp, c_i, c_fp, c_i, c_fp] + [c_i] * 10 + [c_fp, c_fp]),
+    "tbn_conv2d_wgrad_plan": (C.c_longlong, [c_i] * 10 + [C.POINTER(c_i)]),
     "tbn_stem_geometry": (c_i, [c_i, c_i, c_i, c_i, C.POINTER(c_i)]),
     "tbn_stem_workspace_floats": (c_sz, [c_i] * 6),
     "tbn_stem_conv_fwd": (c_i, [c_fp, c_fp, c_fp, c_fp] + [c_i] * 8 + [c_fp, c_fp, c_fp] + [c_i] * 3 + [c_fp, c_fp]),

@@ -569,6 +569,46 @@ int tbn_conv2d_wgrad(const float* dout, int dout_ld, const float* in, int in_ld,
   return tbn_launch_wgrad(wp, 0, dweight, workspace, (hipStream_t)stream);
 }
 
+// the checks the two explicit-tile entries share (host only); `who` prefixes the message
+static int wgrad_tile_args_ok(const char* who, int n, int h, int w, int cin, int cout, int ksize, int stride, int pad, int mt,
+                              int nt) {
+  TBN_REQUIRE(tbn_wgrad_tile_ok(mt, nt), "%s: tile %dx%d (mt 1 | 2 | 3 | 5, nt 1..3 without 5x3, or 0x0)", who, mt, nt);
+  TBN_REQUIRE(n >= 1 && h >= 1 && w >= 1 && ksize >= 1 && stride >= 1 && pad >= 0 && h + 2 * pad >= ksize && w + 2 * pad >= ksize,
+              "%s: bad shape (%d frames of %dx%d, filter %d / stride %d / pad %d)", who, n, h, w, ksize, stride, pad);
+  TBN_REQUIRE(cin >= 4 && cout >= 4 && cin % 4 == 0 && cout % 4 == 0, "%s: cin %d / cout %d must be multiples of 4", who, cin, cout);
+  return TBN_OK;
+}
+
+int tbn_conv2d_wgrad_tile(const float* dout, int dout_ld, const float* in, int in_ld, float* dweight, int n, int h, int w,
+                          int cin, int cout, int ksize, int stride, int pad, int mt, int nt, float* workspace, void* stream) {
+  TBN_REQUIRE(dout && in && dweight, "conv2d_wgrad_tile: null pointer");
+  TBN_TRY(wgrad_tile_args_ok("conv2d_wgrad_tile", n, h, w, cin, cout, ksize, stride, pad, mt, nt));
+  TBN_REQUIRE(dout_ld >= cout && dout_ld % 4 == 0, "conv2d_wgrad_tile: dout_ld %d (at least cout, a multiple of 4)", dout_ld);
+  TBN_REQUIRE(in_ld >= cin && in_ld % 4 == 0, "conv2d_wgrad_tile: in_ld %d (at least cin, a multiple of 4)", in_ld);
+  WgradP wp;
+  wgrad_geom(&wp, n, h, w, cin, cout, ksize, stride, pad);
+  wp.dy = dout;
+  wp.dy_ld = dout_ld;
+  wp.x = in;
+  wp.x_ld = in_ld;
+  wp.mt = mt;
+  wp.nt = nt;
+  return tbn_launch_wgrad(wp, 0, dweight, workspace, (hipStream_t)stream);
+}
+
+long long tbn_conv2d_wgrad_plan(int n, int h, int w, int cin, int cout, int ksize, int stride, int pad, int mt, int nt, int* out8) {
+  TBN_REQUIRE(out8 != nullptr, "conv2d_wgrad_plan: null out");
+  TBN_TRY(wgrad_tile_args_ok("conv2d_wgrad_plan", n, h, w, cin, cout, ksize, stride, pad, mt, nt));
+  WgradP wp;
+  wgrad_geom(&wp, n, h, w, cin, cout, ksize, stride, pad);
+  wp.mt = mt;
+  wp.nt = nt;
+  const WgradLaunchPlan q = tbn_wgrad_launch_plan(wp, 0);
+  const int v[8] = {q.mt, q.nt, q.mode, q.splits, q.rows_per_split, q.tiles_co, q.tiles_ci, q.reduce};
+  memcpy(out8, v, sizeof(v));
+  return (long long)q.ws_floats;
+}
+
 // ---- the 7x7 / stride 2 / pad 3 stem on its own (test / tuning aid): the launches the engine issues for conv1_7x7_s2, built
 // from stem_geom (tbn_kernels.h) as build_graph / fill_fwd / fill_wgrad build them from the plan
 // workspace regions (float offsets, 256-B aligned like the engine's): bordered image | packed weights | packed dW | split-K slabs
@@ -680,7 +720,7 @@ int tbn_stem_conv_wgrad(const float* dy, int dy_ld, const float* x_nchw, float* 
   TBN_REQUIRE(dy && x_nchw && dweight && workspace, "stem_conv_wgrad: null pointer");
   TBN_TRY(stem_args_ok("stem_conv_wgrad", n, h, w, cin, cout, layout, workspace));
   TBN_REQUIRE(dy_ld >= cout && dy_ld % 4 == 0, "stem_conv_wgrad: dy_ld %d (at least cout, a multiple of 4)", dy_ld);
-  TBN_REQUIRE((mt == 0 && nt == 0) || (((mt >= 1 && mt <= 3) || mt == 5) && nt >= 1 && nt <= 3 && !(mt == 5 && nt == 3)),
+  TBN_REQUIRE(tbn_wgrad_tile_ok(mt, nt),
               "stem_conv_wgrad: tile %dx%d (mt 1 | 2 | 3 | 5, nt 1..3 without 5x3, or 0x0)", mt, nt);
   hipStream_t st = (hipStream_t)stream;
   const StemGeom g = stem_geom(cin, h, w, layout);

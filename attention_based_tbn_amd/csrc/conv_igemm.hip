@@ -1653,18 +1653,32 @@ static void launch_wgrad(const WgradP& p, int blocks, hipStream_t st) {
   TBN_LAUNCH((conv_wgrad_kernel<MT, NT, MODE>), dim3(blocks), dim3(256), (MT == 2 && NT == 2) ? pad : 0, st, p);
 }
 
-// f(integral_constant<int, MT>, integral_constant<int, NT>) for the weight-gradient tile (mt, nt): {1, 2, 3, 5} x {1, 2, 3}
-// without (5, 3), which does not fit the register file; any other tile is refused (I walks the admitted tiles in row order)
+// The weight-gradient tiles, in row order: {1, 2, 3, 5} x {1, 2, 3} without (5, 3), which does not fit the register file
+constexpr int kWgradTiles = 11;
+constexpr int wgrad_tile_mt(int i) { return i / 3 == 3 ? 5 : i / 3 + 1; }
+constexpr int wgrad_tile_nt(int i) { return i % 3 + 1; }
+
+// f(integral_constant<int, MT>, integral_constant<int, NT>) for the weight-gradient tile (mt, nt); any tile outside the
+// table above is refused (I walks it)
 template <int I = 0, class F>
 static int with_wgrad_tile(int mt, int nt, F&& f) {
-  if constexpr (I == 11) {
+  if constexpr (I == kWgradTiles) {
     tbn_set_error("wgrad: unsupported tile");
     return TBN_ERR_UNSUPPORTED;
   } else {
-    constexpr int MT = I / 3 == 3 ? 5 : I / 3 + 1, NT = I % 3 + 1;
+    constexpr int MT = wgrad_tile_mt(I), NT = wgrad_tile_nt(I);
     if (mt == MT && nt == NT) return f(std::integral_constant<int, MT>{}, std::integral_constant<int, NT>{});
     return with_wgrad_tile<I + 1>(mt, nt, f);
   }
+}
+
+// THE tile rule of every entry that takes a weight-gradient tile (the conv and stem C-ABI entries, plan import): 0 x 0 = the
+// heuristic, or a tile of the table.  Anything else -- tbn_wgrad_plan would replace it silently -- is for the caller to refuse.
+bool tbn_wgrad_tile_ok(int mt, int nt) {
+  if (mt == 0 && nt == 0) return true;
+  for (int i = 0; i < kWgradTiles; ++i)
+    if (mt == wgrad_tile_mt(i) && nt == wgrad_tile_nt(i)) return true;
+  return false;
 }
 
 // 32-column sub-tiles per workgroup along one dimension: 3 for 96 (and other odd multiples of 96), else 2 when the
@@ -1744,6 +1758,22 @@ size_t tbn_wgrad_workspace_floats(int M, int Cout, int Cin, int taps) {
   return worst;
 }
 
+// Every launch decision of tbn_launch_wgrad in one place (the launcher runs exactly this; tbn_conv2d_wgrad_plan reports it)
+WgradLaunchPlan tbn_wgrad_launch_plan(const WgradP& p, int rowmode) {
+  WgradLaunchPlan q;
+  q.mt = p.mt;   // 0: heuristic tile
+  q.nt = p.nt;
+  tbn_wgrad_plan(p.M, p.Cout, p.Cin, p.taps, &q.mt, &q.nt, &q.splits, &q.rows_per_split);
+  q.tiles_co = cdiv(p.Cout, 32 * q.mt);
+  q.tiles_ci = cdiv(p.Cin, 32 * q.nt);
+  q.mode = rowmode ? 1 : ((p.taps == 1 && p.stride == 1 && p.pad == 0 && p.OH == p.H && p.OW == p.W) ? 2 : 0);
+  const size_t n4 = (size_t)p.Cout * p.taps * p.Cin / 4;
+  // many slabs of a small matrix: 16 slab lanes per output so that the reduce grid still covers the chip
+  q.reduce = q.splits > 1 ? ((q.splits >= 32 && n4 < 64 * 1024) ? 16 : 4) : 0;
+  q.ws_floats = q.splits > 1 ? (size_t)q.splits * p.Cout * p.taps * p.Cin : 0;
+  return q;
+}
+
 int tbn_launch_wgrad(WgradP p, int rowmode, float* dw, float* workspace, hipStream_t st) {
   TBN_REQUIRE(p.Cin % 4 == 0 && p.Cout % 4 == 0 && p.dy_ld % 4 == 0 && (rowmode || p.x_ld % 4 == 0),
               "wgrad: channel counts / pitches must be multiples of 4");
@@ -1770,17 +1800,16 @@ int tbn_launch_wgrad(WgradP p, int rowmode, float* dw, float* workspace, hipStre
                 "wgrad: packed-row mode reads beyond the padded image (%dx%d)", p.H, p.W);
   }
   p.div_rl4 = make_fastdiv((uint32_t)(rowmode ? p.rl / 4 : 1));
-  int mt = p.mt, nt = p.nt, splits, rps;   // 0: heuristic tile
-  tbn_wgrad_plan(p.M, p.Cout, p.Cin, p.taps, &mt, &nt, &splits, &rps);
+  const WgradLaunchPlan plan = tbn_wgrad_launch_plan(p, rowmode);
+  const int mt = plan.mt, nt = plan.nt, splits = plan.splits, rps = plan.rows_per_split, mode = plan.mode;
   p.K = p.taps * p.Cin;
-  p.tiles_co = cdiv(p.Cout, 32 * mt);
-  p.tiles_ci = cdiv(p.Cin, 32 * nt);
+  p.tiles_co = plan.tiles_co;
+  p.tiles_ci = plan.tiles_ci;
   p.rows_per_split = rps;
   p.div_ohw = make_fastdiv((uint32_t)(p.OH * p.OW));
   p.div_ow = make_fastdiv((uint32_t)p.OW);
   // incremental row addressing (see the kernel): 64 rows per step
   TBN_REQUIRE(rps % 64 == 0, "wgrad: rows per split must be a multiple of 64");
-  const int mode = rowmode ? 1 : ((p.taps == 1 && p.stride == 1 && p.pad == 0 && p.OH == p.H && p.OW == p.W) ? 2 : 0);
   {
     const uint64_t ohw = (uint64_t)p.OH * p.OW;
     TBN_REQUIRE(ohw * p.OW < (1ull << 32) && p.H < (1 << 23) && p.W < (1 << 23) && (uint64_t)p.H * p.W < (1ull << 24) &&
@@ -1821,7 +1850,7 @@ int tbn_launch_wgrad(WgradP p, int rowmode, float* dw, float* workspace, hipStre
   if (splits > 1) {
     const size_t n = (size_t)p.Cout * p.K;
     const int n4 = (int)(n / 4);
-    if (splits >= 32 && n4 < 64 * 1024)
+    if (plan.reduce == 16)
       TBN_KLAUNCH(splitk_reduce_kernel<16>, dim3(cdiv(n4, 16)), dim3(256), 0, st, workspace, dw, n4, splits, n / 4);
     else
       TBN_KLAUNCH(splitk_reduce_kernel<4>, dim3(cdiv(n4, 64)), dim3(256), 0, st, workspace, dw, n4, splits, n / 4);

@@ -966,7 +966,7 @@ int tbn_backbone_plan_import(tbn_backbone_plan* P, const void* buf, size_t bytes
     ok = ok && !(d[4] == 1 && (c.pair_next < 0 || c.stride != 1));
     ok = ok && !(d[3] == 3 && (d[0] > 2 || d[1] > 2 || c.stride != 1));
     ok = ok && !((d[3] == 1 || d[3] == 2) && c.stride != 1);            // parity-phase launches: register-staged kernel
-    ok = ok && q[24] >= 0 && q[24] <= 5 && q[25] >= 0 && q[25] <= 5;
+    ok = ok && tbn_wgrad_tile_ok(q[24], q[25]);   // (tbn_wgrad_plan would swap any other value for a tile of its own)
     TBN_REQUIRE(ok, "plan_import: invalid launch choice for GEMM %zu (%s)", i, c.parts[c.nparts - 1].name.c_str());
   }
   for (size_t i = 0; i < P->convs.size(); ++i) {

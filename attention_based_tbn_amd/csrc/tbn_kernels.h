@@ -287,6 +287,17 @@ size_t tbn_bf16x_planes_bytes(size_t floats, int np);
 int tbn_launch_bf16x_split(const float* w, void* planes, const SplitTab& tab, int np, hipStream_t st);
 void tbn_wgrad_plan(int M, int Cout, int Cin, int taps, int* mt, int* nt, int* splits, int* rows_per_split);
 size_t tbn_wgrad_workspace_floats(int M, int Cout, int Cin, int taps);
+bool tbn_wgrad_tile_ok(int mt, int nt);   // 0 x 0 (the heuristic) or a tile the kernel is instantiated for
+// what tbn_launch_wgrad runs for a problem (p: geometry and the requested tile p.mt x p.nt; host only, no device call)
+struct WgradLaunchPlan {
+  int mt, nt;             // the tile run
+  int mode;               // kernel MODE: 0 general, 1 packed-row stem, 2 pointwise
+  int splits, rows_per_split;
+  int tiles_co, tiles_ci;
+  int reduce;             // slab lanes of splitk_reduce_kernel: 0 (no split-K), 4 or 16
+  size_t ws_floats;       // split-K slabs this tile needs
+};
+WgradLaunchPlan tbn_wgrad_launch_plan(const WgradP& p, int rowmode);
 int tbn_launch_wgrad(WgradP p, int rowmode, float* dw, float* workspace, hipStream_t st);
 int tbn_launch_weight_flip_transpose(const float* w, float* wt, int Cout, int taps, int Cin, hipStream_t st);
 // layer table of the one-launch flip/transpose of every data-gradient weight of a backbone (kernel argument)

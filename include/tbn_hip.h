@@ -375,6 +375,18 @@ int tbn_conv_launch_pair(const tbn_conv_desc* a, const tbn_conv_desc* b, int var
 size_t tbn_conv2d_wgrad_workspace_floats(int n, int h, int w, int cin, int cout, int ksize, int stride, int pad);
 int tbn_conv2d_wgrad(const float* dout, int dout_ld, const float* in, int in_ld, float* dweight, int n, int h, int w,
                      int cin, int cout, int ksize, int stride, int pad, float* workspace, void* stream);
+/* tuning / test aid: as tbn_conv2d_wgrad with an explicit tile: a workgroup computes (32*mt) x (32*nt) entries of one filter
+ * tap, mt in {1,2,3,5}, nt in {1,2,3} without 5 x 3; (0,0) = the built-in heuristic.  Any other tile is refused, as are null
+ * pointers, channel counts / pitches that are no multiples of 4 and pitches below the channel count -- before any launch.
+ * workspace: tbn_conv2d_wgrad_workspace_floats() covers every tile. */
+int tbn_conv2d_wgrad_tile(const float* dout, int dout_ld, const float* in, int in_ld, float* dweight, int n, int h, int w,
+                          int cin, int cout, int ksize, int stride, int pad, int mt, int nt, float* workspace, void* stream);
+/* host only (no launch, no device call): what tbn_conv2d_wgrad_tile would run for this problem and tile.
+ * out8 = {mt, nt (the tile run), kernel mode (0 general, 2 pointwise = 1x1 / stride 1 / pad 0), splits, rows_per_split,
+ * tiles_co, tiles_ci, slab lanes of the split-K reduce (0 = no split-K, 4, 16)}: the launch is
+ * conv_wgrad_kernel<mt, nt, mode> on tiles_co * tiles_ci * ksize^2 * splits workgroups, then splitk_reduce_kernel<4 | 16> when
+ * splits > 1.  Returns the split-K workspace floats that tile needs (>= 0), or a negative status. */
+long long tbn_conv2d_wgrad_plan(int n, int h, int w, int cin, int cout, int ksize, int stride, int pad, int mt, int nt, int* out8);
 
 /* ---- the 7x7 / stride 2 / pad 3 stem on its own (test / tuning aid) -----------------------------
  * conv1_7x7_s2 exactly as the backbone engine executes it -- the same launch sequence, built from the same statement of the

@@ -787,6 +787,18 @@ def test_c_abi_rejects_bad_arguments_before_touching_the_gpu():
     fails(stem_wgrad(mt=4, nt=1), "tile 4x1")
     fails(stem_wgrad(mt=5, nt=3), "tile 5x3")
     fails(stem_wgrad(mt=0, nt=2), "tile 0x2")
+    # the conv weight gradient with an explicit tile, and its host-only plan query: the same tile rule, pitches, multiples of 4
+    # (every refusal of the two: tests/test_wgrad_plan_cpu.py)
+    def conv_wgrad(dy=bad, dy_ld=64, x=bad, x_ld=32, dw=bad, mt=0, nt=0):
+        return L.tbn_conv2d_wgrad_tile(dy, dy_ld, x, x_ld, dw, 2, 8, 8, 32, 64, 3, 1, 1, mt, nt, None, None)
+    for kw in (dict(dy=None), dict(x=None), dict(dw=None)):
+        fails(conv_wgrad(**kw), "conv2d_wgrad_tile: null pointer")
+    for mt, nt in ((4, 1), (5, 3), (0, 2), (2, 0), (1, 4)):
+        fails(conv_wgrad(mt=mt, nt=nt), "conv2d_wgrad_tile: tile %dx%d (mt 1 | 2 | 3 | 5, nt 1..3 without 5x3, or 0x0)" % (mt, nt))
+        fails(L.tbn_conv2d_wgrad_plan(2, 8, 8, 32, 64, 3, 1, 1, mt, nt, geo), "conv2d_wgrad_plan: tile %dx%d" % (mt, nt))
+    fails(conv_wgrad(dy_ld=60), "dout_ld 60")
+    fails(conv_wgrad(x_ld=28), "in_ld 28")
+    fails(conv_wgrad(x_ld=34), "in_ld 34")
     # batched training BN: the launchers' shape rules (bn_multi.hip) and null pointers, before any launch
     from attention_based_tbn_amd._lib import BnBwdDesc, BnFwdDesc, BnSeg
 
@@ -1040,8 +1052,12 @@ def test_plan_export_import_round_trip_and_fingerprint():
     bad[0] = 7
     bb = struct.pack("%di" % len(bad), *bad)
     assert L.tbn_backbone_plan_import(a, bb, len(bb)) < 0 and b"not a plan blob" in L.tbn_last_error()
-    for off, val in ((8, 3), (9, 5), (11, 4), (16, 0), (24, 9)):       # tile / variant / wgrad tile out of range
+    # tile / variant / wgrad tile out of range; wgrad tiles the planner would swap for another (mt 4, nt 4 | 5, one of the two 0)
+    for off, val in ((8, 3), (9, 5), (11, 4), (16, 0), (24, 9), (24, 4), (25, 4), (25, 5), (24, 0), (25, 0), (24, -1), (24, 6),
+                     (24, 5)):
         bad = list(tuned)
+        if (off, val) == (24, 5):                                       # 5 x 3 (5 x 2, mt 5 beside the tuned nt 2, is a tile)
+            bad[base + 25] = 3
         bad[base + off] = val
         bb = struct.pack("%di" % len(bad), *bad)
         assert L.tbn_backbone_plan_import(a, bb, len(bb)) < 0 and b"invalid launch choice" in L.tbn_last_error(), (off, val)
