@@ -97,6 +97,12 @@ class InflateMember(C.Structure):
                 ("crc", C.c_uint32), ("method", C.c_uint32), ("skip", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class DeflateMember(C.Structure):
+    """include/tbn_hip.h tbn_deflate_member: one row of the member table of tbn_deflate_batch / tbn_deflate_host"""
+    _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("in_len", C.c_uint32), ("out_cap", C.c_uint32),
+                ("skip", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class MetricHead(C.Structure):
     """include/tbn_hip.h tbn_metric_head"""
     _fields_ = [("scores", c_fp), ("scores_ld", c_i), ("classes", c_i), ("target", c_fp), ("conf_mat", c_fp)]
@@ -252,6 +258,13 @@ SIGNATURES = {
     # reference core/dataset/dataset.py:342-343 (np.load of a flow pickle): inflate + CRC-32 of zip members, one wavefront each
     "tbn_inflate_batch": (c_i, [c_fp, c_sz, c_fp, c_i, c_fp, c_sz, c_fp, c_fp, c_fp]),
     "tbn_inflate_host": (c_i, [c_fp, c_sz, c_fp, c_i, c_fp, c_sz, c_fp, c_fp]),
+    # reference preprocessing/create_epic_flow_pickle.py:203 (np.savez_compressed): raw deflate streams + CRC-32, one
+    # wavefront per 32-KB chunk
+    "tbn_deflate_chunk": (c_sz, []),
+    "tbn_deflate_bound": (c_sz, [c_sz]),
+    "tbn_deflate_workspace_bytes": (c_sz, [c_fp, c_i]),
+    "tbn_deflate_batch": (c_i, [c_fp, c_sz, c_fp, c_i, c_fp, c_sz, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "tbn_deflate_host": (c_i, [c_fp, c_sz, c_fp, c_i, c_fp, c_sz, c_fp, c_fp, c_fp]),
 }
 
 _lib = None

@@ -7,10 +7,16 @@ device does what is large: `load_npz_arrays` packs the members' compressed bytes
 copies it once, and `tbn_inflate_batch` (csrc/inflate.hip) inflates every member and checks its CRC-32 in one call.  One
 small copy back of the status vector is the only synchronisation.  A member the record or the status sends to the host
 (anything np.load reads that this path does not: another dtype, Fortran order, a damaged stream, ...) is read by the
-host code into its slot, so a batch may mix both and error wording stays the host path's; those members are counted."""
+host code into its slot, so a batch may mix both and error wording stays the host path's; those members are counted.
+
+Writing is the mirror image (`save_npz_arrays`, `write_npz_files`; the np.savez_compressed call of
+preprocessing/create_epic_flow_pickle.py:203): the device lays out header and array per member, `tbn_deflate_batch`
+(csrc/deflate.hip) compresses all of them and computes their CRC-32 in one call, and the host writes the zip container
+around each stream (`npy_header`, `npz_container`)."""
 import ast
 import ctypes
 import io
+import os
 import struct
 import zipfile
 import zlib
@@ -197,3 +203,113 @@ def load_npz_arrays(blobs, name="flow", device="cuda", *, records=None, planes=F
     if planes:
         arrays = arrays.permute(0, 3, 1, 2).contiguous().view(n * Cn, H, W, 1)
     return arrays, statuses
+
+
+# ---- writing: the other half of a flow pickle's life (reference preprocessing/create_epic_flow_pickle.py:203) ------------
+STATUS_DEFLATE_SKIPPED = 3     # include/tbn_hip.h, tbn_deflate_batch: the row carried the skip marker
+_ZIP_DATE, _ZIP_TIME = (0 << 9) | (1 << 5) | 1, 0       # 1980-01-01 00:00:00: the files depend on their content alone
+
+
+def npy_header(shape):
+    """The exact bytes np.save writes in front of a C-order uint8 array of `shape`: format version 1.0, the dict
+    padded with spaces (numpy's 21-digit room for a growing first axis, then up to a multiple of 64) and a newline."""
+    shape = tuple(int(v) for v in shape)
+    text = "{'descr': '|u1', 'fortran_order': False, 'shape': %s, }" % repr(shape)
+    if shape:
+        text += " " * (21 - len(repr(shape[0])))
+    used = 10 + len(text) + 1
+    pad = 64 - used % 64
+    body = text.encode("latin1") + b" " * pad + b"\n"
+    if len(body) >= 1 << 16:
+        raise ValueError(f"npy_header: shape {shape} does not fit a version 1.0 header")
+    return b"\x93NUMPY\x01\x00" + struct.pack("<H", len(body)) + body
+
+
+def npz_container(name, stream, crc, size):
+    """One complete .npz file (bytes) around ONE member `name`.npy whose raw deflate stream, CRC-32 and inflated size
+    are given: local header, the stream, central directory, end record; method 8, a fixed timestamp, no zip64."""
+    fname = (name + ".npy").encode("ascii")
+    if size >= 1 << 31 or len(stream) >= 1 << 31:
+        raise ValueError("npz_container: a member of 2 GiB or more needs zip64, which this writer does not do")
+    fields = (20, 0, 8, _ZIP_TIME, _ZIP_DATE, crc & 0xFFFFFFFF, len(stream), size, len(fname), 0)
+    local = struct.pack("<4sHHHHHIIIHH", b"PK\x03\x04", *fields) + fname
+    central = struct.pack("<4sHHHHHHIIIHHHHHII", b"PK\x01\x02", 20, *fields, 0, 0, 0, 0, 0) + fname
+    end = struct.pack("<4sHHHHIIH", b"PK\x05\x06", 0, 0, 1, 1, len(central), len(local) + len(stream), 0)
+    return b"".join((local, bytes(stream), central, end))
+
+
+def save_npz_arrays(arrays, name="flow", *, deflate="device"):
+    """`arrays`: uint8 (n, H, W, C) on the device -> n `bytes`, each a complete .npz file with the one member `name`
+    (what np.savez_compressed(file, **{name: array}) holds; np.load and `load_npz_arrays` read it).
+
+    deflate="device"  the .npy header and the array are laid out per slot on the device, ONE `tbn_deflate_batch` call on
+                      the current stream compresses every member and computes its CRC-32 (csrc/deflate.hip), one small
+                      copy brings lengths, CRCs and statuses back, one copy the streams, packed.  The host only writes
+                      the zip container around each stream.
+    deflate="host"    zlib level 6 on the host, in the same container: the A/B and fallback path."""
+    if deflate not in ("device", "host"):
+        raise ValueError(f"save_npz_arrays: deflate={deflate!r}, expected 'device' or 'host'")
+    if not isinstance(arrays, torch.Tensor) or arrays.dtype != torch.uint8 or arrays.dim() != 4:
+        raise TbnHipError("save_npz_arrays: expected a uint8 tensor (n, H, W, C)")
+    n, H, W, Cn = arrays.shape
+    if n == 0:
+        return []
+    header = npy_header((H, W, Cn))
+    size = len(header) + H * W * Cn
+    if size >= 1 << 31:
+        raise ValueError(f"save_npz_arrays: a member of {size} bytes: 2 GiB or more is refused (no zip64)")
+    if deflate == "host":
+        out = []
+        for a in arrays.contiguous().cpu().numpy():
+            raw = header + a.tobytes()
+            c = zlib.compressobj(6, zlib.DEFLATED, -15)
+            out.append(npz_container(name, c.compress(raw) + c.flush(), zlib.crc32(raw), size))
+        return out
+    if arrays.device.type != "cuda":
+        raise TbnHipError(f"save_npz_arrays: device {arrays.device} is not a GPU (deflate='host' is the host path)")
+    from ..._lib import DeflateMember, lib
+    L = lib()
+    device = arrays.device
+    stride = -(-size // _ALIGN) * _ALIGN
+    cap = -(-int(L.tbn_deflate_bound(size)) // _ALIGN) * _ALIGN
+    table = (DeflateMember * n)()
+    for i in range(n):
+        row = table[i]
+        row.in_off, row.in_len, row.out_off, row.out_cap = i * stride, size, i * cap, cap
+    workspace_bytes = int(L.tbn_deflate_workspace_bytes(ctypes.addressof(table), n))
+    small = torch.empty(len(header) + ctypes.sizeof(table), dtype=torch.uint8, pin_memory=True)   # header + table: one copy
+    flat = small.numpy()
+    flat[:len(header)] = np.frombuffer(header, np.uint8)
+    flat[len(header):] = np.frombuffer(table, np.uint8)
+    small_dev = small.to(device, non_blocking=True)
+    raw = torch.empty((n, stride), dtype=torch.uint8, device=device)
+    raw[:, :len(header)] = small_dev[:len(header)]
+    raw[:, len(header):size] = arrays.reshape(n, -1)
+    table_dev = small_dev[len(header):].clone()               # its own allocation: 8-byte aligned
+    out = torch.empty((n, cap), dtype=torch.uint8, device=device)
+    meta = torch.empty(3 * n, dtype=torch.int32, device=device)            # out_len[n], crc[n], status[n]
+    workspace = torch.empty(workspace_bytes, dtype=torch.uint8, device=device)
+    call("tbn_deflate_batch", ptr(raw), n * stride, ptr(table_dev), n, ptr(out), n * cap, ptr(meta), ptr(meta) + 4 * n,
+         ptr(meta) + 8 * n, ptr(workspace), stream_ptr())
+    host = meta.cpu().numpy()                                               # the first synchronisation
+    lengths, crcs, statuses = host[:n].view(np.uint32), host[n:2 * n].view(np.uint32), host[2 * n:]
+    if statuses.any():
+        raise TbnHipError(f"save_npz_arrays: tbn_deflate_batch statuses {statuses.tolist()}")
+    packed = torch.cat([out[i, :int(lengths[i])] for i in range(n)]).cpu().numpy()      # the streams: one copy
+    ends = np.cumsum(lengths.astype(np.int64))
+    return [npz_container(name, packed[int(e) - int(l):int(e)].tobytes(), int(c), size) for e, l, c in zip(ends, lengths, crcs)]
+
+
+def write_npz_files(paths, arrays, name="flow", *, deflate="device"):
+    """`save_npz_arrays`, then file i goes to paths[i]: written under a temporary name beside it and renamed, so a
+    reader (or an interrupted run) never sees half a file.  -> bytes written per file."""
+    if len(paths) != arrays.shape[0]:
+        raise ValueError(f"write_npz_files: {len(paths)} paths for {arrays.shape[0]} arrays")
+    sizes = []
+    for path, blob in zip(paths, save_npz_arrays(arrays, name, deflate=deflate)):
+        tmp = f"{path}.tmp{os.getpid()}"
+        with open(tmp, "wb") as f:
+            f.write(blob)
+        os.replace(tmp, path)
+        sizes.append(len(blob))
+    return sizes

@@ -17,8 +17,10 @@
 // global staging buffer is only ever written here, in stream order.  76 KB of LDS: two members per CU.
 //
 // crc_kernel, 256 threads per member: the 256-entry table in LDS, one chunk of equal length per thread, each chunk's CRC
-// multiplied by x^(8 * bytes behind it) mod P and XOR-reduced; a mismatch turns status 0 into TBN_INF_CRC.
+// multiplied by x^(8 * bytes behind it) mod P and XOR-reduced; a mismatch turns status 0 into TBN_INF_CRC.  The body is
+// crc_workgroup (csrc/tbn_crc_dev.h), which deflate_crc_kernel of csrc/deflate.hip calls too.
 #include "tbn_common.h"
+#include "tbn_crc_dev.h"
 #include "tbn_inflate.h"
 #include "../../include/tbn_hip.h"
 
@@ -162,30 +164,16 @@ __global__ __launch_bounds__(kInfThreads) void inflate_kernel(const uint8_t* __r
   }
 }
 
-constexpr int kCrcThreads = (int)kCrcChunks;
-
 __global__ __launch_bounds__(kCrcThreads) void inflate_crc_kernel(const tbn_inflate_member* __restrict__ members,
                                                                   const uint8_t* __restrict__ out, int* __restrict__ status) {
   __shared__ uint32_t table[256];
   __shared__ uint32_t part[kCrcThreads];
-  const int m_no = blockIdx.x, t = threadIdx.x;
+  const int m_no = blockIdx.x;
   const tbn_inflate_member m = members[m_no];
   const bool run = status[m_no] == TBN_INF_OK;       // one value for the workgroup: the inflate launch has completed
-  table[t] = crc_table_entry((uint32_t)t);
-  __syncthreads();
-  uint32_t c = 0;
-  if (run) {                                         // status 0: the row was checked and out_len bytes were written
-    const uint32_t n = m.out_len, chunk = crc_chunk_len(n);
-    const uint64_t b = (uint64_t)t * chunk, e = b + chunk;
-    c = crc_chunk(out + m.out_off, (uint32_t)(b < n ? b : n), (uint32_t)(e < n ? e : n), n, table);
-  }
-  part[t] = c;
-  __syncthreads();
-  for (int s = kCrcThreads / 2; s > 0; s >>= 1) {
-    if (t < s) part[t] ^= part[t + s];
-    __syncthreads();
-  }
-  if (t == 0 && run && part[0] != m.crc) status[m_no] = TBN_INF_CRC;
+  // status 0: the row was checked and out_len bytes were written
+  const uint32_t crc = crc_workgroup(out + m.out_off, m.out_len, run, table, part);     // csrc/tbn_crc_dev.h
+  if (threadIdx.x == 0 && run && crc != m.crc) status[m_no] = TBN_INF_CRC;
 }
 
 int check_args(const char* fn, const void* in, size_t in_bytes, const tbn_inflate_member* members, int n, const void* out,

@@ -1040,6 +1040,51 @@ int tbn_inflate_batch(const void* in_dev, size_t in_bytes, const tbn_inflate_mem
 int tbn_inflate_host(const void* in, size_t in_bytes, const tbn_inflate_member* members, int n_members, void* out,
                      size_t out_bytes, int* status, int* info);
 
+/* ---- flow pickles: raw deflate streams (RFC 1951) and the zip CRC-32 written on the device (opt-in) -------- */
+/* Replaces the zlib run inside np.savez_compressed of reference preprocessing/create_epic_flow_pickle.py:203.  The zip
+ * container and the .npy header stay host work (core/dataset/npz_file.py).  The encoder core and the stream format are
+ * csrc/tbn_deflate.h: a member is cut into chunks of tbn_deflate_chunk() bytes that are compressed independently (LZ77
+ * inside the chunk, stored / fixed / dynamic blocks by exact bit cost) and joined on byte boundaries; any inflate reads
+ * the result.  The device and the host twin write the same bytes.  There is no capability bit: callers detect the
+ * feature by the symbol.
+ * One row of the member table (32 bytes):
+ *   in_off, in_len   the member's raw bytes inside `raw`; in_off is a multiple of 4, in_len below 2^31
+ *   out_off, out_cap where its stream goes inside `out` and how much room it has: at least tbn_deflate_bound(in_len).
+ *                    Rows must not overlap in `out` (not checked).
+ *   skip             non-zero: nothing is read or written for the row (status 3)
+ * Status per member: 0 ok; 1 out_cap is below tbn_deflate_bound(in_len); 2 the row is inconsistent (a range outside the
+ * buffers, in_len of 2^31 or more, in_off not a multiple of 4); 3 skipped.  With a non-zero status out_len and crc are 0
+ * and nothing at all is written to `out` for the row; with status 0 only [out_off, out_off + out_len) is. */
+typedef struct tbn_deflate_member {
+  uint64_t in_off, out_off;
+  uint32_t in_len, out_cap;
+  uint32_t skip;
+  uint32_t reserved;
+} tbn_deflate_member;
+/* HOST.  The chunk size of the stream format (reference preprocessing/create_epic_flow_pickle.py:203 has no such notion:
+ * zlib compresses the member whole). */
+size_t tbn_deflate_chunk(void);
+/* HOST, closed form: no stream for n raw bytes is longer than n + 5 * max(1, ceil(n / tbn_deflate_chunk())).  The room
+ * np.savez_compressed of reference preprocessing/create_epic_flow_pickle.py:203 leaves zlib to find. */
+size_t tbn_deflate_bound(size_t n);
+/* HOST, from a host copy of the table tbn_deflate_batch will get: bytes of its `workspace` (one slot per chunk).  Part of
+ * replacing reference preprocessing/create_epic_flow_pickle.py:203. */
+size_t tbn_deflate_workspace_bytes(const tbn_deflate_member* members, int n_members);
+/* DEVICE.  Replaces the compression of reference preprocessing/create_epic_flow_pickle.py:203.  Three launches on
+ * `stream`: one wavefront per chunk compresses it into its workspace slot; one workgroup per member joins the slots
+ * into the member's stream and writes out_len and the status; one workgroup per member computes the CRC-32 of the raw
+ * bytes.  raw_dev[0, raw_bytes): 4-byte aligned; members_dev[n_members]: device memory, 8-byte aligned;
+ * out_dev[0, out_bytes); out_len_dev / crc_dev / status_dev: n_members 32-bit values each; workspace: device memory of
+ * tbn_deflate_workspace_bytes(), 16-byte aligned.  n_members == 0 launches nothing. */
+int tbn_deflate_batch(const void* raw_dev, size_t raw_bytes, const tbn_deflate_member* members_dev, int n_members,
+                      void* out_dev, size_t out_bytes, uint32_t* out_len_dev, uint32_t* crc_dev, int* status_dev,
+                      void* workspace, void* stream);
+/* HOST, thread-safe, no GPU call: the same encoder core and the same chunked CRC run serially over the same table, all
+ * pointers host memory, the same bytes out.  The test aid of tbn_deflate_batch and the host side of replacing reference
+ * preprocessing/create_epic_flow_pickle.py:203. */
+int tbn_deflate_host(const void* raw, size_t raw_bytes, const tbn_deflate_member* members, int n_members, void* out,
+                     size_t out_bytes, uint32_t* out_len, uint32_t* crc, int* status);
+
 #ifdef __cplusplus
 }
 #endif
