@@ -97,6 +97,12 @@ class InflateMember(C.Structure):
                 ("crc", C.c_uint32), ("method", C.c_uint32), ("skip", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class InflateChunk(C.Structure):
+    """include/tbn_hip.h tbn_inflate_chunk: one row of the chunk table of tbn_inflate_chunks / tbn_inflate_chunks_host"""
+    _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("in_len", C.c_uint32), ("out_len", C.c_uint32),
+                ("member", C.c_uint32), ("last", C.c_uint32)]
+
+
 class DeflateMember(C.Structure):
     """include/tbn_hip.h tbn_deflate_member: one row of the member table of tbn_deflate_batch / tbn_deflate_host"""
     _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("in_len", C.c_uint32), ("out_cap", C.c_uint32),
@@ -258,6 +264,9 @@ SIGNATURES = {
     # reference core/dataset/dataset.py:342-343 (np.load of a flow pickle): inflate + CRC-32 of zip members, one wavefront each
     "tbn_inflate_batch": (c_i, [c_fp, c_sz, c_fp, c_i, c_fp, c_sz, c_fp, c_fp, c_fp]),
     "tbn_inflate_host": (c_i, [c_fp, c_sz, c_fp, c_i, c_fp, c_sz, c_fp, c_fp]),
+    # the same members when the file carries a chunk index: one wavefront per 32-KB chunk
+    "tbn_inflate_chunks": (c_i, [c_fp, c_sz, c_fp, c_i, c_fp, c_fp, c_i, c_fp, c_sz, c_fp, c_fp, c_fp, c_fp]),
+    "tbn_inflate_chunks_host": (c_i, [c_fp, c_sz, c_fp, c_i, c_fp, c_fp, c_i, c_fp, c_sz, c_fp, c_fp, c_fp]),
     # reference preprocessing/create_epic_flow_pickle.py:203 (np.savez_compressed): raw deflate streams + CRC-32, one
     # wavefront per 32-KB chunk
     "tbn_deflate_chunk": (c_sz, []),
@@ -265,6 +274,8 @@ SIGNATURES = {
     "tbn_deflate_workspace_bytes": (c_sz, [c_fp, c_i]),
     "tbn_deflate_batch": (c_i, [c_fp, c_sz, c_fp, c_i, c_fp, c_sz, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "tbn_deflate_host": (c_i, [c_fp, c_sz, c_fp, c_i, c_fp, c_sz, c_fp, c_fp, c_fp]),
+    "tbn_deflate_batch_indexed": (c_i, [c_fp, c_sz, c_fp, c_i, c_fp, c_sz, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "tbn_deflate_host_indexed": (c_i, [c_fp, c_sz, c_fp, c_i, c_fp, c_sz, c_fp, c_fp, c_fp, c_fp]),
 }
 
 _lib = None

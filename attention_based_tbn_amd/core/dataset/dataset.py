@@ -126,7 +126,8 @@ class Video_Dataset(object):
     any PCM width or float32, downmixes and resamples on the device like the reference's librosa.load (.wav files only;
     audio pickles are read as before).  `flow_load` matters only with data.flow.read_flow_pickle: "host" (the default)
     reads each frame_XXXXXXXXXX.npz with np.load inside `plan`; "device" keeps the files' bytes and inflates every pickle
-    of a batch with one `npz_file.load_npz_arrays` call (`flow_fallbacks` counts the members that still took np.load).
+    of a batch with one `npz_file.load_npz_arrays` call (`flow_fallbacks` counts the members that still took np.load);
+    pickles written with a chunk index (`write_npz_files(chunk_index=True)`) are inflated one wavefront per chunk there.
     `transform` is the dictionary `get_transforms` returns: RGB / Flow need a
     `DevicePipeline`; the Audio entry is not called, the spectrograms are born on the device as the fp32 tensor it would
     return.

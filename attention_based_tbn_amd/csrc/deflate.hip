@@ -13,7 +13,9 @@
 // inflate_kernel.  No wavefront waits for another one: the slot of chunk c is at c * kSlot, whatever the others produce.
 //
 // deflate_join_kernel, 256 threads per member: walks the member's slots in order, adds up their sizes and copies each
-// slot's bytes behind the previous one (the chunks end on byte boundaries); writes out_len and the status.
+// slot's bytes behind the previous one (the chunks end on byte boundaries); writes out_len and the status -- and, for
+// tbn_deflate_batch_indexed, the chunk index: the stream offset at which each chunk ends, one entry per chunk of every
+// row in table order (zeros for a row that is skipped or refused).
 //
 // deflate_crc_kernel, 256 threads per member: crc_workgroup of csrc/tbn_crc_dev.h (shared with inflate_crc_kernel) over
 // the member's raw bytes.
@@ -125,25 +127,34 @@ __global__ __launch_bounds__(kDefThreads) void deflate_chunk_kernel(const uint8_
 __global__ __launch_bounds__(kJoinThreads) void deflate_join_kernel(const tbn_deflate_member* __restrict__ members, size_t raw_bytes,
                                                                     const uint8_t* __restrict__ workspace, uint8_t* __restrict__ out,
                                                                     size_t out_bytes, uint32_t* __restrict__ out_len,
-                                                                    int* __restrict__ status) {
-  __shared__ unsigned long long part[kJoinThreads];
+                                                                    int* __restrict__ status, uint32_t* __restrict__ chunk_end) {
+  __shared__ unsigned long long part[kJoinThreads], part_all[kJoinThreads];
   const int m_no = blockIdx.x, t = threadIdx.x;
   const tbn_deflate_member m = members[m_no];
   int st = row_status(m, raw_bytes, out_bytes);           // one value for the workgroup
-  // the member's first slot: the chunks of the rows in front of it
-  unsigned long long mine = 0;
-  for (int i = t; i < m_no; i += kJoinThreads) mine += row_chunks(members[i], raw_bytes, out_bytes);
+  // the member's first slot: the chunks of the rows in front of it that are compressed; its first index entry: the
+  // chunks of ALL rows in front of it
+  unsigned long long mine = 0, mine_all = 0;
+  for (int i = t; i < m_no; i += kJoinThreads) {
+    mine += row_chunks(members[i], raw_bytes, out_bytes);
+    mine_all += chunks_of(members[i].in_len);
+  }
   part[t] = mine;
+  part_all[t] = mine_all;
   __syncthreads();
   for (int k = kJoinThreads / 2; k > 0; k >>= 1) {
-    if (t < k) part[t] += part[t + k];
+    if (t < k) part[t] += part[t + k], part_all[t] += part_all[t + k];
     __syncthreads();
   }
   const uint64_t first = part[0];
+  const uint32_t chunks = (uint32_t)chunks_of(m.in_len);
+  uint32_t* ends = chunk_end ? chunk_end + part_all[0] : nullptr;
+  if (ends)
+    for (uint32_t k = (uint32_t)t; k < chunks; k += kJoinThreads) ends[k] = 0;
+  __syncthreads();                                        // the zeros are in place before thread 0 writes an end
   uint64_t at = 0;
   if (st == TBN_DEF_OK) {
     uint8_t* dst = out + m.out_off;
-    const uint32_t chunks = (uint32_t)chunks_of(m.in_len);
     for (uint32_t k = 0; k < chunks; ++k) {
       const uint8_t* slot = workspace + (first + k) * kSlot;
       const uint32_t size = *(const uint32_t*)slot;
@@ -153,6 +164,11 @@ __global__ __launch_bounds__(kJoinThreads) void deflate_join_kernel(const tbn_de
       }
       for (uint32_t i = (uint32_t)t; i < size; i += kJoinThreads) dst[at + i] = slot[kSlotHeader + i];
       at += size;
+      if (ends && t == 0) ends[k] = (uint32_t)at;
+    }
+    if (ends && st != TBN_DEF_OK) {                       // never (see above): a refused row's entries are 0
+      __syncthreads();
+      for (uint32_t k = (uint32_t)t; k < chunks; k += kJoinThreads) ends[k] = 0;
     }
   }
   if (t == 0) {
@@ -200,10 +216,11 @@ extern "C" size_t tbn_deflate_workspace_bytes(const tbn_deflate_member* members,
   return (slots ? slots : 1) * (size_t)kSlot;
 }
 
-extern "C" int tbn_deflate_batch(const void* raw_dev, size_t raw_bytes, const tbn_deflate_member* members_dev, int n_members,
-                                 void* out_dev, size_t out_bytes, uint32_t* out_len_dev, uint32_t* crc_dev, int* status_dev,
-                                 void* workspace, void* stream) {
-  const char* fn = "deflate_batch";
+namespace {
+
+int deflate_batch(const char* fn, const void* raw_dev, size_t raw_bytes, const tbn_deflate_member* members_dev, int n_members,
+                  void* out_dev, size_t out_bytes, uint32_t* out_len_dev, uint32_t* crc_dev, int* status_dev, void* workspace,
+                  void* stream, uint32_t* chunk_end_dev) {
   const int rc = check_args(fn, raw_dev, members_dev, n_members, out_dev, out_len_dev, crc_dev, status_dev);
   if (rc != TBN_OK || n_members == 0) return rc;
   TBN_REQUIRE(workspace != nullptr && ((uintptr_t)workspace & 15) == 0, "%s: the workspace must be 16-byte aligned", fn);
@@ -215,7 +232,7 @@ extern "C" int tbn_deflate_batch(const void* raw_dev, size_t raw_bytes, const tb
               out_bytes, (uint8_t*)workspace);
   TBN_CHECK_LAUNCH(fn);
   TBN_KLAUNCH(deflate_join_kernel, dim3((unsigned)n_members), dim3(kJoinThreads), 0, st, members_dev, raw_bytes,
-              (const uint8_t*)workspace, (uint8_t*)out_dev, out_bytes, out_len_dev, status_dev);
+              (const uint8_t*)workspace, (uint8_t*)out_dev, out_bytes, out_len_dev, status_dev, chunk_end_dev);
   TBN_CHECK_LAUNCH(fn);
   TBN_KLAUNCH(deflate_crc_kernel, dim3((unsigned)n_members), dim3(tbn_inflate::kCrcThreads), 0, st, (const uint8_t*)raw_dev,
               members_dev, (const int*)status_dev, crc_dev);
@@ -223,10 +240,8 @@ extern "C" int tbn_deflate_batch(const void* raw_dev, size_t raw_bytes, const tb
   return TBN_OK;
 }
 
-// the host twin: the same core, serially, over the same member table; no GPU call
-extern "C" int tbn_deflate_host(const void* raw, size_t raw_bytes, const tbn_deflate_member* members, int n_members, void* out,
-                                size_t out_bytes, uint32_t* out_len, uint32_t* crc, int* status) {
-  const char* fn = "deflate_host";
+int deflate_host(const char* fn, const void* raw, size_t raw_bytes, const tbn_deflate_member* members, int n_members, void* out,
+                 size_t out_bytes, uint32_t* out_len, uint32_t* crc, int* status, uint32_t* chunk_end) {
   const int rc = check_args(fn, raw, members, n_members, out, out_len, crc, status);
   if (rc != TBN_OK || n_members == 0) return rc;
   std::vector<State> state(1);          // 70 KB: not on the caller's stack
@@ -240,10 +255,16 @@ extern "C" int tbn_deflate_host(const void* raw, size_t raw_bytes, const tbn_def
     status[i] = st;
     out_len[i] = 0;
     crc[i] = 0;
-    if (st != TBN_DEF_OK) continue;
+    uint32_t* ends = chunk_end;                           // this row's entries: chunks_of(in_len) of them, refused or not
+    if (chunk_end) chunk_end += chunks_of(m.in_len);
+    if (st != TBN_DEF_OK) {
+      if (ends)
+        for (uint64_t k = 0; k < chunks_of(m.in_len); ++k) ends[k] = 0;
+      continue;
+    }
     const uint8_t* src = (const uint8_t*)raw + m.in_off;
     uint64_t produced = 0;
-    status[i] = deflate_member_host(src, m.in_len, (uint8_t*)out + m.out_off, m.out_cap, s, slot.data(), &produced);
+    status[i] = deflate_member_host(src, m.in_len, (uint8_t*)out + m.out_off, m.out_cap, s, slot.data(), &produced, ends);
     out_len[i] = (uint32_t)produced;
     // the CRC in kCrcChunks chunks, as the kernel computes it
     const uint32_t n = m.in_len, chunk = tbn_inflate::crc_chunk_len(n);
@@ -255,4 +276,39 @@ extern "C" int tbn_deflate_host(const void* raw, size_t raw_bytes, const tbn_def
     crc[i] = c;
   }
   return TBN_OK;
+}
+
+}  // namespace
+
+extern "C" int tbn_deflate_batch(const void* raw_dev, size_t raw_bytes, const tbn_deflate_member* members_dev, int n_members,
+                                 void* out_dev, size_t out_bytes, uint32_t* out_len_dev, uint32_t* crc_dev, int* status_dev,
+                                 void* workspace, void* stream) {
+  return deflate_batch("deflate_batch", raw_dev, raw_bytes, members_dev, n_members, out_dev, out_bytes, out_len_dev, crc_dev,
+                       status_dev, workspace, stream, nullptr);
+}
+
+// the same launches; the join launch also writes the chunk index
+extern "C" int tbn_deflate_batch_indexed(const void* raw_dev, size_t raw_bytes, const tbn_deflate_member* members_dev,
+                                         int n_members, void* out_dev, size_t out_bytes, uint32_t* out_len_dev, uint32_t* crc_dev,
+                                         int* status_dev, void* workspace, void* stream, uint32_t* chunk_end_dev) {
+  const char* fn = "deflate_batch_indexed";
+  TBN_REQUIRE(n_members <= 0 || (chunk_end_dev != nullptr && ((uintptr_t)chunk_end_dev & 3) == 0),
+              "%s: chunk_end must be a 4-byte aligned array", fn);
+  return deflate_batch(fn, raw_dev, raw_bytes, members_dev, n_members, out_dev, out_bytes, out_len_dev, crc_dev, status_dev,
+                       workspace, stream, chunk_end_dev);
+}
+
+// the host twins: the same core, serially, over the same member table; no GPU call
+extern "C" int tbn_deflate_host(const void* raw, size_t raw_bytes, const tbn_deflate_member* members, int n_members, void* out,
+                                size_t out_bytes, uint32_t* out_len, uint32_t* crc, int* status) {
+  return deflate_host("deflate_host", raw, raw_bytes, members, n_members, out, out_bytes, out_len, crc, status, nullptr);
+}
+
+extern "C" int tbn_deflate_host_indexed(const void* raw, size_t raw_bytes, const tbn_deflate_member* members, int n_members,
+                                        void* out, size_t out_bytes, uint32_t* out_len, uint32_t* crc, int* status,
+                                        uint32_t* chunk_end) {
+  const char* fn = "deflate_host_indexed";
+  TBN_REQUIRE(n_members <= 0 || (chunk_end != nullptr && ((uintptr_t)chunk_end & 3) == 0),
+              "%s: chunk_end must be a 4-byte aligned array", fn);
+  return deflate_host(fn, raw, raw_bytes, members, n_members, out, out_bytes, out_len, crc, status, chunk_end);
 }

@@ -1,5 +1,5 @@
 // RFC 1951 (raw deflate) ENCODER core, shared by the kernels in csrc/deflate.hip, the host twin tbn_deflate_host and the
-// stand-alone memory check scripts/deflate_check.cpp.  Plain C++: no HIP, no global state; the core is marked TBN_DEF_HD,
+// stand-alone memory checks scripts/deflate_check.cpp and scripts/inflate_chunks_check.cpp.  Plain C++: no HIP, no global state; the core is marked TBN_DEF_HD,
 // which is `__host__ __device__` only under hipcc (the way tbn_inflate.h is shared).  Replaces the zlib level 6 run inside
 // np.savez_compressed of reference preprocessing/create_epic_flow_pickle.py:203.
 //
@@ -461,14 +461,19 @@ struct HostIO {
 };
 
 // One member on the host: n raw bytes at `raw` into the out_cap bytes at `out`.  `s` and `slot` (kSlotData bytes) are
-// scratch.  -> status; *out_len: the stream's length.  Nothing is written unless out_cap >= bound(n).
+// scratch.  -> status; *out_len: the stream's length.  Nothing is written unless out_cap >= bound(n).  `chunk_end`
+// (chunks_of(n) entries, or null): THE CHUNK INDEX, the offset inside the stream at which each chunk's bytes end -- what
+// lets a reader inflate the chunks of a member side by side (csrc/inflate.hip, tbn_inflate_chunks); zeros for a refused row.
 inline int deflate_member_host(const uint8_t* raw, uint32_t n, uint8_t* out, uint64_t out_cap, State& s, uint8_t* slot,
-                               uint64_t* out_len) {
+                               uint64_t* out_len, uint32_t* chunk_end = nullptr) {
   *out_len = 0;
+  if (chunk_end)
+    for (uint64_t k = 0; k < chunks_of(n); ++k) chunk_end[k] = 0;
   if (out_cap < bound(n)) return TBN_DEF_CAPACITY;
   if (n == 0) {
     out[0] = 0x03, out[1] = 0x00;      // BFINAL, fixed, end of block
     *out_len = 2;
+    if (chunk_end) chunk_end[0] = 2;
     return TBN_DEF_OK;
   }
   uint64_t at = 0;
@@ -487,6 +492,7 @@ inline int deflate_member_host(const uint8_t* raw, uint32_t n, uint8_t* out, uin
       memcpy(out + at, slot, size);
       at += size;
     }
+    if (chunk_end) chunk_end[begin / kChunk] = (uint32_t)at;
   }
   *out_len = at;
   return TBN_DEF_OK;

@@ -1,5 +1,6 @@
-// RFC 1951 (raw deflate) decoder core and the zip CRC-32, shared by the kernel in csrc/inflate.hip, its host twin
-// tbn_inflate_host and the stand-alone memory check scripts/inflate_check.cpp.  Plain C++: no HIP, no global state; the
+// RFC 1951 (raw deflate) decoder core and the zip CRC-32, shared by the kernels in csrc/inflate.hip, their host twins
+// tbn_inflate_host / tbn_inflate_chunks_host and the stand-alone memory checks scripts/inflate_check.cpp and
+// scripts/inflate_chunks_check.cpp.  Plain C++: no HIP, no global state; the
 // core is marked TBN_INF_HD, which is `__host__ __device__` only under hipcc (the way tbn_jpeg_sync.h is shared).
 //
 // The core is a template over an IO policy that fetches input, stores literals and copies matches; everything that
@@ -43,7 +44,7 @@
                                    over-subscribed code, or an incomplete one where zlib refuses it */
 #define TBN_INF_SYMBOL 4        /* literal/length symbol 286 / 287, distance symbol 30 / 31, or a code no symbol has */
 #define TBN_INF_NO_EOB 5        /* a dynamic block without an end-of-block code */
-#define TBN_INF_DISTANCE 6      /* a distance before the start of the member's output */
+#define TBN_INF_DISTANCE 6      /* a distance before the start of the member's output (segment mode: of the chunk's) */
 #define TBN_INF_INPUT 7         /* input exhausted before the final block's end of block */
 #define TBN_INF_OUTPUT_FULL 8   /* output would pass the declared size */
 #define TBN_INF_OUTPUT_SHORT 9  /* output ends short of the declared size */
@@ -51,12 +52,17 @@
 #define TBN_INF_SKIPPED 11      /* the row carries the skip marker: nothing read, nothing written */
 #define TBN_INF_ROW 12          /* the row is inconsistent: a range outside the buffers, a misaligned offset, a method
                                    other than 0 / 8, a size of 2^31 or more */
+#define TBN_INF_SEGMENT 13      /* segment mode only: the segment does not end where the chunk index says (input left over,
+                                   BFINAL in a chunk that is not the member's last, no BFINAL in the last one) */
 
 namespace tbn_inflate {
 
 constexpr int kRootL = 10;          // literal/length codes of up to 10 bits decode with one lookup
 constexpr int kRootD = 8;           // distance codes of up to 8 bits
 constexpr int kMaxLens = 320;       // 286 + 30 lengths of a dynamic block; 288 + 32 of the fixed one
+// what inflate_stream is given: a whole stream, or one chunk's slice of a stream written by csrc/tbn_deflate.h (chunks
+// compressed independently and joined on byte boundaries) -- a chunk that is not the member's last, or the last one
+constexpr int kSegWhole = 0, kSegInner = 1, kSegLast = 2;
 
 // decode tables of the current block: 4.2 KB (LDS on the device, the stack on the host)
 struct Tables {
@@ -187,8 +193,18 @@ constexpr uint64_t kClOrderLo = pack_order(kClOrder, 0, 12), kClOrderHi = pack_o
 TBN_INF_HD int cl_order(int i) { return (int)(((i < 12 ? kClOrderLo >> (5 * i) : kClOrderHi >> (5 * (i - 12)))) & 31u); }
 
 // Inflates one raw deflate stream of `clen` bytes into exactly `declared` bytes.  -> status; *produced: bytes written.
+// SEGMENT MODE (`seg` != kSegWhole): the `clen` bytes are one chunk's slice and output byte 0 is the chunk's first byte, so
+// a distance reaching before the chunk is TBN_INF_DISTANCE like any distance before the output: a wrong index, or a
+// foreign stream carrying an index, costs a status.
+//   kSegInner  a run of non-final blocks.  Ends OK exactly when a block ends with ALL 8 * clen bits consumed (the writer
+//              ends the chunk on a byte boundary, with an empty stored block where its last block does not) and
+//              `declared` bytes produced; a block that sets BFINAL is TBN_INF_SEGMENT.
+//   kSegLast   ends at BFINAL as a whole stream does; then nothing but zero padding may follow in the last byte, and that
+//              byte is byte clen - 1, or the status is TBN_INF_SEGMENT.  So is a non-final block that ends with all
+//              input consumed.
+// Every other status and every bound is the whole stream's: the checks below do not depend on the mode.
 template <class IO>
-TBN_INF_HD int inflate_stream(IO& io, Tables& t, uint32_t clen, uint32_t declared, uint32_t* produced) {
+TBN_INF_HD int inflate_stream(IO& io, Tables& t, uint32_t clen, uint32_t declared, uint32_t* produced, int seg = kSegWhole) {
   BitReader br;
   uint32_t pos = 0;
   *produced = 0;
@@ -196,6 +212,7 @@ TBN_INF_HD int inflate_stream(IO& io, Tables& t, uint32_t clen, uint32_t declare
     br.refill(io);
     const uint32_t bfinal = br.get(1), type = br.get(2);
     if (br.past(clen)) return *produced = pos, TBN_INF_INPUT;
+    if (seg == kSegInner && bfinal) return *produced = pos, TBN_INF_SEGMENT;
     if (type == 3) return *produced = pos, TBN_INF_BLOCK_TYPE;
     if (type == 0) {
       br.drop(br.nbits & 7u);
@@ -320,8 +337,19 @@ TBN_INF_HD int inflate_stream(IO& io, Tables& t, uint32_t clen, uint32_t declare
       }
     }
     if (bfinal) break;
+    if (seg != kSegWhole && (uint64_t)br.in_pos * 8u - br.nbits == (uint64_t)clen * 8u) {     // a block ended at the slice's end
+      if (seg == kSegLast) return *produced = pos, TBN_INF_SEGMENT;
+      *produced = pos;
+      return pos == declared ? TBN_INF_OK : TBN_INF_OUTPUT_SHORT;
+    }
   }
   *produced = pos;
+  if (seg == kSegLast) {
+    // the final block ended inside byte clen - 1 (in_pos * 8 is a multiple of 8: nbits & 7 bits of that byte are left)
+    const uint64_t used = (uint64_t)br.in_pos * 8u - br.nbits;
+    const uint32_t pad = br.nbits & 7u;
+    if ((used + 7u) / 8u != clen || ((uint32_t)br.hold & ((1u << pad) - 1u)) != 0) return TBN_INF_SEGMENT;
+  }
   return pos == declared ? TBN_INF_OK : TBN_INF_OUTPUT_SHORT;
 }
 
@@ -387,6 +415,26 @@ struct HostIO {
   void copy_stored(uint32_t src, uint32_t pos, uint32_t len) { memcpy(out + pos, in + src, len); }
 };
 
+// the zip CRC-32 of out[0, n) in kCrcChunks chunks, as inflate_crc_kernel computes it
+inline uint32_t crc_member_host(const uint8_t* out, uint32_t n) {
+  uint32_t table[256];
+  for (uint32_t i = 0; i < 256; ++i) table[i] = crc_table_entry(i);
+  const uint32_t chunk = crc_chunk_len(n);
+  uint32_t c = 0;
+  for (uint32_t k = 0; k < kCrcChunks; ++k) {
+    const uint64_t b = (uint64_t)k * chunk, e = b + chunk;
+    c ^= crc_chunk(out, (uint32_t)(b < n ? b : n), (uint32_t)(e < n ? e : n), n, table);
+  }
+  return c;
+}
+
+// One chunk's slice on the host (segment mode): `clen` bytes at `in` into `declared` bytes at `out`.
+inline int inflate_chunk_host(const uint8_t* in, uint32_t clen, uint8_t* out, uint32_t declared, bool last, uint32_t* produced) {
+  Tables t;
+  HostIO io{in, clen, out};
+  return inflate_stream(io, t, clen, declared, produced, last ? kSegLast : kSegInner);
+}
+
 // One member on the host: method 0 (stored) or 8 (deflate), `clen` bytes at `in` into `declared` bytes at `out`, then the
 // CRC in kCrcChunks chunks as the kernel computes it.  -> status; *produced: bytes written.
 inline int inflate_member_host(const uint8_t* in, uint32_t clen, uint32_t method, uint8_t* out, uint32_t declared,
@@ -406,15 +454,7 @@ inline int inflate_member_host(const uint8_t* in, uint32_t clen, uint32_t method
     return TBN_INF_ROW;
   }
   if (st != TBN_INF_OK) return st;
-  uint32_t table[256];
-  for (uint32_t i = 0; i < 256; ++i) table[i] = crc_table_entry(i);
-  const uint32_t chunk = crc_chunk_len(declared);
-  uint32_t c = 0;
-  for (uint32_t k = 0; k < kCrcChunks; ++k) {
-    const uint64_t b = (uint64_t)k * chunk, e = b + chunk;
-    c ^= crc_chunk(out, (uint32_t)(b < declared ? b : declared), (uint32_t)(e < declared ? e : declared), declared, table);
-  }
-  return c == crc ? TBN_INF_OK : TBN_INF_CRC;
+  return crc_member_host(out, declared) == crc ? TBN_INF_OK : TBN_INF_CRC;
 }
 
 }  // namespace tbn_inflate

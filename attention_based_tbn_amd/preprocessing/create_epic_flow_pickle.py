@@ -1,5 +1,5 @@
 """`python -m attention_based_tbn_amd.preprocessing.create_epic_flow_pickle ANNOTATION_FILE ROOT_DIR [--out-dir DIR]
-[--file-format frame_{:010d}.jpg] [--win-len 5] [--njobs 4]`
+[--file-format frame_{:010d}.jpg] [--win-len 5] [--njobs 4] [--chunk-index]`
 
 The reference's `preprocessing/create_epic_flow_pickle.py` with its arguments, its file layout and its index rule: for
 every row of the annotation CSV (participant_id, video_id, start_frame, stop_frame) and every
@@ -12,7 +12,8 @@ What differs is where the work happens.  Per annotation row every needed JPEG is
 byte-identical to cv2.imread(path, 0); consecutive stacks share win_len - 1 pairs), the stacks are built on the device
 and written in batches through `write_npz_files` (core/dataset/npz_file.py), whose `--deflate device` path compresses on
 the device (csrc/deflate.hip) and whose `--deflate host` path is zlib level 6 in the same container, as
-np.savez_compressed.  An existing file is kept when it passes an integrity check -- the device inflates it and checks
+np.savez_compressed.  `--chunk-index` (device path only, off by default) records in every file where the 32-KB chunks of its
+stream end, so that `load_npz_arrays` inflates it one wavefront per chunk; np.load reads such a file as any other.  An existing file is kept when it passes an integrity check -- the device inflates it and checks
 its CRC-32 (`tbn_inflate_batch` status 0); np.load judges what the device path refuses -- and rewritten when it fails.
 A missing JPEG raises FileNotFoundError with its path (the reference asserts).  `--njobs` sizes the JPEG reader's host
 threads; there are no worker processes.
@@ -43,6 +44,8 @@ def parse_args(argv=None):
     parser.add_argument("--deflate", dest="deflate", choices=("device", "host"), default=DEFAULT_DEFLATE,
                         help="where the .npz members are compressed")
     parser.add_argument("--device", dest="device", type=str, default="cuda", help="device that decodes, stacks and checks")
+    parser.add_argument("--chunk-index", dest="chunk_index", action="store_true",
+                        help="record the chunk index in every file written (needs --deflate device)")
     return parser.parse_args(argv)
 
 
@@ -97,7 +100,7 @@ def _read(path):
         return f.read()
 
 
-def save_images_to_pickle(record, root_dir, out_dir, win_len, file_format, njobs, deflate, device):
+def save_images_to_pickle(record, root_dir, out_dir, win_len, file_format, njobs, deflate, device, chunk_index=False):
     """one annotation row -> (written paths, kept paths)"""
     import torch
 
@@ -137,7 +140,7 @@ def save_images_to_pickle(record, root_dir, out_dir, win_len, file_format, njobs
         stacks = pairs[rows]                                                                      # (n, win, H, W, 2)
         stacks = stacks.permute(0, 2, 3, 1, 4).reshape(len(part), pairs.shape[1], pairs.shape[2], 2 * win_len).contiguous()
         paths = [out_files[k] for k in part]
-        write_npz_files(paths, stacks, "flow", deflate=deflate)
+        write_npz_files(paths, stacks, "flow", deflate=deflate, chunk_index=chunk_index)
         written += paths
     return written, kept
 
@@ -153,7 +156,7 @@ def main(argv=None):
     written, kept = [], []
     for record in annotations:
         w, k = save_images_to_pickle(record, args.root_dir, args.out_dir, args.win_len, args.file_format, args.njobs,
-                                     args.deflate, args.device)
+                                     args.deflate, args.device, chunk_index=getattr(args, "chunk_index", False))
         written += w
         kept += k
     print("Done: {} files written, {} kept".format(len(written), len(kept)))

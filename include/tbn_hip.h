@@ -1039,6 +1039,39 @@ int tbn_inflate_batch(const void* in_dev, size_t in_bytes, const tbn_inflate_mem
  * pointers host memory.  The test aid of tbn_inflate_batch. */
 int tbn_inflate_host(const void* in, size_t in_bytes, const tbn_inflate_member* members, int n_members, void* out,
                      size_t out_bytes, int* status, int* info);
+/* Members that carry a CHUNK INDEX (written by tbn_deflate_batch_indexed below; core/dataset/npz_file.py keeps it in a zip
+ * extra field): the stream is chunks of tbn_deflate_chunk() raw bytes compressed independently and joined on byte
+ * boundaries, so every chunk inflates on its own -- parallelism inside a member that np.load of reference
+ * core/dataset/dataset.py:342-343 has no use for.  One row of the chunk table (32 bytes), rows in member order:
+ *   in_off, in_len   the chunk's compressed bytes inside `in`: ANY byte offset (only the member's in_off is aligned)
+ *   out_off, out_len inside `out`: the member's out_off + chunk_no * tbn_deflate_chunk(); out_len is tbn_deflate_chunk()
+ *                    but for the last chunk, which holds the rest (0 for an empty member)
+ *   member           its row of the member table (method 8)
+ *   last             non-zero: the member's last chunk
+ * chunk_begin[n_members + 1]: member i owns chunk rows [chunk_begin[i], chunk_begin[i + 1]): max(1, ceil(out_len / chunk))
+ * of them, tiling its compressed bytes and its output in order -- anything else is status 12 for the member.
+ * status / info per member: status is the first non-zero chunk status in chunk order (0..12 as above; 13: a segment does
+ * not end where the index says -- input left over, BFINAL in a chunk that is not the last, no BFINAL in the last one; a
+ * distance before the CHUNK's first byte is 6), then the CRC-32 check of the whole member as above: status 0 means the
+ * bytes are the member's whatever the index said.  info is the sum of the bytes the chunks produced.  11 for a member with
+ * `skip`: its chunks do nothing.  chunk_status[2 * n_chunks]: each chunk's status, then the bytes each produced.  The
+ * guarantees of tbn_inflate_batch hold per chunk: nothing outside its slice is read, nothing outside its out range written. */
+typedef struct tbn_inflate_chunk {
+  uint64_t in_off, out_off;
+  uint32_t in_len, out_len;
+  uint32_t member;
+  uint32_t last;
+} tbn_inflate_chunk;
+/* DEVICE.  Three launches on `stream`: one wavefront per chunk inflates it; one wavefront per member folds its chunks'
+ * statuses; one workgroup per member checks the CRC-32.  chunks_dev[n_chunks]: device memory, 8-byte aligned;
+ * chunk_begin_dev, chunk_status_dev: 4-byte aligned; the rest as for tbn_inflate_batch.  n_members == 0 launches nothing. */
+int tbn_inflate_chunks(const void* in_dev, size_t in_bytes, const tbn_inflate_member* members_dev, int n_members,
+                       const tbn_inflate_chunk* chunks_dev, const uint32_t* chunk_begin_dev, int n_chunks, void* out_dev,
+                       size_t out_bytes, int* status_dev, int* info_dev, int* chunk_status_dev, void* stream);
+/* HOST, thread-safe, no GPU call: the test aid of tbn_inflate_chunks, all pointers host memory. */
+int tbn_inflate_chunks_host(const void* in, size_t in_bytes, const tbn_inflate_member* members, int n_members,
+                            const tbn_inflate_chunk* chunks, const uint32_t* chunk_begin, int n_chunks, void* out,
+                            size_t out_bytes, int* status, int* info, int* chunk_status);
 
 /* ---- flow pickles: raw deflate streams (RFC 1951) and the zip CRC-32 written on the device (opt-in) -------- */
 /* Replaces the zlib run inside np.savez_compressed of reference preprocessing/create_epic_flow_pickle.py:203.  The zip
@@ -1084,6 +1117,16 @@ int tbn_deflate_batch(const void* raw_dev, size_t raw_bytes, const tbn_deflate_m
  * preprocessing/create_epic_flow_pickle.py:203. */
 int tbn_deflate_host(const void* raw, size_t raw_bytes, const tbn_deflate_member* members, int n_members, void* out,
                      size_t out_bytes, uint32_t* out_len, uint32_t* crc, int* status);
+/* DEVICE / HOST.  tbn_deflate_batch / tbn_deflate_host -- the same bytes, lengths, CRCs and statuses -- plus THE CHUNK
+ * INDEX (reference preprocessing/create_epic_flow_pickle.py:203 has no such notion): chunk_end holds, for every row in
+ * table order, max(1, ceil(in_len / tbn_deflate_chunk())) entries, the offset inside the row's stream at which each
+ * chunk's bytes end (the last equals out_len); the entries of a skipped or refused row are 0.  The join launch writes
+ * them.  chunk_end: 4-byte aligned, the sum of those counts over ALL rows long. */
+int tbn_deflate_batch_indexed(const void* raw_dev, size_t raw_bytes, const tbn_deflate_member* members_dev, int n_members,
+                              void* out_dev, size_t out_bytes, uint32_t* out_len_dev, uint32_t* crc_dev, int* status_dev,
+                              void* workspace, void* stream, uint32_t* chunk_end_dev);
+int tbn_deflate_host_indexed(const void* raw, size_t raw_bytes, const tbn_deflate_member* members, int n_members, void* out,
+                             size_t out_bytes, uint32_t* out_len, uint32_t* crc, int* status, uint32_t* chunk_end);
 
 #ifdef __cplusplus
 }
