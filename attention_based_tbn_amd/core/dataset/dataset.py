@@ -94,6 +94,50 @@ def read_wav(path, sampling_rate):
     return mono * np.float32(1.0 / 32768.0)
 
 
+_SOF = frozenset(range(0xC0, 0xD0)) - {0xC4, 0xC8, 0xCC}
+_HEADER_BYTES = 1 << 16
+
+
+def jpeg_frame_size(path):
+    """(H, W) of a JPEG file from its frame header alone: the markers are walked up to the first SOFn segment over the
+    file's first 64 KiB (the whole file only when application segments push the header past that).  What `plan` reads of
+    a clip it does not keep: the transform's draw needs the frame size and nothing else."""
+    try:
+        with open(path, "rb") as f:
+            head = f.read(_HEADER_BYTES)
+            size = _sof_size(head)
+            if size is None and len(head) == _HEADER_BYTES:
+                size = _sof_size(head + f.read())
+    except OSError:
+        raise Exception(f"Problem reading file {path}")
+    if size is None:
+        raise TbnHipError(f"jpeg_frame_size: {path}: no frame header")
+    return size
+
+
+def _sof_size(b):
+    if b[:2] != b"\xff\xd8":
+        return None
+    at = 2
+    while at + 4 <= len(b):
+        if b[at] != 0xFF:
+            return None
+        marker = b[at + 1]
+        if marker == 0xFF:                                  # fill byte
+            at += 1
+        elif marker == 0x01 or 0xD0 <= marker <= 0xD8:      # stand-alone markers
+            at += 2
+        elif marker in _SOF:
+            if at + 9 > len(b):
+                return None
+            return (b[at + 5] << 8 | b[at + 6], b[at + 7] << 8 | b[at + 8])
+        elif marker in (0xD9, 0xDA):                        # the scan begins: no frame header in front of it
+            return None
+        else:
+            at += 2 + (b[at + 2] << 8 | b[at + 3])
+    return None
+
+
 class _Visual(object):
     """what `plan` records for one clip and one visual modality"""
 
@@ -113,6 +157,7 @@ class _Clip(object):
 
     def __init__(self, record):
         self.record = record
+        self.kept = True        # False: a clip outside `keep` -- its draws were made, its files were not read
         self.vid_id = record.untrimmed_video_name
         self.indices = OrderedDict()
         self.visual = OrderedDict()
@@ -286,17 +331,43 @@ class Video_Dataset(object):
         hw = (keys[0][1], keys[0][0])
         return _Visual(paths, blobs, None, ("jpg",) + hw, hw, None, keys)
 
-    def plan(self, indices, rng=None):
+    def _frame_size(self, m, vid_id, indices):
+        """the source frame size (H, W) of a clip that is not kept, from ONE file's header: the first JPEG's frame header,
+        or the first pickle's `npz_member` record (the member itself only when the record sends it to the host)"""
+        path = self._frame_files(m, vid_id, indices)[0]         # names only: nothing is opened
+        if m == "Flow" and self.read_flow_pickle:
+            try:
+                with open(path, "rb") as f:
+                    record = npz_member(f.read())
+            except Exception as e:
+                raise Exception("Failed to load flow file {} with error {}.".format(path, e))
+            if record.host:
+                planes = self._read_flow_pickle(path)
+                return (int(planes.shape[1]), int(planes.shape[2]))
+            return tuple(int(v) for v in record.shape[:2])
+        return jpeg_frame_size(path)
+
+    def plan(self, indices, rng=None, keep=None):
         """The host half of `batch`: for every clip, in order, and every modality, in order, the segment indices (when
         that modality draws any) and THEN that modality's transform geometry -- the draw order of the reference's
         `__getitem__` (dataset.py:157-178) called clip after clip, under data.sampling "sync" and "async" alike.  Reads
         the frame files (the geometry needs the frame size) but touches no GPU.  Returns one record per clip with
         `.indices[m]`, `.visual[m].paths` and `.visual[m].geo`.  Every draw comes from `rng` (a `np.random.RandomState`);
-        None: from the global `np.random`, the same calls in the same order."""
+        None: from the global `np.random`, the same calls in the same order.
+
+        `keep` (positions into `indices`; None: all of them) names the clips this caller goes on to decode -- a rank's
+        share of a global batch (`ClipLoader(shard=)`).  EVERY draw is still made for EVERY clip, in the same order, so
+        the generator leaves in the state it would without `keep`; of a clip outside `keep` only the frame size the
+        transform's draw needs is read (`_frame_size`: one JPEG header or one `npz_member` record per visual modality,
+        no audio), its record carries `.kept = False` and `.visual[m]` without files."""
         draw = np.random if rng is None else rng
+        keep = None if keep is None else {int(k) for k in keep}
+        if keep is not None and not keep <= set(range(len(indices))):
+            raise ValueError(f"Video_Dataset.plan: keep {sorted(keep)} is not within the {len(indices)} clips")
         clips = []
-        for i in indices:
+        for pos, i in enumerate(indices):
             clip = _Clip(EpicVideoRecord(self.annotations.iloc[int(i)]))
+            clip.kept = keep is None or pos in keep
             first, num = clip.record.start_frame, clip.record.num_frames
             for m_no, m in enumerate(self.modality):
                 if m_no > 0 and self.cfg.data.sampling == "sync":
@@ -306,7 +377,11 @@ class Video_Dataset(object):
                     clip.indices[m] = get_offsets(first[m], num[m], m, self.mode, self.num_segments, self.frame_len[m],
                                                   rng=draw)
                 if m != "Audio":
-                    v = self._read_visual(m, clip.vid_id, clip.indices[m])
+                    if clip.kept:
+                        v = self._read_visual(m, clip.vid_id, clip.indices[m])
+                    else:
+                        hw = self._frame_size(m, clip.vid_id, clip.indices[m])
+                        v = _Visual(None, None, None, None, hw, None, None)
                     v.geo = self.transform[m]._record(*v.hw, rng=rng)
                     clip.visual[m] = v
             clips.append(clip)
@@ -385,7 +460,7 @@ class Video_Dataset(object):
         waves = [self._waveform(clip.vid_id) for clip in clips]
         return self._audio(waves, np.stack([clip.indices["Audio"] for clip in clips], 0))
 
-    def batch(self, indices, rng=None):
+    def batch(self, indices, rng=None, keep=None):
         """`(data, target)` in train mode, `(data, target, action_id)` otherwise: what `default_collate` makes of the
         reference's items `[dataset[i] for i in indices]`, already on the device --
           data[m]            (B, n, C, H, W) fp32 per modality;
@@ -393,7 +468,9 @@ class Video_Dataset(object):
           data["weights"]    (B, n, T, 1) with attention and use_fixed; target["weights"] with attention and use_prior;
           target["class"]    {"verb", "noun"}: int64 (B,), or an int64 (B,) of -1 when the label columns are missing;
           action_id          int64 (B,) when the uids are integers, else a list.
-        `rng`: handed to `plan`."""
+        `rng`, `keep`: handed to `plan`.  With `keep` (positions into `indices`) the batch holds the kept clips only, in
+        their order, while the generator advances as for the whole of `indices`; an empty `keep` makes the draws and
+        returns None."""
         indices = [int(i) for i in indices]
         if not indices:
             raise ValueError("Video_Dataset.batch: no indices")
@@ -401,7 +478,11 @@ class Video_Dataset(object):
         wants_weights = self.use_attention and (att.use_fixed or att.use_prior)
         if wants_weights and "Audio" not in self.modality:
             raise ValueError("Video_Dataset: the attention weights come from the Audio modality, which is not enabled")
-        clips = self.plan(indices, rng)
+        clips = self.plan(indices, rng, keep)
+        if keep is not None:
+            clips = [clip for clip in clips if clip.kept]
+            if not clips:
+                return None
         data, target = OrderedDict(), OrderedDict()
         data["vid_id"] = [clip.vid_id for clip in clips]
         data["start_time"] = [clip.record.start_time for clip in clips]

@@ -90,6 +90,7 @@ class DataParallel(nn.Module):
         self._callback_queued = False
         self._hooks = []
         self._sync = True               # False inside no_sync(): gradients stay local (accumulation steps, tests)
+        self.grad_weight = None         # see weigh_next_backward(): factor on this rank's gradients in the NEXT exchange
         self._presence = None           # ("pending", event, pinned host tensor) | ("count", n): see _exchange_presence
         self._side_stream = None
         self._host_flag = None
@@ -117,8 +118,17 @@ class DataParallel(nn.Module):
     def broadcast_parameters(self, src=0):
         """rank `src`'s parameters and buffers become everyone's (once, at wrap time): one broadcast per dtype over a
         flat buffer -- the same coalescing the gradient all-reduce uses -- instead of one per tensor (1464 of them)"""
+        self._broadcast_flat(list(self.module.parameters()) + list(self.module.buffers()), src)
+
+    def broadcast_buffers(self, src=0):
+        """rank `src`'s buffers (the BatchNorm running statistics) become everyone's, by the same flat broadcast: the
+        reference's nn.DataParallel keeps replica 0's running statistics as the model's, so the epoch loops call this
+        before each validation and before the checkpoint is written.  No-op for a lone rank."""
+        if self.world_size > 1:
+            self._broadcast_flat(list(self.module.buffers()), src)
+
+    def _broadcast_flat(self, tensors, src):
         with torch.no_grad():
-            tensors = list(self.module.parameters()) + list(self.module.buffers())
             by_dtype = {}
             for t in tensors:
                 by_dtype.setdefault((t.dtype, t.device), []).append(t)
@@ -154,6 +164,20 @@ class DataParallel(nn.Module):
             finally:
                 self._sync = old
         return ctx()
+
+    def weigh_next_backward(self, weight):
+        """the NEXT synchronised backward exchanges `weight` times this rank's gradients: with weight_r = n_r W / n the
+        average over the ranks is sum_r (n_r / n) g_r, the gradient of a mean over a global batch of n clips of which
+        this rank holds n_r (`TrainStep(share=)`).  Every gradient is multiplied ONCE, finished, right before its
+        collective is issued (gradient hook, bucket, end-of-backward tensors and the packed buffer alike) -- the backward
+        pass itself runs exactly as without a weight, so g_r keeps its bits.  Only right when `.grad` holds nothing
+        before that backward (every tensor is then what this backward produced); a caller that accumulates scales its
+        loss instead.  None clears it; the exchange clears it too."""
+        self.grad_weight = None if weight is None else float(weight)
+
+    def _weigh(self, t):
+        if self.grad_weight is not None and t.numel():
+            t.mul_(self.grad_weight)
 
     def _exchange_presence(self):
         """after a training forward: how many replicas used the optional parameters in this step (the module's
@@ -214,6 +238,7 @@ class DataParallel(nn.Module):
                 # enqueued AFTER this one (ready long before) until then.  So the prefix waits for the end of backward.
                 self._pending.append((p, p.grad.view(-1)[:self._bucketed[id(p)]], None))
             else:
+                self._weigh(p.grad)
                 self._pending.append((p, p.grad, dist.all_reduce(p.grad, op=op, group=self.process_group, async_op=True)))
 
     def _begin_backward(self):
@@ -247,6 +272,7 @@ class DataParallel(nn.Module):
             return None                  # not the next slice down: leave the rest to the hook
         avg, op = self._reduce_op()
         view = fresh.view(-1)[lo:hi]
+        self._weigh(view)
         work = dist.all_reduce(view, op=op, group=self.process_group, async_op=True)
         self._bucketed[id(p)] = lo
         self.bucket_log.append((fresh.numel(), lo, hi))
@@ -313,10 +339,13 @@ class DataParallel(nn.Module):
                       and not (nobody and id(p) in optional)]
         small = [p for p in params if p.numel() < self.SMALL]
         works = [w for _, _, w in self._pending if w is not None]
+        for p in late_large:
+            self._weigh(p.grad)
         works += [dist.all_reduce(p.grad, op=op, group=self.process_group, async_op=True) for p in late_large]
         # the prefixes of the bucketed tensors (see _on_grad_ready): now, behind every bucket of every backbone
         for i, (p, view, w) in enumerate(self._pending):
             if w is None and view.numel():
+                self._weigh(view)
                 w = dist.all_reduce(view, op=op, group=self.process_group, async_op=True)
                 self._pending[i] = (p, view, w)
                 works.append(w)
@@ -330,6 +359,7 @@ class DataParallel(nn.Module):
                 flags.append(1.0 if mismatch else 0.0)       # some rank's gradients contradict the exchanged draw
             flags = torch.tensor(flags, dtype=ref.dtype, device=ref.device)
             flat = torch.cat(pieces + [flags])
+            self._weigh(flat[:flat.numel() - flags.numel()])       # the gradients, not the presence flags
             works.append(dist.all_reduce(flat, op=op, group=self.process_group, async_op=True))
         for work in works:
             work.wait()          # stream-level wait on RCCL; host-blocking only on gloo
@@ -374,6 +404,7 @@ class DataParallel(nn.Module):
         self._count = None
         self._forwards_pending = 0
         self._unsynced = False
+        self.grad_weight = None
         if mismatch:
             # this rank followed the peers' schedule, i.e. its optional gradients were NOT reduced: drop them (the peers
             # hold None as well, so the replicas stay identical) and fail here; the peers fail at their next forward /
@@ -423,6 +454,7 @@ class DataParallel(nn.Module):
         self._pending, self._fired, self._callback_queued, self._presence, self._count = [], set(), False, None, None
         self._bucketed = {}
         self._forwards_pending = 0
+        self.grad_weight = None
 
     def _abort_group(self):
         try:

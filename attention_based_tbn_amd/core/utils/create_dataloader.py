@@ -12,6 +12,8 @@ What differs from the DataLoader, on purpose:
     reproducible shuffle, but it is NOT pinned to the draw of `torch.utils.data.RandomSampler` (which seeds a generator
     of its own from the global one first): the same `torch.manual_seed` gives another order than the reference's loader.
 The last, shorter batch is kept, as with the DataLoader's default `drop_last=False`.
+`shard=(rank, world)` makes the loader one of `world`, one per rank of a data-parallel job: the same global batches, each
+rank its contiguous share of every one (`ClipLoader`).
 """
 import os
 import queue
@@ -53,25 +55,50 @@ def _put(q, item, stop):
     return False
 
 
+def share_of(n, rank, world):
+    """rank `rank`'s share of a global batch of `n` clips: positions [floor(rank * n / world), floor((rank + 1) * n / world))"""
+    return rank * n // world, (rank + 1) * n // world
+
+
+class _Part(object):
+    """one global batch of a pass as one rank sees it: its number in the pass, its dataset indices, and the positions
+    [lo, hi) of them that are this rank's (`keep` None: the loader is not sharded and the whole batch is made)"""
+
+    def __init__(self, no, indices, keep, world):
+        self.no, self.indices, self.keep = no, indices, keep
+        n = len(indices)
+        self.share = (n if keep is None else len(keep), n, world)      # (n_r, n, W)
+
+    def make(self, dataset, rng):
+        """the batch, or None when this rank's share is empty (the draws of the whole global batch are made all the same)"""
+        if self.keep is None:
+            return dataset.batch(self.indices, rng=rng)
+        return dataset.batch(self.indices, rng=rng, keep=self.keep)
+
+
 def _produce(dataset, parts, rng, q, stop, stream, device):
-    """the producer thread: `dataset.batch(part, rng=rng)` for every part, in order, on `stream`; each result is queued
-    with the event recorded behind it.  Holds no reference to the iterator, so that one can be collected."""
+    """the producer thread: `part.make(dataset, rng)` for every part, in order, on `stream`; each result is queued
+    with its part and the event recorded behind it (an empty share is made for its draws and not queued).  Holds no
+    reference to the iterator, so that one can be collected."""
     try:
         if stream is None:
             for part in parts:
                 if stop.is_set():
                     return
-                if not _put(q, ("batch", dataset.batch(part, rng=rng), None), stop):
+                item = part.make(dataset, rng)
+                if item is not None and not _put(q, ("batch", (part, item), None), stop):
                     return
         else:
             with torch.cuda.device(device), torch.cuda.stream(stream):
                 for part in parts:
                     if stop.is_set():
                         return
-                    item = dataset.batch(part, rng=rng)
+                    item = part.make(dataset, rng)
+                    if item is None:
+                        continue
                     event = torch.cuda.Event()
                     event.record(stream)
-                    if not _put(q, ("batch", item, event), stop):
+                    if not _put(q, ("batch", (part, item), event), stop):
                         return
         _put(q, ("end", None, None), stop)
     except BaseException as e:      # delivered to the consumer at the __next__ that would have returned this batch
@@ -81,10 +108,10 @@ def _produce(dataset, parts, rng, q, stop, stream, device):
 class _PrefetchIter(object):
     """one pass of a `ClipLoader(prefetch > 0)`: owns the producer thread, its queue and its stop flag"""
 
-    def __init__(self, dataset, parts, rng, prefetch, stream, device):
+    def __init__(self, dataset, parts, rng, prefetch, stream, device, note):
         self._q = queue.Queue(maxsize=prefetch)
         self._stop = threading.Event()
-        self._stream, self._done = stream, False
+        self._stream, self._done, self._note = stream, False, note
         self.thread = threading.Thread(target=_produce, name="ClipLoader-producer", daemon=True,
                                        args=(dataset, parts, rng, self._q, self._stop, stream, device))
         self.thread.start()
@@ -109,10 +136,12 @@ class _PrefetchIter(object):
                     self.close()
                     raise RuntimeError("ClipLoader: the producer thread ended without a batch, an end mark or an error")
         if kind == "batch":
+            part, item = item
             if event is not None:
                 current = torch.cuda.current_stream(self._stream.device)
                 current.wait_event(event)           # device-side wait: the host does not synchronise
                 _record_stream(item, current)       # allocated on the loader stream, used (and freed) on this one
+            self._note(part)
             return item
         self.close()
         if kind == "error":
@@ -162,25 +191,64 @@ class ClipLoader(object):
     loader: a second `__iter__` closes the first.
 
     While an iterator is live the dataset object must not be used by another thread: its waveform cache is mutated by
-    the producer only."""
+    the producer only.
 
-    def __init__(self, dataset, batch_size, shuffle=False, *, prefetch=0, rng=_DEFAULT_RNG):
+    `shard=(rank, world)` (one loader per rank of a data-parallel job; `(0, 1)` and None are the unsharded loader).
+    `batch_size` stays the GLOBAL batch and the global batches of a pass are exactly the unsharded loader's
+    (`batches()`); of a global batch of n clips rank r makes positions [floor(r n / W), floor((r + 1) n / W)) and
+    nothing else (`dataset.batch(part, rng=, keep=)`: every draw of the whole batch, the files of the kept clips only).
+    `__iter__` has rank 0 draw the shuffle and the pass's NumPy seed from ITS torch generator and broadcast them -- one
+    small collective per pass on the default process group (`process_group=`), issued on the calling thread, never on
+    the producer's -- so a pass does not depend on the ranks' generators having stayed in step.  Implies and requires
+    `rng="private"`.  Under one torch seed on rank 0 the ranks' batches, concatenated in rank order, are the batch of
+    `ClipLoader(prefetch=0, rng="private")` at world 1 bit for bit, with and without `prefetch`.
+    In train mode (`dataset.mode == "train"`) a global batch of fewer than W clips -- it would leave a rank without a
+    backward to exchange gradients in -- is dropped on every rank and rank 0 logs one line; in val / test mode a rank
+    whose share of a batch is empty makes that batch's draws and does not yield it.  `len()` stays the number of GLOBAL
+    batches (without the dropped ones), so a rank may yield fewer.
+    `broadcast=` replaces the collective: a callable that takes rank 0's int64 tensor `[seed, order...]` (zeros on the
+    other ranks) and returns rank 0's (tests without a process group).
+
+    For the batch most recently yielded the loop reads `loader.share = (n_r, n, W)` -- this rank's clips, the global
+    batch's, the world size -- and `loader.batch_no`, the batch's number among the pass's global batches; both are set
+    on the consumer's thread when the batch is handed out, and also by an unsharded loader (`(n, n, 1)`)."""
+
+    def __init__(self, dataset, batch_size, shuffle=False, *, prefetch=0, rng=_DEFAULT_RNG, shard=None,
+                 process_group=None, broadcast=None, logger=None):
         if batch_size < 1:
             raise ValueError(f"ClipLoader: batch_size {batch_size}")
         if int(prefetch) != prefetch or prefetch < 0:
             raise ValueError(f"ClipLoader: prefetch {prefetch!r} is not a count >= 0")
         if rng not in ("global", "private"):
             raise ValueError(f"ClipLoader: rng={rng!r} is not 'global' or 'private'")
-        if prefetch > 0:
+        rank, world = 0, 1
+        if shard is not None:
+            try:
+                rank, world = shard
+                ok = int(rank) == rank and int(world) == world and world >= 1 and 0 <= rank < world
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"ClipLoader: shard={shard!r} is not (rank, world) with 0 <= rank < world")
+        if prefetch > 0 or world > 1:
             if rng is not _DEFAULT_RNG and rng == "global":
-                raise ValueError("ClipLoader: prefetch > 0 draws on another thread, which needs rng='private'")
+                raise ValueError("ClipLoader: prefetch > 0 draws on another thread and shard=(r, W > 1) draws from a seed "
+                                 "the ranks share; both need rng='private'")
             rng = "private"
         self.dataset, self.batch_size, self.shuffle = dataset, int(batch_size), bool(shuffle)
         self.prefetch, self.rng = int(prefetch), str(rng)
+        self.rank, self.world = int(rank), int(world)
+        self.process_group, self._broadcast, self._logger = process_group, broadcast, logger
+        self.drops = self.world > 1 and getattr(dataset, "mode", None) == "train"
+        self.share, self.batch_no = None, None
         self._stream, self._live = None, None
 
     def __len__(self):
-        return -(-len(self.dataset) // self.batch_size)
+        n = len(self.dataset)
+        if not self.drops:
+            return -(-n // self.batch_size)
+        full, last = divmod(n, self.batch_size)
+        return (full if self.batch_size >= self.world else 0) + (1 if last >= self.world else 0)
 
     def batches(self):
         """the index lists of one pass; with `shuffle` one `torch.randperm` draw from the global generator"""
@@ -188,13 +256,65 @@ class ClipLoader(object):
         order = torch.randperm(n).tolist() if self.shuffle else list(range(n))
         return [order[i:i + self.batch_size] for i in range(0, n, self.batch_size)]
 
+    def _note(self, part):
+        self.share, self.batch_no = part.share, part.no
+
     def _global_pass(self):
-        for part in self.batches():
-            yield self.dataset.batch(part)
+        for no, part in enumerate(self.batches()):
+            item = self.dataset.batch(part)
+            self._note(_Part(no, part, None, 1))
+            yield item
 
     def _private_pass(self, parts, rng):
         for part in parts:
-            yield self.dataset.batch(part, rng=rng)
+            item = part.make(self.dataset, rng)
+            if item is not None:
+                self._note(part)
+                yield item
+
+    def _exchange(self, packed):
+        """rank 0's `[seed, order...]` on every rank: ONE broadcast over the process group"""
+        if self._broadcast is not None:
+            return self._broadcast(packed)
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            raise RuntimeError(f"ClipLoader: shard=({self.rank}, {self.world}) needs an initialised torch.distributed "
+                               "process group (or broadcast=)")
+        if dist.get_world_size(self.process_group) != self.world or dist.get_rank(self.process_group) != self.rank:
+            raise RuntimeError(f"ClipLoader: shard=({self.rank}, {self.world}) is not this process's place in its group "
+                               f"({dist.get_rank(self.process_group)}, {dist.get_world_size(self.process_group)})")
+        src = dist.get_global_rank(self.process_group, 0) if self.process_group is not None else 0
+        if dist.get_backend(self.process_group) == "nccl":
+            device = torch.device(getattr(self.dataset, "device", "cuda"))
+            packed = packed.to(device)
+            dist.broadcast(packed, src, group=self.process_group)
+            return packed.cpu()
+        dist.broadcast(packed, src, group=self.process_group)
+        return packed
+
+    def _sharded_parts(self):
+        """rank 0 draws the pass (the shuffle, then the seed: `__iter__`'s order) and broadcasts it -> (parts, seed)"""
+        n = len(self.dataset)
+        packed = torch.zeros(n + 1, dtype=torch.int64)
+        if self.rank == 0:
+            batches = self.batches()
+            packed[0] = int(torch.randint(0, 2 ** 31 - 1, (1,)))
+            packed[1:] = torch.tensor([i for part in batches for i in part], dtype=torch.int64)
+        packed = self._exchange(packed).tolist()
+        seed, order = packed[0], packed[1:]
+        parts, dropped = [], 0
+        for first in range(0, n, self.batch_size):
+            indices = order[first:first + self.batch_size]
+            if self.drops and len(indices) < self.world:
+                dropped += 1
+                continue
+            lo, hi = share_of(len(indices), self.rank, self.world)
+            parts.append(_Part(len(parts), indices, range(lo, hi), self.world))
+        if dropped and self.rank == 0:
+            import logging
+            (self._logger or logging.getLogger(__name__)).info(
+                f"ClipLoader: dropped {dropped} train batch(es) of fewer than {self.world} clips (one per rank is needed)")
+        return parts, seed
 
     def _loader_stream(self):
         """(side stream, device), made on first use; (None, None) without CUDA"""
@@ -213,15 +333,18 @@ class ClipLoader(object):
         if self.rng == "global":
             return self._global_pass()
         self.close()
-        parts = self.batches()
-        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)))
+        if self.world > 1:
+            parts, seed = self._sharded_parts()
+        else:
+            parts = [_Part(no, part, None, 1) for no, part in enumerate(self.batches())]
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)))
         rng = np.random.RandomState(seed)
         if self.prefetch == 0:
             return self._private_pass(parts, rng)
         stream, device = self._loader_stream()
         if stream is not None:
             stream.wait_stream(torch.cuda.current_stream(device))    # e.g. waveforms cached by a synchronous pass
-        live = _PrefetchIter(self.dataset, parts, rng, self.prefetch, stream, device)
+        live = _PrefetchIter(self.dataset, parts, rng, self.prefetch, stream, device, self._note)
         self._live = weakref.ref(live)      # weak: dropping the iterator (a `break`) collects it, which stops the producer
         return live
 
@@ -233,8 +356,8 @@ class ClipLoader(object):
 
 
 def create_dataloader(cfg, logger, modality, mode="test", device="cuda", *, prefetch=0, audio_load="host",
-                      flow_load="host"):
-    """The annotation file, video list and batch size per mode follow the reference (:86-120); val reads the TRAIN
+                      flow_load="host", shard=None):
+    """`shard=(rank, world)`: handed to `ClipLoader`; the mode's batch size stays the global batch.  The annotation file, video list and batch size per mode follow the reference (:86-120); val reads the TRAIN
     annotation file filtered by the val video list, as there.  A relative `vid_list` path is taken from the directory
     above the `core` package, like the reference's; an empty one keeps every video.  `prefetch` is handed to `ClipLoader`,
     `audio_load` ("host" / "device": who reads raw audio files) and `flow_load` ("host" / "device": who inflates the flow
@@ -259,7 +382,7 @@ def create_dataloader(cfg, logger, modality, mode="test", device="cuda", *, pref
     transforms = get_transforms(cfg, modality, mode, device=device, flow_length=2 * cfg.data.flow.win_length)
     dataset = Video_Dataset(cfg, vid_list, annotation_file, modality, transform=transforms, mode=mode, device=device,
                             audio_load=audio_load, flow_load=flow_load)
-    loader = ClipLoader(dataset, batch_size, shuffle=(mode == "train"), prefetch=prefetch)
+    loader = ClipLoader(dataset, batch_size, shuffle=(mode == "train"), prefetch=prefetch, shard=shard, logger=logger)
     logger.info("Done.")
     logger.info("----------------------------------------------------------")
     return loader
