@@ -318,6 +318,15 @@ int tbn_profile_entry_bytes(int i, double* total_alg_bytes) {
 }
 const char* tbn_last_error(void) { return g_err; }
 
+// the input pitch rule of every conv C-ABI entry (host only, ahead of any launch): every family forms its input offsets from
+// the pitch and reads `channels` floats per pixel in float4 steps
+static int conv_in_ld_ok(const char* who, int in_ld, int channels) {
+  if (channels % 32 != 0) return TBN_OK;   // no kernel takes it: the launcher's channel rule refuses the launch in its own words
+  TBN_REQUIRE(in_ld >= channels && in_ld % 4 == 0, "%s: in_ld %d (at least the %d input channels, a multiple of 4)", who, in_ld,
+              channels);
+  return TBN_OK;
+}
+
 int tbn_conv2d_stat_tiles(int n, int h, int w, int cin, int cout, int ksize, int stride, int pad) {
   ConvP p;
   conv_geom(&p, n, h, w, cin, cout, ksize, stride, pad);
@@ -337,6 +346,7 @@ int tbn_conv2d_fwd(const float* in, int in_ld, const float* weight, const float*
   // only the explicit-tile entry point (tbn_conv2d_fwd_tile / tbn_conv_launch) may combine the two
   TBN_REQUIRE(!(epilogue == CONV_EPI_STATS && (flags & CONV_FLAG_SK4)),
               "conv2d_fwd: the split-K tile variant with the statistics epilogue needs an explicit tile (tbn_conv2d_fwd_tile)");
+  TBN_TRY(conv_in_ld_ok("conv2d_fwd", in_ld, cin));
   ConvP p;
   conv_geom(&p, n, h, w, cin, cout, ksize, stride, pad);
   p.in = in;
@@ -359,6 +369,7 @@ int tbn_conv2d_fwd(const float* in, int in_ld, const float* weight, const float*
 int tbn_conv2d_fwd_tile(const float* in, int in_ld, const float* weight, const float* bias, float* out, int out_ld,
                         int n, int h, int w, int cin, int cout, int ksize, int stride, int pad, int epilogue, int flags,
                         float* stat_partial, int mt, int nt, void* stream) {
+  TBN_TRY(conv_in_ld_ok("conv2d_fwd_tile", in_ld, cin));
   ConvP p;
   conv_geom(&p, n, h, w, cin, cout, ksize, stride, pad);
   p.in = in;
@@ -379,6 +390,7 @@ int tbn_conv2d_dgrad(const float* dout, int dout_ld, const float* weight, float*
                      int cin, int cout, int ksize, int stride, int pad, int accumulate, float* workspace,
                      void* stream) {
   TBN_REQUIRE(dout && weight && din && workspace, "conv2d_dgrad: null pointer");
+  TBN_TRY(conv_in_ld_ok("conv2d_dgrad", dout_ld, cout));
   hipStream_t st = (hipStream_t)stream;
   TBN_TRY(tbn_launch_weight_flip_transpose(weight, workspace, cout, ksize * ksize, cin, st));
   const int oh = (h + 2 * pad - ksize) / stride + 1, ow = (w + 2 * pad - ksize) / stride + 1;
@@ -413,6 +425,7 @@ int tbn_conv2d_dgrad(const float* dout, int dout_ld, const float* weight, float*
 static int desc_to_convp(const tbn_conv_desc* d, float* workspace, hipStream_t st, ConvP* pp) {
   ConvP& p = *pp;
   TBN_REQUIRE(d && d->in && d->weight && d->out, "conv_launch: null pointer");
+  TBN_TRY(conv_in_ld_ok("conv_launch", d->in_ld, d->dgrad ? d->cout : d->cin));
   if (!d->dgrad) {
     TBN_REQUIRE(d->epilogue >= 0 && d->epilogue <= 2, "conv_launch: bad epilogue");
     TBN_REQUIRE(d->epilogue != CONV_EPI_STATS || d->stat_partial, "conv_launch: stats epilogue needs stat_partial");
@@ -513,7 +526,7 @@ int tbn_conv_split_weights(const float* weight, int cout, int ksize, int cin, in
 int tbn_conv_partial_rows(const tbn_conv_desc* d, int mt, int pair) {
   if (!d || mt < 1) return 0;
   const int rows = ((d->flags & CONV_FLAG_SK4) && !pair ? 32 : 128) * mt;
-  if (d->dgrad) return tbn_conv_red_rows(d->n, d->h, d->w, d->stride, rows);
+  if (d->dgrad) return tbn_conv_red_rows(d->n, d->h, d->w, d->stride, d->ksize, d->pad, rows);
   const int oh = (d->h + 2 * d->pad - d->ksize) / d->stride + 1, ow = (d->w + 2 * d->pad - d->ksize) / d->stride + 1;
   return cdiv(d->n * oh * ow, rows);
 }

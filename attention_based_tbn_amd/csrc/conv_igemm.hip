@@ -1220,14 +1220,34 @@ void tbn_conv_pick_tile(int M, int Cout, int K, int* mt_out, int* nt_out) {
   *nt_out = bn;
 }
 
-// number of partial rows (M tiles) a data-gradient launch with a fused BN-backward reduce writes per reduce segment
-int tbn_conv_red_rows(int N, int OH, int OW, int up, int tile_rows) {
+// Stride-2 data gradient, one axis: filter tap r reaches a real (not zero-inserted) dy sample of the output pixels of
+// parity `par` when par - pad + r is even; *d = that sample's offset in dy (the number halved is even, possibly
+// negative: the division is exact)
+static bool parity_tap(int par, int pad, int r, int* d) {
+  const int o = par - pad + r;
+  *d = o / 2;
+  return (o & 1) == 0;
+}
+// one axis of a parity phase: does any of the `ksize` taps contribute to the output pixels of parity `par`
+static bool parity_has_tap(int par, int pad, int ksize) {
+  int d;
+  for (int r = 0; r < ksize; ++r)
+    if (parity_tap(par, pad, r, &d)) return true;
+  return false;
+}
+
+// number of partial rows (M tiles) a data-gradient launch with a fused BN-backward reduce writes per reduce segment: the
+// M tiles of every parity phase that launches (tbn_launch_conv skips a parity with pixels but no tap: 1x1 / stride 2).
+// ksize / pad: the FORWARD layer's (the launch pads by ksize - 1 - pad)
+int tbn_conv_red_rows(int N, int OH, int OW, int up, int ksize, int pad, int tile_rows) {
   if (up == 1) return cdiv(N * OH * OW, tile_rows);
   int rows = 0;
   for (int py = 0; py < 2; ++py)
     for (int px = 0; px < 2; ++px) {
       const int ohs = (OH - py + 1) / 2, ows = (OW - px + 1) / 2;
-      if (ohs > 0 && ows > 0) rows += cdiv(N * ohs * ows, tile_rows);
+      if (ohs <= 0 || ows <= 0) continue;
+      if (!parity_has_tap(py, ksize - 1 - pad, ksize) || !parity_has_tap(px, ksize - 1 - pad, ksize)) continue;
+      rows += cdiv(N * ohs * ows, tile_rows);
     }
   return rows;
 }
@@ -1403,14 +1423,6 @@ static int conv_prepare(ConvP& p, int rowmode, int* single) {
   return TBN_OK;
 }
 
-// Stride-2 data gradient, one axis: filter tap r reaches a real (not zero-inserted) dy sample of the output pixels of
-// parity `par` when par - pad + r is even; *d = that sample's offset in dy (the number halved is even, possibly
-// negative: the division is exact)
-static bool parity_tap(int par, int pad, int r, int* d) {
-  const int o = par - pad + r;
-  *d = o / 2;
-  return (o & 1) == 0;
-}
 // The output-parity phases of the strided data gradient `p` (prepared, up == 2): each phase is a unit-stride GEMM over
 // the output pixels of one parity with the taps that contribute there.  *empty_phase: a parity with pixels but no tap
 // (1x1 / stride 2 only) -- its gradient is zero and no phase writes it.
@@ -1499,6 +1511,10 @@ int tbn_launch_conv(ConvP p, int rowmode, int mt, int nt, hipStream_t st, const 
   static thread_local ConvPhases phases;   // ~2 KB kernel argument, built in place
   bool empty_phase = false;
   conv_build_phases(p, phases, &empty_phase);
+  // the fused reduce sums the gradient of the pixels its phases visit: where a parity has no phase, an accumulating launch
+  // leaves the earlier gradient of those pixels out of the sums
+  TBN_REQUIRE_OR(TBN_ERR_UNSUPPORTED, !(empty_phase && p.nred > 0 && (p.flags & CONV_FLAG_ACCUM)),
+                 "conv: an accumulating 1x1 strided data gradient cannot carry the fused BN-backward reduce");
   if (empty_phase && !(p.flags & CONV_FLAG_ACCUM)) {
     // pixels no phase writes: clear the whole destination first (stream order keeps this ahead of the phases)
     TBN_REQUIRE(p.nseg == 1, "conv: 1x1 strided data gradient writes one segment");

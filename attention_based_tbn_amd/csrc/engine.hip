@@ -2010,7 +2010,7 @@ int tbn_backbone_backward(const tbn_backbone_plan* P, const float* dfeatures, co
           // S1 / S2 partials were formed by the data-gradient epilogue that finished dz (conv RedSeg)
           const Conv& f = P->convs[q.red_src];
           L.partial = ws + q.bpart_off;
-          L.ext_parts = tbn_conv_red_rows(R, f.inH, f.inW, f.stride, writer_rows(P, f, GEMM_DGRAD, br));
+          L.ext_parts = tbn_conv_red_rows(R, f.inH, f.inW, f.stride, f.k, f.pad, writer_rows(P, f, GEMM_DGRAD, br));
         } else {
           L.partial = partial + (size_t)slot * P->partial_floats;
           L.ext_parts = 0;

@@ -209,7 +209,7 @@ void tbn_conv_pick_tile(int M, int Cout, int K, int* mt, int* nt);
 int tbn_launch_conv(ConvP p, int rowmode, int mt, int nt, hipStream_t st, const RiderP* rider = nullptr);
 // two independent unit-stride convs in one launch (variant 0 LDS-halo, 1 / 2 generic with 1 / 2 LDS stages; tiles <= (2,2))
 int tbn_launch_conv_pair(ConvP a, ConvP b, int variant, int mt, int nt, hipStream_t st, const RiderP* rider = nullptr);
-int tbn_conv_red_rows(int N, int OH, int OW, int up, int tile_rows);   // tile_rows = M rows per workgroup tile (128 * mt; 32 * mt for the split-K tile kernel)
+int tbn_conv_red_rows(int N, int OH, int OW, int up, int ksize, int pad, int tile_rows);   // tile_rows = M rows per workgroup tile (128 * mt; 32 * mt for the split-K tile kernel)
 size_t tbn_conv_halo_lds_bytes(const ConvP& p, int mt, int nt);   // 0: shape not handled by the LDS-halo kernel
 // f(integral_constant<int, MT>, integral_constant<int, NT>) for the tile (mt, nt) of a kernel family that admits
 // 1..MAXM x 1..MAXN; any other tile is refused (I walks the admitted tiles in row order)

@@ -362,7 +362,10 @@ typedef struct {
   int out2_raw;           /* epilogue 2: 1 = out2 receives the bare accumulator (no scale / shift / ReLU), what the engine does
                              for a pool_proj part whose average pool follows the conv */
 } tbn_conv_desc;
-/* rows of stat_partial / red[i].partial that a launch with M tile `mt` writes (pair = 1: issued by tbn_conv_launch_pair) */
+/* rows of stat_partial / red[i].partial that a launch with M tile `mt` writes (pair = 1: issued by tbn_conv_launch_pair); a
+ * strided data gradient writes one row per M tile of every parity phase that launches (1x1 / stride 2: one parity in four;
+ * accumulating, that launch refuses the reduce, which would miss the gradient already in the other pixels).
+ * Every conv entry refuses an input pitch below the channels read per pixel or not a multiple of 4 floats. */
 int tbn_conv_partial_rows(const tbn_conv_desc* d, int mt, int pair);
 int tbn_conv_launch(const tbn_conv_desc* d, int mt, int nt, float* workspace, void* stream);
 /* two independent unit-stride convolutions with the same epilogue in ONE launch (the 3x3 | double_3x3_1 siblings of an
