@@ -170,6 +170,11 @@ SIGNATURES = {
     "tbn_stem_workspace_floats": (c_sz, [c_i] * 6),
     "tbn_stem_conv_fwd": (c_i, [c_fp, c_fp, c_fp, c_fp] + [c_i] * 8 + [c_fp, c_fp, c_fp] + [c_i] * 3 + [c_fp, c_fp]),
     "tbn_stem_conv_wgrad": (c_i, [c_fp, c_i, c_fp, c_fp] + [c_i] * 8 + [c_fp, c_fp]),
+    # reference core/models/bn_inception_audio.py:11-18, 408-415 (conv1_1x3_s2 | conv1_3x1_s2, concatenated)
+    "tbn_audio_stem_stat_rows": (c_i, [c_i, c_i, c_i]),
+    "tbn_audio_stem_fwd": (c_i, [c_fp, c_fp, c_fp, c_fp] + [c_i] * 6 + [c_fp, c_fp, c_fp, c_fp]),
+    "tbn_audio_stem_wgrad_workspace_floats": (c_sz, [c_i, c_i, c_i]),
+    "tbn_audio_stem_wgrad": (c_i, [c_fp, c_i, c_fp, c_fp, c_i, c_i, c_i, c_fp, c_fp]),
     "tbn_linear_fwd": (c_i, [c_fp, c_i, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp]),
     "tbn_linear_dgrad": (c_i, [c_fp, c_i, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp]),
     "tbn_linear_wgrad_workspace_floats": (c_sz, [c_i, c_i, c_i]),

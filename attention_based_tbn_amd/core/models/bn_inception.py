@@ -606,13 +606,21 @@ class BNInception(nn.Module):
 
 
 def bninception(in_channels, modality, pretrained="imagenet", model_dir="", is_audio=False, attend=False,
-                state_dict=None):
+                state_dict=None, *, audio_stem="7x7"):
     """reference factory core/models/bn_inception.py:38-107.
 
     `state_dict` lets a caller hand over the weights directly instead of the Drive-hosted
     `weights/{imagenet_bninception_rgb,kinetics_bninception_flow}.pth` files; with `pretrained`
     set and no `state_dict` the file is loaded from `model_dir` exactly like the reference.
+
+    `audio_stem`: "7x7" (the reference as it stands) | "1x3_3x1": modality "Audio" gets `BNInception_Audio`, the line the
+    reference keeps commented out at :73; its pretrained state is reconciled as at :81-88 (keys the file lacks -- the
+    separable stem -- keep the model's own initialisation, keys the model lacks are dropped).
     """
+    if audio_stem not in ("7x7", "1x3_3x1"):
+        raise ValueError(f"bninception: audio_stem must be \"7x7\" or \"1x3_3x1\", got {audio_stem!r}")
+    if audio_stem == "1x3_3x1" and modality == "Audio":
+        return _bninception_audio(pretrained, model_dir, attend, state_dict)
     num_classes = 1000
     data_dict = state_dict
     if pretrained is not None:
@@ -637,6 +645,26 @@ def bninception(in_channels, modality, pretrained="imagenet", model_dir="", is_a
         model.load_state_dict(data_dict)
         print(f"Model initialized with {pretrained} weights")
     model.is_audio = is_audio
+    model.attend = attend
+    model.feature_size = 1024
+    delattr(model, "last_linear")
+    return model
+
+
+def _bninception_audio(pretrained, model_dir, attend, state_dict):
+    """the "1x3_3x1" arm of `bninception` for modality "Audio": same files, same class counts as the default arm"""
+    from .bn_inception_audio import BNInception_Audio
+    data_dict = state_dict
+    if pretrained is not None and data_dict is None:
+        file = "kinetics_bninception_flow.pth" if pretrained == "kinetics" else "imagenet_bninception_rgb.pth"
+        data_dict = torch.load(os.path.join(model_dir, file), map_location="cpu")
+    model = BNInception_Audio(num_classes=400 if pretrained == "kinetics" else 1000, attend=attend)
+    if data_dict is not None:
+        own = model.state_dict()
+        data_dict = {k: (data_dict[k] if k in data_dict else v) for k, v in own.items()}
+        model.load_state_dict(data_dict)
+        print(f"Model initialized with {pretrained} weights")
+    model.is_audio = True
     model.attend = attend
     model.feature_size = 1024
     delattr(model, "last_linear")

@@ -96,6 +96,10 @@ class _PEStack(nn.Sequential):
 
 class TBNModel(nn.Module):
     IN_CHANNELS = {"RGB": 3, "Flow": 10, "Audio": 1}
+    # stem of the BN-Inception audio backbone: "7x7" (the reference as it stands) | "1x3_3x1" (BNInception_Audio, the line
+    # reference bn_inception.py:73 keeps commented out).  A class attribute read in _create_base_model, set before the model
+    # is built: the config tree stays the reference's, so this is no config key
+    audio_stem = "7x7"
 
     def __init__(self, cfg, modality, device, pretrained_state=None):
         """`pretrained_state`: optional {"imagenet": sd, "kinetics": sd} replacing the `.pth` files
@@ -196,7 +200,8 @@ class TBNModel(nn.Module):
             if not os.path.exists(os.path.join(model_dir, fname)):
                 pretrained = None  # weights are Drive-hosted in the reference; offline -> random init
         return bninception(self.IN_CHANNELS[modality], modality, model_dir=model_dir, pretrained=pretrained,
-                           is_audio=(modality == "Audio"), attend=self.use_attention, state_dict=state)
+                           is_audio=(modality == "Audio"), attend=self.use_attention, state_dict=state,
+                           audio_stem=self.audio_stem)
 
     def _freeze_base_model(self, modality, freeze_mode):
         base = getattr(self, "Base_{}".format(modality))

@@ -8,6 +8,10 @@ ResNets of core/models/resnet.py -- is composed here from the stand-alone C-ABI 
                   conv1's data gradient meet in the block input's gradient buffer through the `accumulate` arguments of
                   tbn_bn_res_bwd / tbn_conv2d_dgrad instead of a separate add
   stem_bn_pool    the 7x7 / stride 2 / pad 3 stem straight from NCHW frames + BatchNorm + ReLU + MaxPool(3, 2, 1)
+and, for the BN-Inception trunk of core/models/bn_inception_audio.py (whose convs all carry a bias: conv_bn_act(bias=)):
+  audio_stem_bn_pool  the separable 1x3 | 3x1 / stride 2 audio stem + two BatchNorms + ReLU + MaxPool(3, 2, ceil)
+  maxpool3, avgpool3  the 3x3 pools of the inception blocks
+  freq_mean           the mean over the frequency axis alone, beside global_mean
 
 Training: tbn_conv2d_fwd epilogue 1 (bias-free output + statistics partials), then tbn_bn_fwd_batch (no residual, ReLU,
 at most 1024 channels) or tbn_bn_res_fwd (the join: residual and / or no ReLU and / or more channels).  Eval: running
@@ -68,15 +72,16 @@ def _oihw(dwk):
     return dwk.permute(0, 3, 1, 2)
 
 
-def folded_bn(gamma, beta, state):
-    """(2, c): scale = gamma / sqrt(var + eps) | shift = beta - mean * scale, folded once and kept until one of the four
-    tensors changes (`_version`)"""
+def folded_bn(gamma, beta, state, bias=None):
+    """(2, c): scale = gamma / sqrt(var + eps) | shift = beta - mean * scale (with a conv bias: beta + (bias - mean) *
+    scale), folded once and kept until one of the tensors changes (`_version`)"""
     rm, rv = state.running_mean, state.running_var
-    key = tuple((t.data_ptr(), t._version) for t in (gamma, beta, rm, rv))
+    key = tuple((t.data_ptr(), t._version) for t in (gamma, beta, rm, rv) + (() if bias is None else (bias,)))
     cache = state.fcache
     if cache.get("key") != key:
         sc = gamma.detach().float() / torch.sqrt(rv.float() + EPS)
-        cache["ss"] = torch.stack([sc, beta.detach().float() - rm.float() * sc]).contiguous()
+        mean = rm.float() if bias is None else rm.float() - bias.detach().float()
+        cache["ss"] = torch.stack([sc, beta.detach().float() - mean * sc]).contiguous()
         cache["key"] = key
     return cache["ss"]
 
@@ -105,10 +110,18 @@ def _conv_fwd(x, wk, stride, pad, epilogue, ss=None, partial=None):
     return y
 
 
-def _unit_fwd_train(x, wk, gamma, beta, state, res, relu):
-    """-> (y, z, stats): bias-free conv output, block output, (4, c) rows batch mean | 1/std | scale | shift"""
+_BIAS_AT_JOIN = ("{}: a conv bias in front of the BatchNorm of a join (residual, no ReLU, or more than 1024 channels) is "
+                 "not implemented: only the tbn_bn_fwd_batch path carries the bias into the running mean")
+
+
+def _unit_fwd_train(x, wk, gamma, beta, state, res, relu, bias=None):
+    """-> (y, z, stats): bias-free conv output, block output, (4, c) rows batch mean | 1/std | scale | shift.  A conv
+    `bias` cancels in the batch statistics: y and z do not see it, running_mean takes mean + bias"""
     n, h, w, cin = x.shape
     cout, k = wk.shape[0], wk.shape[1]
+    batched = res is None and relu and cout <= 1024
+    if bias is not None and not batched:
+        raise TbnHipError(_BIAS_AT_JOIN.format("conv_bn_act"))
     tiles = lib().tbn_conv2d_stat_tiles(n, h, w, cin, cout, k, state.stride, state.pad)
     partial = torch.empty(tiles * 2 * cout, device=x.device, dtype=torch.float32)
     y = _conv_fwd(x, wk, state.stride, state.pad, 1, partial=partial)
@@ -116,11 +129,11 @@ def _unit_fwd_train(x, wk, gamma, beta, state, res, relu):
     z = torch.empty_like(y)
     stats = torch.empty(4, cout, device=x.device, dtype=torch.float32)
     rm, rv = state.running_mean, state.running_var
-    if res is None and relu and cout <= 1024:
+    if batched:
         d = BnFwdDesc()
         d.y, d.y_ld, d.p, d.c = y.data_ptr(), cout, p, cout
         d.partial, d.pld, d.nparts = partial.data_ptr(), cout, tiles
-        d.gamma, d.beta, d.conv_bias = gamma.data_ptr(), beta.data_ptr(), 0
+        d.gamma, d.beta, d.conv_bias = gamma.data_ptr(), beta.data_ptr(), ptr(bias)
         d.running_mean, d.running_var = ptr(rm), ptr(rv)
         d.save_mean, d.save_rstd, d.scale, d.shift = (stats[i].data_ptr() for i in range(4))
         d.seg[0] = BnSeg(z.data_ptr(), cout, 0)
@@ -136,8 +149,8 @@ def _unit_fwd_train(x, wk, gamma, beta, state, res, relu):
     return y, z, stats
 
 
-def _unit_fwd_eval(x, wk, gamma, beta, state, res, relu):
-    ss = folded_bn(gamma, beta, state)
+def _unit_fwd_eval(x, wk, gamma, beta, state, res, relu, bias=None):
+    ss = folded_bn(gamma, beta, state, bias)
     if res is None and relu:
         return _conv_fwd(x, wk, state.stride, state.pad, 2, ss=ss)
     z = _conv_fwd(x, wk, state.stride, state.pad, 0)
@@ -203,17 +216,18 @@ _EVAL_BACKWARD = ("{}: backward through an eval-mode backbone (running-statistic
 # ---------------------------------------------------------------------------------------------- one fused unit
 class _ConvBnActFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, gamma, beta, residual, state, relu, training):
+    def forward(ctx, x, weight, gamma, beta, residual, state, relu, training, bias=None):
         _need_cuda(x, "conv_bn_act")
         x = _f32c(x)
         wk = kernel_weight(weight, state.wcache)
         _check_conv(x, wk, "conv_bn_act")
         res = _f32c(residual) if residual is not None else None
+        cb = _f32c(bias.detach()) if bias is not None else None
         ctx.eval_mode = not training
-        ctx.live = training and any(ctx.needs_input_grad[:5])
+        ctx.live = training and (any(ctx.needs_input_grad[:5]) or ctx.needs_input_grad[8])
         if not training:
-            return _unit_fwd_eval(x, wk, gamma, beta, state, res, relu)
-        y, z, stats = _unit_fwd_train(x, wk, gamma, beta, state, res, relu)
+            return _unit_fwd_eval(x, wk, gamma, beta, state, res, relu, cb)
+        y, z, stats = _unit_fwd_train(x, wk, gamma, beta, state, res, relu, cb)
         if ctx.live:
             ctx.state, ctx.relu, ctx.had_res = state, relu, res is not None
             ctx.save_for_backward(x, wk, y, z, stats)
@@ -223,29 +237,34 @@ class _ConvBnActFn(torch.autograd.Function):
     def backward(ctx, dz):
         need = ctx.needs_input_grad
         if not ctx.live:
-            if ctx.eval_mode and any(need[:5]):
+            if ctx.eval_mode and (any(need[:5]) or need[8]):
                 raise TbnHipError(_EVAL_BACKWARD.format("conv_bn_act"))
-            return (None,) * 8
+            return (None,) * 9
         x, wk, y, z, stats = ctx.saved_tensors
         dz = _f32c(dz)
         dres = torch.empty_like(y) if (ctx.had_res and need[4]) else None
         dy, dg, db = _bn_bwd(dz, y, z, stats, ctx.had_res, ctx.relu, dres, need[2] or need[3])
         dw = _conv_wgrad(dy, x, wk, ctx.state) if need[1] else None
         dx = _conv_dgrad(dy, wk, x.shape, ctx.state) if need[0] else None
-        return dx, dw, dg if need[2] else None, db if need[3] else None, dres, None, None, None
+        # a per-channel constant in front of a batch-statistics BatchNorm has exactly zero gradient
+        dbias = torch.zeros(y.shape[-1], device=y.device, dtype=torch.float32) if need[8] else None
+        return dx, dw, dg if need[2] else None, db if need[3] else None, dres, None, None, None, dbias
 
 
 def conv_bn_act(x, weight, gamma, beta, running_mean, running_var, stride, pad, residual=None, relu=True,
-                training=True, state=None):
-    """act(bn(conv(x)) + residual) on NHWC tensors: x (n, h, w, cin), weight OIHW (no conv bias), residual (n, oh, ow,
-    cout) or None, act = ReLU or identity.  training: batch statistics, running_mean / running_var (may be None) updated
-    with momentum 0.1; else the running statistics.  `state` (a BnState the caller keeps) carries the weight and fold
-    caches from call to call; without one they are rebuilt per call."""
+                training=True, state=None, bias=None):
+    """act(bn(conv(x) + bias) + residual) on NHWC tensors: x (n, h, w, cin), weight OIHW, residual (n, oh, ow, cout) or
+    None, act = ReLU or identity.  training: batch statistics, running_mean / running_var (may be None) updated with
+    momentum 0.1; else the running statistics.  `state` (a BnState the caller keeps) carries the weight and fold caches
+    from call to call; without one they are rebuilt per call.  `bias` (cout floats or None): in training it cancels in the
+    batch statistics -- the output is bit-identical to the call without it, running_mean takes mean + bias, its gradient
+    is zeros -- and is only taken where no residual joins (ReLU, at most 1024 channels); in eval it is folded into the
+    shift."""
     if state is None:
         state = BnState(stride, pad, running_mean, running_var)
     else:
         state.stride, state.pad, state.running_mean, state.running_var = stride, pad, running_mean, running_var
-    return _ConvBnActFn.apply(x, weight, gamma, beta, residual, state, bool(relu), bool(training))
+    return _ConvBnActFn.apply(x, weight, gamma, beta, residual, state, bool(relu), bool(training), bias)
 
 
 # ---------------------------------------------------------------------------------------------- a residual block
@@ -353,19 +372,20 @@ def residual_block(x, main, downsample=None, training=True):
 
 # ---------------------------------------------------------------------------------------------- global average pool
 class _GlobalMeanFn(torch.autograd.Function):
-    """NHWC (n, h, w, c) -> (n, c).  tbn_spatial_mean_fwd takes at most 1024 channels per call: wider maps (the 2048 of
-    ResNet-50/101/152) go through it as column ranges of the same buffers (the entry reads and writes pitched rows)."""
+    """NHWC (n, h, w, c) -> (n, c), or with `freq_only` the mean over h alone -> (n, w, c).  tbn_spatial_mean_fwd takes at
+    most 1024 channels per call: wider maps (the 2048 of ResNet-50/101/152) go through it as column ranges of the same
+    buffers (the entry reads and writes pitched rows)."""
 
     @staticmethod
-    def forward(ctx, x):
-        _need_cuda(x, "global_mean")
+    def forward(ctx, x, freq_only=False):
+        _need_cuda(x, "freq_mean" if freq_only else "global_mean")
         x = _f32c(x)
         n, h, w, c = x.shape
-        out = torch.empty(n, c, device=x.device, dtype=torch.float32)
+        out = torch.empty((n, w, c) if freq_only else (n, c), device=x.device, dtype=torch.float32)
         for c0 in range(0, c, 1024):
             call("tbn_spatial_mean_fwd", x.data_ptr() + 4 * c0, c, out.data_ptr() + 4 * c0, c, n, h, w, min(1024, c - c0),
-                 0, stream_ptr())
-        ctx.shape = tuple(x.shape)
+                 int(freq_only), stream_ptr())
+        ctx.shape, ctx.freq_only = tuple(x.shape), freq_only
         return out
 
     @staticmethod
@@ -373,13 +393,88 @@ class _GlobalMeanFn(torch.autograd.Function):
         n, h, w, c = ctx.shape
         dout = _f32c(dout)
         dx = torch.empty(ctx.shape, device=dout.device, dtype=torch.float32)
-        call("tbn_spatial_mean_bwd", ptr(dout), c, ptr(dx), c, n, h, w, c, 0, stream_ptr())
-        return dx
+        call("tbn_spatial_mean_bwd", ptr(dout), c, ptr(dx), c, n, h, w, c, int(ctx.freq_only), stream_ptr())
+        return dx, None
 
 
 def global_mean(x_nhwc):
     """AdaptiveAvgPool2d(1) + flatten on an NHWC map of any width that is a multiple of 4"""
     return _GlobalMeanFn.apply(x_nhwc)
+
+
+def freq_mean(x_nhwc):
+    """the mean over the frequency axis alone, (n, h, w, c) -> (n, w, c): F.avg_pool2d(features, (h, 1)) of the attended
+    audio trunk (reference bn_inception_audio.py:1012-1019) in the layout the attention heads read"""
+    return _GlobalMeanFn.apply(x_nhwc, True)
+
+
+# ---------------------------------------------------------------------------------------------- 3x3 pools
+def pool_out_size(size, stride, pad, ceil_mode):
+    """output length of a kernel-3 pool along one axis (torch's rule: in ceil mode the last window must start inside the
+    input or its left padding)"""
+    o = (size + 2 * pad - 3 + (stride - 1 if ceil_mode else 0)) // stride + 1
+    if ceil_mode and (o - 1) * stride >= size + pad:
+        o -= 1
+    return o
+
+
+def _check_pool(x, what):
+    _need_cuda(x, what)
+    if x.dim() != 4 or x.shape[3] % 4:
+        raise TbnHipError(f"{what}: input {tuple(x.shape)} is not NHWC with a multiple of 4 channels")
+
+
+class _MaxPool3Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, stride, pad, ceil_mode):
+        _check_pool(x, "maxpool3")
+        x = _f32c(x)
+        n, h, w, c = x.shape
+        oh, ow = pool_out_size(h, stride, pad, ceil_mode), pool_out_size(w, stride, pad, ceil_mode)
+        out = torch.empty(n, oh, ow, c, device=x.device, dtype=torch.float32)
+        live = ctx.needs_input_grad[0]
+        argmax = torch.empty(n, oh, ow, c, device=x.device, dtype=torch.uint8) if live else None
+        call("tbn_maxpool3_fwd", ptr(x), c, ptr(out), c, ptr(argmax), n, h, w, c, oh, ow, stride, pad, stream_ptr())
+        if live:
+            ctx.geom = (n, h, w, c, oh, ow, stride, pad)
+            ctx.save_for_backward(argmax)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (argmax,) = ctx.saved_tensors
+        n, h, w, c, oh, ow, stride, pad = ctx.geom
+        dout = _f32c(dout)
+        dx = torch.empty(n, h, w, c, device=dout.device, dtype=torch.float32)
+        call("tbn_maxpool3_bwd", ptr(dout), c, ptr(argmax), ptr(dx), c, n, h, w, c, oh, ow, stride, pad, 0, stream_ptr())
+        return dx, None, None, None
+
+
+def maxpool3(x_nhwc, stride, pad, ceil_mode=False):
+    """nn.MaxPool2d(3, stride, pad, ceil_mode=ceil_mode) on an NHWC map (channels a multiple of 4)"""
+    return _MaxPool3Fn.apply(x_nhwc, int(stride), int(pad), bool(ceil_mode))
+
+
+class _AvgPool3Fn(torch.autograd.Function):
+    """tbn_avgpool3_fwd is self-adjoint: the same launch on the output's gradient is the backward"""
+
+    @staticmethod
+    def forward(ctx, x):
+        _check_pool(x, "avgpool3")
+        x = _f32c(x)
+        n, h, w, c = x.shape
+        out = torch.empty_like(x)
+        call("tbn_avgpool3_fwd", ptr(x), c, ptr(out), c, n, h, w, c, 0, stream_ptr())
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        return _AvgPool3Fn.apply(dout)
+
+
+def avgpool3(x_nhwc):
+    """nn.AvgPool2d(3, stride 1, padding 1, count_include_pad=True) on an NHWC map (channels a multiple of 4)"""
+    return _AvgPool3Fn.apply(x_nhwc)
 
 
 # ---------------------------------------------------------------------------------------------- the stem
@@ -466,3 +561,98 @@ def stem_bn_pool(x_nchw, weight, gamma, beta, state, training=True, who="stem_bn
     """MaxPool2d(3, 2, 1)(relu(bn(conv7x7_s2_p3(x)))): NCHW frames (n, cin <= 16, h, w) -> NHWC (n, ph, pw, cout).  No
     input gradient is formed: asking for one raises TbnHipError in backward."""
     return _StemFn.apply(x_nchw, weight, gamma, beta, state, bool(training), who)
+
+
+# ---------------------------------------------------------------------------------------------- the separable audio stem
+class _AudioStemFn(torch.autograd.Function):
+    """params: the two conv weights, the two conv biases, then gamma / beta of the two BatchNorms"""
+
+    @staticmethod
+    def forward(ctx, x, wa, wb, ba, bb, ga, gb, bea, beb, bns, training):
+        who = "audio_stem_bn_pool"
+        _need_cuda(x, who)
+        x = _f32c(x)
+        if (x.dim() != 4 or x.shape[1] != 1 or tuple(wa.shape) != (32, 1, 3, 1) or tuple(wb.shape) != (32, 1, 1, 3)
+                or any(t.numel() != 32 for t in (ba, bb, ga, gb, bea, beb))):
+            raise TbnHipError(f"{who}: the audio stem is Conv2d(1, 32, (3, 1)) | Conv2d(1, 32, (1, 3)) with bias on a "
+                              f"one-channel input, got weights {tuple(wa.shape)}, {tuple(wb.shape)} for input "
+                              f"{tuple(x.shape)}")
+        n, _, h, w = x.shape
+        st = stream_ptr()
+        cat = lambda a, b: torch.cat([a.detach().reshape(32, -1), b.detach().reshape(32, -1)]).float().contiguous()
+        wk = cat(wa, wb)                                   # [64][3]
+        bias, gamma, beta = cat(ba, bb).view(64), cat(ga, gb).view(64), cat(bea, beb).view(64)
+        # two 32-channel BatchNorms over a concatenation are one 64-channel BatchNorm
+        rm = torch.cat([bns[0].running_mean, bns[1].running_mean]).float()
+        rv = torch.cat([bns[0].running_var, bns[1].running_var]).float()
+        oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        ph, pw = pool_out_size(oh, 2, 0, True), pool_out_size(ow, 2, 0, True)      # MaxPool2d(3, 2, ceil_mode=True)
+        y = torch.empty(n, oh, ow, 64, device=x.device, dtype=torch.float32)
+        pooled = torch.empty(n, ph, pw, 64, device=x.device, dtype=torch.float32)
+        ctx.eval_mode = not training
+        ctx.live = training and any(ctx.needs_input_grad[1:9])
+        if not training:
+            sc = gamma / torch.sqrt(rv + EPS)
+            sh = beta + (bias - rm) * sc
+            call("tbn_audio_stem_fwd", ptr(x), ptr(wk), 0, ptr(y), 64, n, h, w, 2, 0, ptr(sc), ptr(sh), 0, st)
+            call("tbn_maxpool3_fwd", ptr(y), 64, ptr(pooled), 64, 0, n, oh, ow, 64, ph, pw, 2, 0, st)
+            return pooled
+        argmax = torch.empty(n, ph, pw, 64, device=x.device, dtype=torch.uint8)
+        partial = torch.empty(lib().tbn_audio_stem_stat_rows(n, h, w) * 128, device=x.device, dtype=torch.float32)
+        call("tbn_audio_stem_fwd", ptr(x), ptr(wk), 0, ptr(y), 64, n, h, w, 1, 0, 0, 0, ptr(partial), st)
+        m = n * oh * ow
+        stats = torch.empty(4, 64, device=x.device, dtype=torch.float32)
+        bnws = torch.empty(lib().tbn_bn_workspace_floats(m, 64), device=x.device, dtype=torch.float32)
+        call("tbn_bn_relu_maxpool_train_fwd", ptr(y), n, oh, ow, 64, ptr(gamma), ptr(beta), ptr(rm), ptr(rv), MOMENTUM,
+             EPS, stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), ptr(pooled), 64,
+             ptr(argmax), ph, pw, 2, 0, ptr(bnws), st)
+        # y is the bias-free conv output: the reference's BatchNorm sees conv + bias, its batch mean is larger by the bias
+        rm += MOMENTUM * bias
+        for i, bn in enumerate(bns):       # (copy_ bumps the buffers' `_version` for the caches keyed on it)
+            bn.running_mean.copy_(rm[32 * i:32 * i + 32])
+            bn.running_var.copy_(rv[32 * i:32 * i + 32])
+        if ctx.live:
+            ctx.save_for_backward(x, y, argmax, stats)
+        return pooled
+
+    @staticmethod
+    def backward(ctx, dpooled):
+        who = "audio_stem_bn_pool"
+        need = ctx.needs_input_grad
+        if need[0]:
+            raise TbnHipError(_NO_INPUT_GRAD.format(who))
+        if not ctx.live:
+            if ctx.eval_mode and any(need[1:9]):
+                raise TbnHipError(_EVAL_BACKWARD.format(who))
+            return (None,) * 11
+        x, y, argmax, stats = ctx.saved_tensors
+        n, _, h, w = x.shape
+        _, oh, ow, _ = y.shape
+        ph, pw = argmax.shape[1], argmax.shape[2]
+        st = stream_ptr()
+        dpooled = _f32c(dpooled)
+        dy = torch.empty_like(y)
+        dgb = torch.empty(2, 64, device=x.device, dtype=torch.float32)
+        bnws = torch.empty(lib().tbn_bn_workspace_floats(n * oh * ow, 64), device=x.device, dtype=torch.float32)
+        call("tbn_bn_relu_maxpool_train_bwd", ptr(dpooled), 64, ptr(argmax), ptr(y), n, oh, ow, 64, ph, pw, 2, 0,
+             stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), ptr(dy),
+             dgb[0].data_ptr(), dgb[1].data_ptr(), ptr(bnws), st)
+        dwa = dwb = None
+        if need[1] or need[2]:
+            ws = torch.empty(lib().tbn_audio_stem_wgrad_workspace_floats(n, h, w), device=x.device, dtype=torch.float32)
+            dwk = torch.empty(64, 3, device=x.device, dtype=torch.float32)
+            call("tbn_audio_stem_wgrad", ptr(dy), 64, ptr(x), ptr(dwk), n, h, w, ptr(ws), st)
+            dwa, dwb = dwk[:32].view(32, 1, 3, 1), dwk[32:].view(32, 1, 1, 3)
+        zeros = lambda: torch.zeros(32, device=x.device, dtype=torch.float32)   # a bias in front of a batch-statistics BN
+        return (None, dwa if need[1] else None, dwb if need[2] else None, zeros() if need[3] else None,
+                zeros() if need[4] else None, dgb[0, :32] if need[5] else None, dgb[0, 32:] if need[6] else None,
+                dgb[1, :32] if need[7] else None, dgb[1, 32:] if need[8] else None, None, None)
+
+
+def audio_stem_bn_pool(x_nchw, conv_a, bn_a, conv_b, bn_b, training=True):
+    """MaxPool2d(3, 2, ceil_mode=True)(cat(relu(bn_a(conv_a(x))), relu(bn_b(conv_b(x))))): a one-channel spectrogram
+    (n, 1, h, w) -> NHWC (n, ph, pw, 64).  conv_a = Conv2d(1, 32, (3, 1), stride 2, padding (1, 0)), conv_b = Conv2d(1, 32,
+    (1, 3), stride 2, padding (0, 1)), both with bias; the modules are parameter containers, in training their running
+    statistics are updated in place.  No input gradient is formed: asking for one raises TbnHipError in backward."""
+    return _AudioStemFn.apply(x_nchw, conv_a.weight, conv_b.weight, conv_a.bias, conv_b.bias, bn_a.weight, bn_b.weight,
+                              bn_a.bias, bn_b.bias, (bn_a, bn_b), bool(training))

@@ -419,6 +419,31 @@ int tbn_stem_conv_fwd(const float* x_nchw, const float* weight, const float* bia
 int tbn_stem_conv_wgrad(const float* dy, int dy_ld, const float* x_nchw, float* dweight, int n, int h, int w, int cin, int cout,
                         int layout, int mt, int nt, float* workspace, void* stream);
 
+/* ---- the separable audio stem of BNInception_Audio -------------------------------------------------
+ * Both stem convolutions of the one-channel spectrogram in one pass, concatenated: x (n, 1, h, w) contiguous, any h, w >= 1;
+ * out NHWC (n, oh, ow, 64), oh = (h - 1) / 2 + 1, ow = (w - 1) / 2 + 1, pitch out_ld >= 64, a multiple of 4, out 16-B aligned.
+ *   channel c < 32:  sum_t weight[c][t]      * x[2 oy - 1 + t][2 ox]      (three taps along frequency)
+ *   channel 32 + c:  sum_t weight[32 + c][t] * x[2 oy][2 ox - 1 + t]      (three taps along time)
+ * reads outside the image are zero.  weight / dweight [64][3]: rows 0..31 = conv1_1x3_s2.weight.view(32, 3), rows 32..63 =
+ * conv1_3x1_s2.weight.view(32, 3); bias / scale / shift: 64 floats.  Plain fp32 FMAs in tap order (no MFMA: 6 multiply-adds
+ * per value, the kernel streams); deterministic.
+ * tbn_audio_stem_stat_rows: rows of stat_partial that epilogue 1 writes; 0 for arguments the entries refuse.  Host only.
+ * tbn_audio_stem_fwd: epilogue / flags / bias / scale / shift / stat_partial as tbn_conv2d_fwd: 0 = + bias (NULL: none;
+ *   flag 2: ReLU, no other flag), 1 = bias-free output plus stat_partial[(i*2 + {0,1}) * 64 + ch] = sum | sum of squares over
+ *   row chunk i, the layout tbn_bn_fwd_batch reads, 2 = relu(acc * scale + shift).
+ * tbn_audio_stem_wgrad: dweight from dy (n, oh, ow, 64) with pitch dy_ld (as out_ld); workspace of
+ *   tbn_audio_stem_wgrad_workspace_floats floats (one [64][3] partial per workgroup, summed in fixed order in fp64; no
+ *   atomics).  No data gradient (the input is a spectrogram) and no bias gradient (a BatchNorm follows) are formed.
+ * replaces: the forward / weight gradient of conv1_1x3_s2 = nn.Conv2d(1, 32, (3, 1), stride 2, padding (1, 0)) and
+ * conv1_3x1_s2 = nn.Conv2d(1, 32, (1, 3), stride 2, padding (0, 1)) with the torch.cat behind them
+ * (bn_inception_audio.py:11-13, 16-18, 408, 411, 415; cuDNN there). */
+int tbn_audio_stem_stat_rows(int n, int h, int w);
+int tbn_audio_stem_fwd(const float* x, const float* weight, const float* bias, float* out, int out_ld, int n, int h, int w,
+                       int epilogue, int flags, const float* scale, const float* shift, float* stat_partial, void* stream);
+size_t tbn_audio_stem_wgrad_workspace_floats(int n, int h, int w);
+int tbn_audio_stem_wgrad(const float* dy, int dy_ld, const float* x, float* dweight, int n, int h, int w, float* workspace,
+                         void* stream);
+
 /* nn.Linear / nn.Conv1d(k=1) (model.py:337-386 Fusion/Classifier, model.py:62-67 pe.1, the MHA
  * projections attention.py:48-57): out[m][n] = x[m][:] . w[n][:] + bias[n].  k % 32 == 0. */
 int tbn_linear_fwd(const float* x, int x_ld, const float* w, const float* bias, float* out, int out_ld, int m, int k,
