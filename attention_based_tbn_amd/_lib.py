@@ -175,6 +175,15 @@ SIGNATURES = {
     "tbn_audio_stem_fwd": (c_i, [c_fp, c_fp, c_fp, c_fp] + [c_i] * 6 + [c_fp, c_fp, c_fp, c_fp]),
     "tbn_audio_stem_wgrad_workspace_floats": (c_sz, [c_i, c_i, c_i]),
     "tbn_audio_stem_wgrad": (c_i, [c_fp, c_i, c_fp, c_fp, c_i, c_i, c_i, c_fp, c_fp]),
+    # reference core/models/vgg.py:15-41 (torchvision's vgg features[0], MaxPool2d(2, 2), avgpool + flatten)
+    "tbn_conv3_first_stat_rows": (c_i, [c_i] * 4),
+    "tbn_conv3_first_fwd": (c_i, [c_fp, c_fp, c_fp, c_fp] + [c_i] * 8 + [c_fp, c_fp, c_fp, c_fp]),
+    "tbn_conv3_first_wgrad_workspace_floats": (c_sz, [c_i] * 4),
+    "tbn_conv3_first_wgrad": (c_i, [c_fp, c_i, c_fp, c_fp] + [c_i] * 5 + [c_fp, c_fp]),
+    "tbn_maxpool2_fwd": (c_i, [c_fp, c_i, c_fp, c_i, c_fp] + [c_i] * 4 + [c_fp]),
+    "tbn_maxpool2_bwd": (c_i, [c_fp, c_i, c_fp, c_fp, c_i, c_fp, c_i] + [c_i] * 5 + [c_fp]),
+    "tbn_adaptive_avgpool7_fwd": (c_i, [c_fp, c_i, c_fp] + [c_i] * 4 + [c_fp]),
+    "tbn_adaptive_avgpool7_bwd": (c_i, [c_fp, c_fp, c_i] + [c_i] * 5 + [c_fp]),
     "tbn_linear_fwd": (c_i, [c_fp, c_i, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp]),
     "tbn_linear_dgrad": (c_i, [c_fp, c_i, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp]),
     "tbn_linear_wgrad_workspace_floats": (c_sz, [c_i, c_i, c_i]),

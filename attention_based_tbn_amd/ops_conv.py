@@ -12,6 +12,11 @@ and, for the BN-Inception trunk of core/models/bn_inception_audio.py (whose conv
   audio_stem_bn_pool  the separable 1x3 | 3x1 / stride 2 audio stem + two BatchNorms + ReLU + MaxPool(3, 2, ceil)
   maxpool3, avgpool3  the 3x3 pools of the inception blocks
   freq_mean           the mean over the frequency axis alone, beside global_mean
+and, for the VGGs of core/models/vgg.py (no BatchNorm in the plain variants, a 3x3 first layer, 2x2 pools, a 7x7 head):
+  conv_bias_act       conv + bias + optional ReLU without BatchNorm
+  first_conv3         the 3x3 / stride 1 / pad 1 first layer straight from NCHW frames, plain or with BatchNorm
+  maxpool2            MaxPool2d(2, 2), optionally carrying the ReLU mask of the conv in front of it in its backward
+  adaptive_avgpool7_flat  AdaptiveAvgPool2d((7, 7)) + flatten in the NCHW order the classifier's weight expects
 
 Training: tbn_conv2d_fwd epilogue 1 (bias-free output + statistics partials), then tbn_bn_fwd_batch (no residual, ReLU,
 at most 1024 channels) or tbn_bn_res_fwd (the join: residual and / or no ReLU and / or more channels).  Eval: running
@@ -100,13 +105,14 @@ def _check_conv(x, wk, what):
 
 
 # ---------------------------------------------------------------------------------------------- launches (no autograd)
-def _conv_fwd(x, wk, stride, pad, epilogue, ss=None, partial=None):
+def _conv_fwd(x, wk, stride, pad, epilogue, ss=None, partial=None, bias=None, flags=0):
     n, h, w, cin = x.shape
     cout, k = wk.shape[0], wk.shape[1]
     oh, ow = _out_size(h, w, k, stride, pad)
     y = torch.empty(n, oh, ow, cout, device=x.device, dtype=torch.float32)
-    call("tbn_conv2d_fwd", ptr(x), cin, ptr(wk), 0, ptr(y), cout, n, h, w, cin, cout, k, stride, pad, epilogue, 0,
-         ss[0].data_ptr() if ss is not None else 0, ss[1].data_ptr() if ss is not None else 0, ptr(partial), stream_ptr())
+    call("tbn_conv2d_fwd", ptr(x), cin, ptr(wk), ptr(bias), ptr(y), cout, n, h, w, cin, cout, k, stride, pad, epilogue,
+         flags, ss[0].data_ptr() if ss is not None else 0, ss[1].data_ptr() if ss is not None else 0, ptr(partial),
+         stream_ptr())
     return y
 
 
@@ -656,3 +662,229 @@ def audio_stem_bn_pool(x_nchw, conv_a, bn_a, conv_b, bn_b, training=True):
     statistics are updated in place.  No input gradient is formed: asking for one raises TbnHipError in backward."""
     return _AudioStemFn.apply(x_nchw, conv_a.weight, conv_b.weight, conv_a.bias, conv_b.bias, bn_a.weight, bn_b.weight,
                               bn_a.bias, bn_b.bias, (bn_a, bn_b), bool(training))
+
+
+# ---------------------------------------------------------------------------------------------- conv + bias (+ ReLU), no BN
+def _relu_mask(dz, z):
+    g = torch.empty_like(dz)
+    call("tbn_relu_mask_bwd", ptr(dz), ptr(z), 0, ptr(g), dz.numel(), stream_ptr())
+    return g
+
+
+def _colsum(g):
+    """column sums of a (..., c) tensor seen as (rows, c): the bias gradient.  tbn_colsum runs c / 32 workgroups whatever the
+    row count (it was written for the heads' few hundred rows; over the 4.8 M rows of a 96 x 224 x 224 map it took 70 % of a
+    VGG16 step), so the rows are first folded into the per-chunk sums of tbn_bn_stats_partials at streaming rate (its sums
+    of squares go unused) and tbn_colsum adds those few rows"""
+    c = g.shape[-1]
+    rows = g.numel() // c
+    out = torch.empty(c, device=g.device, dtype=torch.float32)
+    if c > 1024:         # wider than the statistics kernel takes
+        call("tbn_colsum", ptr(g), c, ptr(out), rows, c, stream_ptr())
+        return out
+    partial = torch.empty(lib().tbn_bn_workspace_floats(rows, c), device=g.device, dtype=torch.float32)
+    nparts = C.c_int(0)
+    call("tbn_bn_stats_partials", ptr(g), c, rows, c, ptr(partial), C.byref(nparts), stream_ptr())
+    call("tbn_colsum", ptr(partial), 2 * c, ptr(out), nparts.value, c, stream_ptr())
+    return out
+
+
+class _ConvBiasActFn(torch.autograd.Function):
+    """Without BatchNorm train and eval are the same function: backward works in both."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, state, relu, relu_in_pool):
+        _need_cuda(x, "conv_bias_act")
+        x = _f32c(x)
+        wk = kernel_weight(weight, state.wcache)
+        _check_conv(x, wk, "conv_bias_act")
+        cb = _f32c(bias.detach()) if bias is not None else None
+        z = _conv_fwd(x, wk, state.stride, state.pad, 0, bias=cb, flags=2 if relu else 0)
+        if any(ctx.needs_input_grad[:3]):
+            ctx.state, ctx.mask = state, relu and not relu_in_pool
+            ctx.save_for_backward(x, wk, z if ctx.mask else None)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        need = ctx.needs_input_grad
+        x, wk, z = ctx.saved_tensors
+        dy = _f32c(dz)
+        if ctx.mask:
+            dy = _relu_mask(dy, z)
+        db = _colsum(dy) if need[2] else None
+        dw = _conv_wgrad(dy, x, wk, ctx.state) if need[1] else None
+        dx = _conv_dgrad(dy, wk, x.shape, ctx.state) if need[0] else None
+        return dx, dw, db, None, None, None
+
+
+def conv_bias_act(x, weight, bias, stride, pad, relu=True, relu_in_pool=False, state=None):
+    """act(conv(x) + bias) on NHWC tensors, act = ReLU or identity: x (n, h, w, cin), weight OIHW (1x1 / 3x3, cin and cout
+    multiples of 32), bias (cout floats or None).  `relu_in_pool`: the caller passes the output straight to
+    maxpool2(..., relu_gate=True), whose backward applies this unit's ReLU mask -- the backward here then skips its own mask
+    pass (the pair costs one pass over the map instead of two).  A frozen weight / bias costs no gradient launch.  `state`
+    (a BnState the caller keeps) carries the kernel-layout weight copy from call to call."""
+    if state is None:
+        state = BnState(stride, pad, None, None)
+    else:
+        state.stride, state.pad = stride, pad
+    return _ConvBiasActFn.apply(x, weight, bias, state, bool(relu), bool(relu and relu_in_pool))
+
+
+# ---------------------------------------------------------------------------------------------- the 3x3 first layer
+class _FirstConv3Fn(torch.autograd.Function):
+    """x NCHW frames; gamma is None: relu(conv + bias) (train = eval); else BatchNorm + ReLU behind the conv"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, state, relu, training, relu_in_pool, who):
+        _need_cuda(x, who)
+        x = _f32c(x)
+        if x.dim() != 4 or tuple(weight.shape) != (64, x.shape[1], 3, 3) or not 1 <= x.shape[1] <= 16:
+            raise TbnHipError(f"{who}: the first layer is a 3x3 / stride 1 / pad 1 conv of 1..16 input channels to 64, got "
+                              f"weight {tuple(weight.shape)} for input {tuple(x.shape)}")
+        n, cin, h, w = x.shape
+        wk = kernel_weight(weight, state.wcache)
+        cb = _f32c(bias.detach()) if bias is not None else None
+        st = stream_ptr()
+        y = torch.empty(n, h, w, 64, device=x.device, dtype=torch.float32)
+        ctx.who, ctx.bn, ctx.eval_mode = who, gamma is not None, False
+        if gamma is None:
+            call("tbn_conv3_first_fwd", ptr(x), ptr(wk), ptr(cb), ptr(y), 64, n, h, w, cin, 64, 0, 2 if relu else 0, 0, 0,
+                 0, st)
+            ctx.live = any(ctx.needs_input_grad[1:3])
+            if ctx.live:
+                ctx.mask = relu and not relu_in_pool
+                ctx.save_for_backward(x, y if ctx.mask else None)
+            return y
+        if not relu:
+            raise TbnHipError(f"{who}: the BatchNorm form of the first layer is always followed by ReLU")
+        ctx.eval_mode = not training
+        ctx.live = training and any(ctx.needs_input_grad[1:5])
+        if not training:
+            ss = folded_bn(gamma, beta, state, cb)
+            call("tbn_conv3_first_fwd", ptr(x), ptr(wk), 0, ptr(y), 64, n, h, w, cin, 64, 2, 0, ss[0].data_ptr(),
+                 ss[1].data_ptr(), 0, st)
+            return y
+        rows = lib().tbn_conv3_first_stat_rows(n, cin, h, w)
+        partial = torch.empty(rows * 128, device=x.device, dtype=torch.float32)
+        call("tbn_conv3_first_fwd", ptr(x), ptr(wk), 0, ptr(y), 64, n, h, w, cin, 64, 1, 0, 0, 0, ptr(partial), st)
+        z = torch.empty_like(y)
+        stats = torch.empty(4, 64, device=x.device, dtype=torch.float32)
+        rm, rv = state.running_mean, state.running_var
+        d = BnFwdDesc()
+        d.y, d.y_ld, d.p, d.c = y.data_ptr(), 64, n * h * w, 64
+        d.partial, d.pld, d.nparts = partial.data_ptr(), 64, rows
+        d.gamma, d.beta, d.conv_bias = gamma.data_ptr(), beta.data_ptr(), ptr(cb)
+        d.running_mean, d.running_var = ptr(rm), ptr(rv)
+        d.save_mean, d.save_rstd, d.scale, d.shift = (stats[i].data_ptr() for i in range(4))
+        d.seg[0] = BnSeg(z.data_ptr(), 64, 0)
+        d.nseg = 1
+        call("tbn_bn_fwd_batch", C.byref(d), 1, MOMENTUM, EPS, st)
+        if rm is not None:
+            torch.autograd.graph.increment_version((rm, rv))
+        if ctx.live:
+            ctx.save_for_backward(x, y, z, stats)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        need = ctx.needs_input_grad
+        if need[0]:
+            raise TbnHipError(_NO_INPUT_GRAD.format(ctx.who))
+        if not ctx.live:
+            if ctx.eval_mode and any(need[1:5]):
+                raise TbnHipError(_EVAL_BACKWARD.format(ctx.who))
+            return (None,) * 10
+        dy = _f32c(dz)
+        dg = dbeta = db = None
+        if ctx.bn:
+            x, y, z, stats = ctx.saved_tensors
+            dy, dg, dbeta = _bn_bwd(dy, y, z, stats, False, True, None, need[3] or need[4])
+            # a per-channel constant in front of a batch-statistics BatchNorm has exactly zero gradient
+            db = torch.zeros(64, device=x.device, dtype=torch.float32) if need[2] else None
+        else:
+            x, z = ctx.saved_tensors
+            if ctx.mask:
+                dy = _relu_mask(dy, z)
+            db = _colsum(dy) if need[2] else None
+        dw = None
+        if need[1]:
+            n, cin, h, w = x.shape
+            ws = torch.empty(max(lib().tbn_conv3_first_wgrad_workspace_floats(n, cin, h, w), 1), device=x.device,
+                             dtype=torch.float32)
+            dwk = torch.empty(64, 3, 3, cin, device=x.device, dtype=torch.float32)
+            call("tbn_conv3_first_wgrad", ptr(dy), 64, ptr(x), ptr(dwk), n, h, w, cin, 64, ptr(ws), stream_ptr())
+            dw = _oihw(dwk)
+        return (None, dw, db, dg if need[3] else None, dbeta if need[4] else None, None, None, None, None, None)
+
+
+def first_conv3(x_nchw, weight, bias, gamma=None, beta=None, state=None, relu=True, training=True, relu_in_pool=False,
+                who="first_conv3"):
+    """The 3x3 / stride 1 / pad 1 first layer straight from NCHW frames (n, cin <= 16, h, w) -> NHWC (n, h, w, 64).
+    Plain form (gamma is None): act(conv + bias), the same function in train and eval; `relu_in_pool` as in conv_bias_act.
+    BatchNorm form (gamma, beta and a BnState with the running statistics): relu(bn(conv + bias)); in training the bias
+    cancels in the batch statistics and only enters the running mean, as conv_bn_act(bias=) does it, in eval it is folded
+    into the shift.  No input gradient is formed: asking for one raises TbnHipError in backward."""
+    if state is None:
+        state = BnState(1, 1, None, None)
+    return _FirstConv3Fn.apply(x_nchw, weight, bias, gamma, beta, state, bool(relu), bool(training),
+                               bool(relu and relu_in_pool and gamma is None), who)
+
+
+# ---------------------------------------------------------------------------------------------- the pools of a VGG
+class _MaxPool2Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, relu_gate):
+        _check_pool(x, "maxpool2")
+        x = _f32c(x)
+        n, h, w, c = x.shape
+        out = torch.empty(n, h // 2, w // 2, c, device=x.device, dtype=torch.float32)
+        live = ctx.needs_input_grad[0]
+        argmax = torch.empty(n, h // 2, w // 2, c, device=x.device, dtype=torch.uint8) if live else None
+        call("tbn_maxpool2_fwd", ptr(x), c, ptr(out), c, ptr(argmax), n, h, w, c, stream_ptr())
+        if live:
+            ctx.shape = (n, h, w, c)
+            ctx.save_for_backward(argmax, x if relu_gate else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        argmax, z = ctx.saved_tensors
+        n, h, w, c = ctx.shape
+        dout = _f32c(dout)
+        dx = torch.empty(n, h, w, c, device=dout.device, dtype=torch.float32)
+        call("tbn_maxpool2_bwd", ptr(dout), c, ptr(argmax), ptr(z), c, ptr(dx), c, n, h, w, c, 0, stream_ptr())
+        return dx, None
+
+
+def maxpool2(x_nhwc, relu_gate=None):
+    """nn.MaxPool2d(2, 2) on an NHWC map (channels a multiple of 4, h and w at least 2; a trailing odd row / column is
+    dropped).  `relu_gate` true: x is the output of a ReLU whose own backward mask was left out (conv_bias_act /
+    first_conv3 with relu_in_pool) -- the gradient written is additionally gated by x > 0."""
+    return _MaxPool2Fn.apply(x_nhwc, bool(relu_gate))
+
+
+class _AdaptiveAvgPool7Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        _check_pool(x, "adaptive_avgpool7_flat")
+        x = _f32c(x)
+        n, h, w, c = x.shape
+        out = torch.empty(n, c * 49, device=x.device, dtype=torch.float32)
+        call("tbn_adaptive_avgpool7_fwd", ptr(x), c, ptr(out), n, h, w, c, stream_ptr())
+        ctx.shape = (n, h, w, c)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        n, h, w, c = ctx.shape
+        dout = _f32c(dout)
+        dx = torch.empty(n, h, w, c, device=dout.device, dtype=torch.float32)
+        call("tbn_adaptive_avgpool7_bwd", ptr(dout), ptr(dx), c, n, h, w, c, 0, stream_ptr())
+        return dx
+
+
+def adaptive_avgpool7_flat(x_nhwc):
+    """torch.flatten(nn.AdaptiveAvgPool2d((7, 7))(x), 1) of an NHWC map (n, h, w, c) -> (n, c * 49) in the NCHW order
+    (column = ch * 49 + oy * 7 + ox): a checkpoint's classifier.0.weight multiplies it as it is"""
+    return _AdaptiveAvgPool7Fn.apply(x_nhwc)

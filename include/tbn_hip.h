@@ -444,6 +444,55 @@ size_t tbn_audio_stem_wgrad_workspace_floats(int n, int h, int w);
 int tbn_audio_stem_wgrad(const float* dy, int dy_ld, const float* x, float* dweight, int n, int h, int w, float* workspace,
                          void* stream);
 
+/* ---- the operators of the VGG backbones beside the 3x3 convolutions and the Linear layers -----------
+ * All fp32, deterministic (no atomics); every entry checks its arguments before any launch.
+ *
+ * The first convolution, 3x3 / stride 1 / pad 1 straight from the frames: x (n, cin, h, w) contiguous NCHW, cin in 1..16, any
+ * h, w >= 1 with n * h * w < 2^27; weight / dweight [cout][3][3][cin] with cout = 64 (anything else: TBN_ERR_UNSUPPORTED);
+ * out NHWC (n, h, w, 64), pitch out_ld >= 64, a multiple of 4, out 16-B aligned.  Reads outside the image are zero.  Plain
+ * fp32 FMAs in the fixed order filter row, input channel, filter column (no MFMA: 9 cin multiply-adds per value against
+ * 256 B written per pixel, the kernel streams).
+ * tbn_conv3_first_stat_rows: rows of stat_partial that epilogue 1 writes; 0 for arguments the entries refuse.  Host only.
+ * tbn_conv3_first_fwd: epilogue / flags / bias / scale / shift / stat_partial as tbn_audio_stem_fwd: 0 = + bias (NULL: none;
+ *   flag 2: ReLU, no other flag), 1 = bias-free output plus stat_partial[(i*2 + {0,1}) * 64 + ch] = sum | sum of squares over
+ *   row chunk i, the layout tbn_bn_fwd_batch reads, 2 = relu(acc * scale + shift).
+ * tbn_conv3_first_wgrad: dweight from dy (n, h, w, 64) with pitch dy_ld (as out_ld); workspace of
+ *   tbn_conv3_first_wgrad_workspace_floats floats (one [64][3][3][cin] partial per workgroup, summed in fixed order in fp64).
+ *   No data gradient is formed: the input is frames.
+ * replaces: the forward / weight gradient of features[0] = nn.Conv2d(cin, 64, 3, padding 1) of torchvision's vgg11 / vgg16
+ * (_bn) as core/models/vgg.py:15-41 builds and replaces it (cuDNN there). */
+int tbn_conv3_first_stat_rows(int n, int cin, int h, int w);
+int tbn_conv3_first_fwd(const float* x, const float* weight, const float* bias, float* out, int out_ld, int n, int h, int w,
+                        int cin, int cout, int epilogue, int flags, const float* scale, const float* shift,
+                        float* stat_partial, void* stream);
+size_t tbn_conv3_first_wgrad_workspace_floats(int n, int cin, int h, int w);
+int tbn_conv3_first_wgrad(const float* dy, int dy_ld, const float* x, float* dweight, int n, int h, int w, int cin, int cout,
+                          float* workspace, void* stream);
+/* nn.MaxPool2d(2, 2) on NHWC (n, h, w, c): c a multiple of 4, h, w >= 2, floor mode -- out (n, h / 2, w / 2, c), a trailing
+ * odd row / column is dropped.  Pitches are multiples of 4 and >= c, the float tensors 16-B aligned.  argmax (n, h / 2,
+ * w / 2, c) uint8, unpitched, 4-B aligned, may be NULL in the forward: the tap 2 * dy + dx of the first maximum in scan order
+ * (a NaN wins), the rule of tbn_maxpool3_fwd.
+ * tbn_maxpool2_bwd writes EVERY element of din (n, h, w, c): dout where the element is its window's argmax, zero elsewhere
+ * and in a dropped row / column; accumulate != 0 adds to din instead.  z (NULL, or the pool's own forward input with pitch
+ * z_ld): the value is additionally gated by z > 0 -- the pool's backward and the ReLU mask of the layer in front of it in one
+ * pass; the result equals tbn_maxpool2_bwd without z followed by tbn_relu_mask_bwd on z.
+ * replaces: the nn.MaxPool2d(kernel_size=2, stride=2) layers of torchvision's vgg features (core/models/vgg.py:15-41). */
+int tbn_maxpool2_fwd(const float* in, int in_ld, float* out, int out_ld, uint8_t* argmax, int n, int h, int w, int c,
+                     void* stream);
+int tbn_maxpool2_bwd(const float* dout, int dout_ld, const uint8_t* argmax, const float* z, int z_ld, float* din, int din_ld,
+                     int n, int h, int w, int c, int accumulate, void* stream);
+/* nn.AdaptiveAvgPool2d((7, 7)) + torch.flatten(x, 1): in NHWC (n, h, w, c) with pitch in_ld (a multiple of 4, >= c), c a
+ * multiple of 4, any h, w >= 1; out (n, c * 49) contiguous in the order of the flattened NCHW tensor, column = ch * 49 +
+ * oy * 7 + ox, so classifier.0.weight of a checkpoint is used as it is.  Windows are PyTorch's: bin i of an axis of length L
+ * covers [floor(i L / 7), ceil((i + 1) L / 7)) -- replication for L < 7, overlap where 7 does not divide L.  A window is
+ * summed in fp32 in row order and divided by its area; at h = w = 7 the forward is the transposition, bit for bit.
+ * tbn_adaptive_avgpool7_bwd: din NHWC (pitch din_ld) = for every element the sum of dout / area over the windows that
+ * contain it (summed in fp64, rounded once); accumulate != 0 adds to din instead.
+ * replaces: avgpool + flatten of torchvision's VGG.forward (core/models/vgg.py:15-41). */
+int tbn_adaptive_avgpool7_fwd(const float* in, int in_ld, float* out, int n, int h, int w, int c, void* stream);
+int tbn_adaptive_avgpool7_bwd(const float* dout, float* din, int din_ld, int n, int h, int w, int c, int accumulate,
+                              void* stream);
+
 /* nn.Linear / nn.Conv1d(k=1) (model.py:337-386 Fusion/Classifier, model.py:62-67 pe.1, the MHA
  * projections attention.py:48-57): out[m][n] = x[m][:] . w[n][:] + bias[n].  k % 32 == 0. */
 int tbn_linear_fwd(const float* x, int x_ld, const float* w, const float* bias, float* out, int out_ld, int m, int k,
