@@ -22,8 +22,9 @@ import torch
 import torch.nn as nn
 
 from ... import ops_conv
-from ..._lib import ConvInfo, TbnHipError, call, lib
+from ..._lib import ConvInfo, call, lib
 from .bn_inception import _BLOCKS, reference_conv_order
+from .ops_backbone import OpsBackbone, conv_bn_relu, count_batch
 
 # (name, kernel, padding) of the two stem branches, stride 2 (reference bn_inception_audio.py:11-13, 16-18)
 _STEM = (("conv1_1x3_s2", (3, 1), (1, 0)), ("conv1_3x1_s2", (1, 3), (0, 1)))
@@ -47,7 +48,7 @@ def _trunk_layers():
     return {name: table[name] for name in reference_conv_order()[1:]}
 
 
-class BNInception_Audio(nn.Module):
+class BNInception_Audio(OpsBackbone, nn.Module):
     def __init__(self, num_classes=1000, attend=False):
         super().__init__()
         self.attend = attend
@@ -62,37 +63,6 @@ class BNInception_Audio(nn.Module):
             setattr(self, name, nn.Conv2d(cin, cout, kernel_size=(k, k), stride=(stride, stride), padding=(pad, pad)))
             setattr(self, name + "_bn", nn.BatchNorm2d(cout, affine=True))
         self.last_linear = nn.Linear(1024, num_classes)
-        # knobs TBNModel sets on every backbone; they steer the backbone engine, which this backbone does not use
-        self.use_aux_stream = False
-        self.use_branch_streams = False
-        self.stem_wgrad_last = False
-        self._conv_math, self._conv_math_layers = "f32", "3x3"
-
-    # ---- the per-backbone knobs of TBNModel
-    @property
-    def conv_math(self):
-        return self._conv_math
-
-    @conv_math.setter
-    def conv_math(self, value):
-        if value != "f32":
-            raise ValueError(f"BNInception_Audio: conv_math {value!r} is not available (the split-bf16 modes cover the "
-                             "BN-Inception engine only); \"f32\" is the only mode")
-        self._conv_math = value
-
-    @property
-    def conv_math_layers(self):
-        return self._conv_math_layers
-
-    @conv_math_layers.setter
-    def conv_math_layers(self, value):
-        if value != "3x3":
-            raise ValueError(f"BNInception_Audio: conv_math_layers {value!r} is not available; \"3x3\" (the default) is "
-                             "the only value")
-        self._conv_math_layers = value
-
-    def flip_weights_early(self):
-        """no-op: the operator-level data gradients prepare their weights themselves"""
 
     def set_bn_trainable(self, first, rest):
         """BN affine requires_grad split of TBNModel 'partialbn' (reference model.py:164-176: every BatchNorm2d child
@@ -104,27 +74,15 @@ class BNInception_Audio(nn.Module):
     # ---- compute
     def _unit(self, name, x):
         """relu(bn(conv(x))) of the trunk layer `name`, NHWC in and out"""
-        conv, bn = getattr(self, name), getattr(self, name + "_bn")
-        s = conv.__dict__.get("_tbn_state")
-        if s is None:
-            s = conv.__dict__["_tbn_state"] = ops_conv.BnState(conv.stride[0], conv.padding[0], None, None)
-        out = ops_conv.conv_bn_act(x, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, conv.stride[0],
-                                   conv.padding[0], relu=True, training=self.training, state=s, bias=conv.bias)
-        if self.training:
-            bn.num_batches_tracked += 1
-        return out
+        return conv_bn_relu(getattr(self, name), getattr(self, name + "_bn"), x, self.training)
 
     def _stem(self, x):
         """NCHW spectrogram -> the NHWC output of pool1_3x3_s2"""
-        if not x.is_cuda:
-            raise TbnHipError("BNInception_Audio: input is on the CPU; this backbone only runs on an MI355X via "
-                              "libtbn_hip.so (no CPU fallback)")
+        self._need_gpu(x)
         (a, _, _), (b, _, _) = _STEM
         bn_a, bn_b = getattr(self, a + "_bn"), getattr(self, b + "_bn")
         out = ops_conv.audio_stem_bn_pool(x, getattr(self, a), bn_a, getattr(self, b), bn_b, training=self.training)
-        if self.training:
-            bn_a.num_batches_tracked += 1
-            bn_b.num_batches_tracked += 1
+        count_batch(self.training, bn_a, bn_b)
         return out
 
     def _trunk(self, x):

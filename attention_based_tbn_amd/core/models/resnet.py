@@ -14,7 +14,7 @@ BN-Inception this backbone does not go through the backbone engine (no plans, au
 import torch.nn as nn
 
 from ... import ops_conv
-from ..._lib import TbnHipError
+from .ops_backbone import OpsBackbone, count_batch, unit_state
 
 _DEPTHS = {
     18: ("basic", (2, 2, 2, 2)),
@@ -23,19 +23,6 @@ _DEPTHS = {
     101: ("bottleneck", (3, 4, 23, 3)),
     152: ("bottleneck", (3, 8, 36, 3)),
 }
-
-
-def _state(conv, bn):
-    """the unit's BnState, kept on the conv container so its weight / fold caches live from call to call"""
-    s = conv.__dict__.get("_tbn_state")
-    if s is None:
-        s = conv.__dict__["_tbn_state"] = ops_conv.BnState(conv.stride[0], conv.padding[0], None, None)
-    s.running_mean, s.running_var = bn.running_mean, bn.running_var     # (module.to() replaces the buffers)
-    return s
-
-
-def _unit(conv, bn):
-    return (conv.weight, bn.weight, bn.bias, _state(conv, bn))
 
 
 def _conv(cin, cout, k, stride):
@@ -50,13 +37,12 @@ class _Block(nn.Module):
 
     def forward(self, x):
         """NHWC in, NHWC out"""
-        main = [_unit(getattr(self, "conv%d" % i), getattr(self, "bn%d" % i)) for i in range(1, self.units + 1)]
-        ds = _unit(self.downsample[0], self.downsample[1]) if self.downsample is not None else None
-        out = ops_conv.residual_block(x, main, ds, training=self.training)
-        if self.training:
-            for m in self.modules():
-                if isinstance(m, nn.BatchNorm2d):
-                    m.num_batches_tracked += 1
+        pairs = [(getattr(self, "conv%d" % i), getattr(self, "bn%d" % i)) for i in range(1, self.units + 1)]
+        if self.downsample is not None:
+            pairs.append(tuple(self.downsample))
+        units = [(conv.weight, bn.weight, bn.bias, unit_state(conv, bn)) for conv, bn in pairs]
+        out = ops_conv.residual_block(x, units[:self.units], *units[self.units:], training=self.training)
+        count_batch(self.training, *(bn for _, bn in pairs))
         return out
 
 
@@ -85,7 +71,7 @@ class Bottleneck(_Block):
         self._downsample(cin, 4 * width, stride)
 
 
-class Resnet(nn.Module):
+class Resnet(OpsBackbone, nn.Module):
     def __init__(self, model_depth, modality, in_channels, state_dict=None):
         """`state_dict`: torchvision resnet weights (`conv1.weight`, `layer1.0.bn1.weight`, ...; an `fc.*` entry is
         ignored) standing in for the reference's `pretrained=True` download; None -> torchvision's random initialisation."""
@@ -126,11 +112,6 @@ class Resnet(nn.Module):
             weight = conv1.weight.detach().mean(dim=1).unsqueeze(dim=1)
             self.model[0] = _conv(in_channels, 64, 7, 2)
             self.model[0].weight = nn.Parameter(weight)
-        # knobs TBNModel sets on every backbone; they steer the backbone engine, which this backbone does not use
-        self.use_aux_stream = False
-        self.use_branch_streams = False
-        self.stem_wgrad_last = False
-        self._conv_math, self._conv_math_layers = "f32", "3x3"
 
     def _load_torchvision(self, sd):
         names = {"conv1": "model.0", "bn1": "model.1", "layer1": "model.4", "layer2": "model.5", "layer3": "model.6",
@@ -142,41 +123,13 @@ class Resnet(nn.Module):
                 own[names[head] + "." + rest] = v
         self.load_state_dict(own, strict=True)
 
-    # ---- the per-backbone knobs of TBNModel
-    @property
-    def conv_math(self):
-        return self._conv_math
-
-    @conv_math.setter
-    def conv_math(self, value):
-        if value != "f32":
-            raise ValueError(f"Resnet: conv_math {value!r} is not available (the split-bf16 modes cover the BN-Inception "
-                             "engine only); \"f32\" is the only mode")
-        self._conv_math = value
-
-    @property
-    def conv_math_layers(self):
-        return self._conv_math_layers
-
-    @conv_math_layers.setter
-    def conv_math_layers(self, value):
-        if value != "3x3":
-            raise ValueError(f"Resnet: conv_math_layers {value!r} is not available; \"3x3\" (the default) is the only value")
-        self._conv_math_layers = value
-
-    def flip_weights_early(self):
-        """no-op: the operator-level data gradients prepare their weights themselves"""
-
     def forward(self, input):
         """(frames, C, H, W) -> (frames, feature_size), as reference resnet.py:41-44"""
-        if not input.is_cuda:
-            raise TbnHipError("Resnet: input is on the CPU; this backbone only runs on an MI355X via libtbn_hip.so "
-                              "(no CPU fallback)")
+        self._need_gpu(input)
         conv1, bn1 = self.model[0], self.model[1]
-        x = ops_conv.stem_bn_pool(input, conv1.weight, bn1.weight, bn1.bias, _state(conv1, bn1), training=bn1.training,
+        x = ops_conv.stem_bn_pool(input, conv1.weight, bn1.weight, bn1.bias, unit_state(conv1, bn1), training=bn1.training,
                                   who="Resnet")
-        if bn1.training:
-            bn1.num_batches_tracked += 1
+        count_batch(bn1.training, bn1)
         for i in range(4, 8):
             for blk in self.model[i]:
                 x = blk(x)

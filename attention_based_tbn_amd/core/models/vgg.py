@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops, ops_conv
-from ..._lib import TbnHipError
+from .ops_backbone import OpsBackbone, conv_bn_relu, count_batch, unit_state
 
 _STAGE_WIDTHS = (64, 128, 256, 512, 512)
 _STAGE_CONVS = {"11": (1, 1, 2, 2, 2), "16": (2, 2, 3, 3, 3)}       # convolutions in front of each of the five pools
@@ -56,17 +56,7 @@ class _Net(nn.Module):
                                         nn.Linear(4096, 4096), nn.ReLU(inplace=True), nn.Dropout())
 
 
-def _state(conv, bn=None):
-    """the unit's BnState, kept on the conv container so its weight / fold caches live from call to call"""
-    s = conv.__dict__.get("_tbn_state")
-    if s is None:
-        s = conv.__dict__["_tbn_state"] = ops_conv.BnState(1, 1, None, None)
-    if bn is not None:
-        s.running_mean, s.running_var = bn.running_mean, bn.running_var     # (module.to() replaces the buffers)
-    return s
-
-
-class VGG(nn.Module):
+class VGG(OpsBackbone, nn.Module):
     _chunk_frames = None      # tests: force the frames per chunk of the eval / no_grad forward (None: the 2 GiB rule)
 
     def __init__(self, model_type, modality, in_channels, state_dict=None):
@@ -98,36 +88,6 @@ class VGG(nn.Module):
             # RGB filters, unlike the ResNet)
             self.model.features[0] = nn.Conv2d(in_channels, 64, kernel_size=3, stride=1, padding=1)
         self.feature_size = self.model.classifier[3].out_features      # in_features of the removed Linear (vgg.py:33)
-        # knobs TBNModel sets on every backbone; they steer the backbone engine, which this backbone does not use
-        self.use_aux_stream = False
-        self.use_branch_streams = False
-        self.stem_wgrad_last = False
-        self._conv_math, self._conv_math_layers = "f32", "3x3"
-
-    # ---- the per-backbone knobs of TBNModel
-    @property
-    def conv_math(self):
-        return self._conv_math
-
-    @conv_math.setter
-    def conv_math(self, value):
-        if value != "f32":
-            raise ValueError(f"VGG: conv_math {value!r} is not available (the split-bf16 modes cover the BN-Inception "
-                             "engine only); \"f32\" is the only mode")
-        self._conv_math = value
-
-    @property
-    def conv_math_layers(self):
-        return self._conv_math_layers
-
-    @conv_math_layers.setter
-    def conv_math_layers(self, value):
-        if value != "3x3":
-            raise ValueError(f"VGG: conv_math_layers {value!r} is not available; \"3x3\" (the default) is the only value")
-        self._conv_math_layers = value
-
-    def flip_weights_early(self):
-        """no-op: the operator-level data gradients prepare their weights themselves"""
 
     # ---- forward
     def _units(self):
@@ -147,21 +107,17 @@ class VGG(nn.Module):
             if bn is None:
                 # the pool's backward carries this unit's ReLU mask
                 if x is None:
-                    x = ops_conv.first_conv3(frames, conv.weight, conv.bias, state=_state(conv), relu_in_pool=pooled,
+                    x = ops_conv.first_conv3(frames, conv.weight, conv.bias, state=unit_state(conv), relu_in_pool=pooled,
                                              who="VGG")
                 else:
                     x = ops_conv.conv_bias_act(x, conv.weight, conv.bias, 1, 1, relu=True, relu_in_pool=pooled,
-                                               state=_state(conv))
+                                               state=unit_state(conv))
+            elif x is None:
+                x = ops_conv.first_conv3(frames, conv.weight, conv.bias, bn.weight, bn.bias, state=unit_state(conv, bn),
+                                         training=bn.training, who="VGG")
+                count_batch(bn.training, bn)
             else:
-                st = _state(conv, bn)
-                if x is None:
-                    x = ops_conv.first_conv3(frames, conv.weight, conv.bias, bn.weight, bn.bias, state=st,
-                                             training=bn.training, who="VGG")
-                else:
-                    x = ops_conv.conv_bn_act(x, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, 1, 1,
-                                             relu=True, training=bn.training, state=st, bias=conv.bias)
-                if bn.training:
-                    bn.num_batches_tracked += 1
+                x = conv_bn_relu(conv, bn, x, bn.training)
             if pooled:
                 x = ops_conv.maxpool2(x, relu_gate=bn is None)
         return x
@@ -179,9 +135,7 @@ class VGG(nn.Module):
         if input.dim() != 4 or input.shape[2] < _MIN_SIZE or input.shape[3] < _MIN_SIZE:
             raise ValueError(f"VGG: input {tuple(input.shape)} is smaller than {_MIN_SIZE} x {_MIN_SIZE}: the five "
                              "MaxPool2d(2, 2) of the features halve the map five times and would leave nothing")
-        if not input.is_cuda:
-            raise TbnHipError("VGG: input is on the CPU; this backbone only runs on an MI355X via libtbn_hip.so "
-                              "(no CPU fallback)")
+        self._need_gpu(input)
         n, _, h, w = input.shape
         if not self.training and not torch.is_grad_enabled():
             # eval has no cross-frame operation: walking the frames in chunks is exact.  The largest operand of a chunk is

@@ -1,22 +1,24 @@
-"""Operator-level autograd wrappers for conv / BatchNorm networks on NHWC tensors (HIP only -- no CPU fallback).
+"""Operator-level autograd wrappers for conv / BatchNorm networks on NHWC tensors (HIP only -- no CPU fallback): what a
+backbone the engine does not know is composed from (core/models/resnet.py, vgg.py, bn_inception_audio.py).
 
-The BN-Inception backbone is one engine call (core/models/bn_inception.py).  A network the engine does not know -- the
-ResNets of core/models/resnet.py -- is composed here from the stand-alone C-ABI operators instead:
-
-  conv_bn_act     conv (1x1 / 3x3, stride 1 / 2, cin a multiple of 32) + BatchNorm + optional residual + optional ReLU
-  residual_block  a whole BasicBlock / Bottleneck as ONE autograd node: its backward pass lets the identity path and
-                  conv1's data gradient meet in the block input's gradient buffer through the `accumulate` arguments of
-                  tbn_bn_res_bwd / tbn_conv2d_dgrad instead of a separate add
-  stem_bn_pool    the 7x7 / stride 2 / pad 3 stem straight from NCHW frames + BatchNorm + ReLU + MaxPool(3, 2, 1)
-and, for the BN-Inception trunk of core/models/bn_inception_audio.py (whose convs all carry a bias: conv_bn_act(bias=)):
-  audio_stem_bn_pool  the separable 1x3 | 3x1 / stride 2 audio stem + two BatchNorms + ReLU + MaxPool(3, 2, ceil)
-  maxpool3, avgpool3  the 3x3 pools of the inception blocks
-  freq_mean           the mean over the frequency axis alone, beside global_mean
-and, for the VGGs of core/models/vgg.py (no BatchNorm in the plain variants, a 3x3 first layer, 2x2 pools, a 7x7 head):
-  conv_bias_act       conv + bias + optional ReLU without BatchNorm
-  first_conv3         the 3x3 / stride 1 / pad 1 first layer straight from NCHW frames, plain or with BatchNorm
-  maxpool2            MaxPool2d(2, 2), optionally carrying the ReLU mask of the conv in front of it in its backward
-  adaptive_avgpool7_flat  AdaptiveAvgPool2d((7, 7)) + flatten in the NCHW order the classifier's weight expects
+  fused units
+    conv_bn_act         conv (1x1 / 3x3, stride 1 / 2, cin a multiple of 32) [+ bias] + BatchNorm + optional residual +
+                        optional ReLU
+    residual_block      a whole BasicBlock / Bottleneck as ONE autograd node: its backward pass lets the identity path and
+                        conv1's data gradient meet in the block input's gradient buffer through the `accumulate` arguments
+                        of tbn_bn_res_bwd / tbn_conv2d_dgrad instead of a separate add
+    conv_bias_act       conv + bias + optional ReLU without BatchNorm
+  stems and first layers (straight from NCHW frames, no input gradient)
+    stem_bn_pool        7x7 / stride 2 / pad 3 conv + BatchNorm + ReLU + MaxPool(3, 2, 1)
+    audio_stem_bn_pool  the separable 1x3 | 3x1 / stride 2 audio stem + two BatchNorms + ReLU + MaxPool(3, 2, ceil)
+    first_conv3         3x3 / stride 1 / pad 1 conv to 64 channels, plain (bias + ReLU) or with BatchNorm
+  pools
+    maxpool3, avgpool3  the 3x3 pools of the inception blocks
+    maxpool2            MaxPool2d(2, 2), optionally carrying the ReLU mask of the conv in front of it in its backward
+    adaptive_avgpool7_flat  AdaptiveAvgPool2d((7, 7)) + flatten in the NCHW order a classifier's weight expects
+  means
+    global_mean         AdaptiveAvgPool2d(1) + flatten
+    freq_mean           the mean over the frequency axis alone
 
 Training: tbn_conv2d_fwd epilogue 1 (bias-free output + statistics partials), then tbn_bn_fwd_batch (no residual, ReLU,
 at most 1024 channels) or tbn_bn_res_fwd (the join: residual and / or no ReLU and / or more channels).  Eval: running
@@ -55,6 +57,40 @@ def _f32c(t):
     return t if t.dtype == torch.float32 else t.float()
 
 
+def _new(ref, *shape, dtype=torch.float32):
+    return torch.empty(*shape, device=ref.device, dtype=dtype)
+
+
+def _bias_f32(bias):
+    return _f32c(bias.detach()) if bias is not None else None
+
+
+def _zero_bias_grad(ref, c):
+    """a per-channel constant in front of a batch-statistics BatchNorm has exactly zero gradient"""
+    return torch.zeros(c, device=ref.device, dtype=torch.float32)
+
+
+def _rows(stats):
+    """the pointers of the four rows of a (4, c) statistics tensor: batch mean | 1/std | scale | shift"""
+    return tuple(stats[i].data_ptr() for i in range(4))
+
+
+def _wrote_running(state):
+    """the kernels wrote the running buffers behind autograd's back: tell the caches keyed on `_version` (folded_bn)"""
+    if state.running_mean is not None:
+        torch.autograd.graph.increment_version((state.running_mean, state.running_var))
+
+
+def _adopt_state(state, stride, pad, running=None):
+    """a fresh BnState, or the caller's with the geometry (and the running buffers, when given) of this call"""
+    if state is None:
+        return BnState(stride, pad, *(running or (None, None)))
+    state.stride, state.pad = stride, pad
+    if running is not None:
+        state.running_mean, state.running_var = running
+    return state
+
+
 def kernel_weight(weight, cache):
     """an OIHW conv weight in the kernels' [cout][k][k][cin] order.  k = 1 or cin = 1: the same memory, no copy.
     Otherwise a permuted copy kept in `cache` until the parameter changes (`_version`: optimiser steps bump it)."""
@@ -66,7 +102,7 @@ def kernel_weight(weight, cache):
     if cache.get("key") != key:
         buf = cache.get("buf")
         if buf is None or tuple(buf.shape) != (cout, k, k, cin) or buf.device != w.device:
-            buf = cache["buf"] = torch.empty(cout, k, k, cin, device=w.device, dtype=torch.float32)
+            buf = cache["buf"] = _new(w, cout, k, k, cin)
         buf.copy_(w.permute(0, 2, 3, 1))
         cache["key"] = key
     return cache["buf"]
@@ -109,7 +145,7 @@ def _conv_fwd(x, wk, stride, pad, epilogue, ss=None, partial=None, bias=None, fl
     n, h, w, cin = x.shape
     cout, k = wk.shape[0], wk.shape[1]
     oh, ow = _out_size(h, w, k, stride, pad)
-    y = torch.empty(n, oh, ow, cout, device=x.device, dtype=torch.float32)
+    y = _new(x, n, oh, ow, cout)
     call("tbn_conv2d_fwd", ptr(x), cin, ptr(wk), ptr(bias), ptr(y), cout, n, h, w, cin, cout, k, stride, pad, epilogue,
          flags, ss[0].data_ptr() if ss is not None else 0, ss[1].data_ptr() if ss is not None else 0, ptr(partial),
          stream_ptr())
@@ -120,38 +156,42 @@ _BIAS_AT_JOIN = ("{}: a conv bias in front of the BatchNorm of a join (residual,
                  "not implemented: only the tbn_bn_fwd_batch path carries the bias into the running mean")
 
 
+def _bn_fwd_batch(y, partial, nparts, pld, gamma, beta, bias, state, z):
+    """z = relu(bn(y)) with batch statistics from `nparts` rows of (sum, sumsq) partials of pitch `pld` -> the (4, c) stats.
+    A conv `bias` cancels in the batch statistics: y and z do not see it, running_mean takes mean + bias"""
+    c = y.shape[-1]
+    stats = _new(y, 4, c)
+    d = BnFwdDesc()
+    d.y, d.y_ld, d.p, d.c = y.data_ptr(), c, y.numel() // c, c
+    d.partial, d.pld, d.nparts = partial.data_ptr(), pld, nparts
+    d.gamma, d.beta, d.conv_bias = gamma.data_ptr(), beta.data_ptr(), ptr(bias)
+    d.running_mean, d.running_var = ptr(state.running_mean), ptr(state.running_var)
+    d.save_mean, d.save_rstd, d.scale, d.shift = _rows(stats)
+    d.seg[0] = BnSeg(z.data_ptr(), c, 0)
+    d.nseg = 1
+    call("tbn_bn_fwd_batch", C.byref(d), 1, MOMENTUM, EPS, stream_ptr())
+    _wrote_running(state)
+    return stats
+
+
 def _unit_fwd_train(x, wk, gamma, beta, state, res, relu, bias=None):
-    """-> (y, z, stats): bias-free conv output, block output, (4, c) rows batch mean | 1/std | scale | shift.  A conv
-    `bias` cancels in the batch statistics: y and z do not see it, running_mean takes mean + bias"""
+    """-> (y, z, stats): bias-free conv output, block output, (4, c) rows batch mean | 1/std | scale | shift"""
     n, h, w, cin = x.shape
     cout, k = wk.shape[0], wk.shape[1]
     batched = res is None and relu and cout <= 1024
     if bias is not None and not batched:
         raise TbnHipError(_BIAS_AT_JOIN.format("conv_bn_act"))
     tiles = lib().tbn_conv2d_stat_tiles(n, h, w, cin, cout, k, state.stride, state.pad)
-    partial = torch.empty(tiles * 2 * cout, device=x.device, dtype=torch.float32)
+    partial = _new(x, tiles * 2 * cout)
     y = _conv_fwd(x, wk, state.stride, state.pad, 1, partial=partial)
-    p = y.numel() // cout
     z = torch.empty_like(y)
-    stats = torch.empty(4, cout, device=x.device, dtype=torch.float32)
-    rm, rv = state.running_mean, state.running_var
     if batched:
-        d = BnFwdDesc()
-        d.y, d.y_ld, d.p, d.c = y.data_ptr(), cout, p, cout
-        d.partial, d.pld, d.nparts = partial.data_ptr(), cout, tiles
-        d.gamma, d.beta, d.conv_bias = gamma.data_ptr(), beta.data_ptr(), ptr(bias)
-        d.running_mean, d.running_var = ptr(rm), ptr(rv)
-        d.save_mean, d.save_rstd, d.scale, d.shift = (stats[i].data_ptr() for i in range(4))
-        d.seg[0] = BnSeg(z.data_ptr(), cout, 0)
-        d.nseg = 1
-        call("tbn_bn_fwd_batch", C.byref(d), 1, MOMENTUM, EPS, stream_ptr())
-    else:
-        call("tbn_bn_res_fwd", ptr(y), cout, p, cout, ptr(partial), cout, tiles, ptr(gamma), ptr(beta), ptr(rm), ptr(rv),
-             MOMENTUM, EPS, stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(),
-             ptr(res), cout, int(relu), ptr(z), cout, stream_ptr())
-    if rm is not None:
-        # the kernels wrote the buffers behind autograd's back: tell the caches keyed on `_version` (folded_bn)
-        torch.autograd.graph.increment_version((rm, rv))
+        return y, z, _bn_fwd_batch(y, partial, tiles, cout, gamma, beta, bias, state, z)
+    stats = _new(x, 4, cout)
+    call("tbn_bn_res_fwd", ptr(y), cout, y.numel() // cout, cout, ptr(partial), cout, tiles, ptr(gamma), ptr(beta),
+         ptr(state.running_mean), ptr(state.running_var), MOMENTUM, EPS, *_rows(stats), ptr(res), cout, int(relu), ptr(z),
+         cout, stream_ptr())
+    _wrote_running(state)
     return y, z, stats
 
 
@@ -171,23 +211,22 @@ def _bn_bwd(dz, y, z, stats, had_res, relu, dres, need_affine):
     cout = y.shape[-1]
     p = y.numel() // cout
     dy = torch.empty_like(y)
-    dgb = torch.empty(2, cout, device=y.device, dtype=torch.float32) if need_affine else None
+    dgb = _new(y, 2, cout) if need_affine else None
     dg, db = (dgb[0].data_ptr(), dgb[1].data_ptr()) if need_affine else (0, 0)
     if not had_res and relu and cout <= 1024:
-        scratch = torch.empty(lib().tbn_bn_bwd_partial_floats(p, cout) + 3 * cout, device=y.device, dtype=torch.float32)
+        scratch = _new(y, lib().tbn_bn_bwd_partial_floats(p, cout) + 3 * cout)
         d = BnBwdDesc()
         d.dz[0] = BnSeg(dz.data_ptr(), cout, 0)
         d.nseg = 1
         d.y, d.dy, d.y_ld, d.p, d.c = y.data_ptr(), dy.data_ptr(), cout, p, cout
-        d.mean, d.rstd, d.scale, d.shift = (stats[i].data_ptr() for i in range(4))
+        d.mean, d.rstd, d.scale, d.shift = _rows(stats)
         d.partial, d.ext_parts, d.coef = scratch.data_ptr(), 0, scratch.data_ptr() + 4 * (scratch.numel() - 3 * cout)
         d.dgamma, d.dbeta, d.dbias = dg, db, 0
         call("tbn_bn_bwd_batch", C.byref(d), 1, stream_ptr())
     else:
-        ws = torch.empty(lib().tbn_bn_res_bwd_workspace_floats(p, cout), device=y.device, dtype=torch.float32)
-        call("tbn_bn_res_bwd", ptr(dz), cout, ptr(z) if relu else 0, cout, ptr(y), cout, p, cout, stats[0].data_ptr(),
-             stats[1].data_ptr(), stats[2].data_ptr(), int(relu), ptr(dy), cout, ptr(dres), cout, 0, dg, db,
-             ptr(ws), stream_ptr())
+        ws = _new(y, lib().tbn_bn_res_bwd_workspace_floats(p, cout))
+        call("tbn_bn_res_bwd", ptr(dz), cout, ptr(z) if relu else 0, cout, ptr(y), cout, p, cout, *_rows(stats)[:3],
+             int(relu), ptr(dy), cout, ptr(dres), cout, 0, dg, db, ptr(ws), stream_ptr())
     return dy, (dgb[0] if need_affine else None), (dgb[1] if need_affine else None)
 
 
@@ -196,7 +235,7 @@ def _conv_wgrad(dy, x, wk, state):
     cout, k = wk.shape[0], wk.shape[1]
     dwk = torch.empty_like(wk)
     nws = lib().tbn_conv2d_wgrad_workspace_floats(n, h, w, cin, cout, k, state.stride, state.pad)
-    ws = torch.empty(max(nws, 1), device=x.device, dtype=torch.float32)
+    ws = _new(x, max(nws, 1))
     call("tbn_conv2d_wgrad", ptr(dy), cout, ptr(x), cin, ptr(dwk), n, h, w, cin, cout, k, state.stride, state.pad,
          ptr(ws), stream_ptr())
     return _oihw(dwk)
@@ -208,8 +247,8 @@ def _conv_dgrad(dy, wk, x_shape, state, dx=None):
     cout, k = wk.shape[0], wk.shape[1]
     acc = dx is not None
     if dx is None:
-        dx = torch.empty(x_shape, device=dy.device, dtype=torch.float32)
-    ws = torch.empty(wk.numel(), device=dy.device, dtype=torch.float32)
+        dx = _new(dy, x_shape)
+    ws = _new(dy, wk.numel())
     call("tbn_conv2d_dgrad", ptr(dy), cout, ptr(wk), ptr(dx), cin, n, h, w, cin, cout, k, state.stride, state.pad,
          int(acc), ptr(ws), stream_ptr())
     return dx
@@ -217,6 +256,22 @@ def _conv_dgrad(dy, wk, x_shape, state, dx=None):
 
 _EVAL_BACKWARD = ("{}: backward through an eval-mode backbone (running-statistics BN) is not implemented; call .train() "
                   "for fine-tuning or wrap inference in torch.no_grad()")
+_NO_INPUT_GRAD = ("{}: the gradient with respect to the input frames is not implemented (the first conv's data gradient "
+                  "is never formed); detach the input")
+
+
+def _dead_backward(ctx, who, slots, input_grad=True):
+    """the opening of every backward with a BatchNorm in it -> None when the node saved what its backward needs (`ctx.live`),
+    else the all-None result.  `slots`: the needs_input_grad entries that this operator can differentiate; with
+    `input_grad` off (stems, first layers) entry 0, the frames, is not one of them and asking for it is refused."""
+    need = ctx.needs_input_grad
+    if not input_grad and need[0]:
+        raise TbnHipError(_NO_INPUT_GRAD.format(who))
+    if ctx.live:
+        return None
+    if ctx.eval_mode and any(need[i] for i in slots):
+        raise TbnHipError(_EVAL_BACKWARD.format(who))
+    return (None,) * len(need)
 
 
 # ---------------------------------------------------------------------------------------------- one fused unit
@@ -228,7 +283,7 @@ class _ConvBnActFn(torch.autograd.Function):
         wk = kernel_weight(weight, state.wcache)
         _check_conv(x, wk, "conv_bn_act")
         res = _f32c(residual) if residual is not None else None
-        cb = _f32c(bias.detach()) if bias is not None else None
+        cb = _bias_f32(bias)
         ctx.eval_mode = not training
         ctx.live = training and (any(ctx.needs_input_grad[:5]) or ctx.needs_input_grad[8])
         if not training:
@@ -242,18 +297,16 @@ class _ConvBnActFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dz):
         need = ctx.needs_input_grad
-        if not ctx.live:
-            if ctx.eval_mode and (any(need[:5]) or need[8]):
-                raise TbnHipError(_EVAL_BACKWARD.format("conv_bn_act"))
-            return (None,) * 9
+        dead = _dead_backward(ctx, "conv_bn_act", (0, 1, 2, 3, 4, 8))
+        if dead:
+            return dead
         x, wk, y, z, stats = ctx.saved_tensors
         dz = _f32c(dz)
         dres = torch.empty_like(y) if (ctx.had_res and need[4]) else None
         dy, dg, db = _bn_bwd(dz, y, z, stats, ctx.had_res, ctx.relu, dres, need[2] or need[3])
         dw = _conv_wgrad(dy, x, wk, ctx.state) if need[1] else None
         dx = _conv_dgrad(dy, wk, x.shape, ctx.state) if need[0] else None
-        # a per-channel constant in front of a batch-statistics BatchNorm has exactly zero gradient
-        dbias = torch.zeros(y.shape[-1], device=y.device, dtype=torch.float32) if need[8] else None
+        dbias = _zero_bias_grad(y, y.shape[-1]) if need[8] else None
         return dx, dw, dg if need[2] else None, db if need[3] else None, dres, None, None, None, dbias
 
 
@@ -266,10 +319,7 @@ def conv_bn_act(x, weight, gamma, beta, running_mean, running_var, stride, pad, 
     batch statistics -- the output is bit-identical to the call without it, running_mean takes mean + bias, its gradient
     is zeros -- and is only taken where no residual joins (ReLU, at most 1024 channels); in eval it is folded into the
     shift."""
-    if state is None:
-        state = BnState(stride, pad, running_mean, running_var)
-    else:
-        state.stride, state.pad, state.running_mean, state.running_var = stride, pad, running_mean, running_var
+    state = _adopt_state(state, stride, pad, (running_mean, running_var))
     return _ConvBnActFn.apply(x, weight, gamma, beta, residual, state, bool(relu), bool(training), bias)
 
 
@@ -311,10 +361,9 @@ class _ResidualBlockFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         need = ctx.needs_input_grad
-        if not ctx.live:
-            if ctx.eval_mode and (need[0] or any(need[4:])):
-                raise TbnHipError(_EVAL_BACKWARD.format("residual_block"))
-            return (None,) * len(need)
+        dead = _dead_backward(ctx, "residual_block", (0, *range(4, len(need))))
+        if dead:
+            return dead
         saved = list(ctx.saved_tensors)
         states, nmain, has_ds = ctx.states, ctx.nmain, ctx.has_ds
         x = saved.pop(0)
@@ -387,7 +436,7 @@ class _GlobalMeanFn(torch.autograd.Function):
         _need_cuda(x, "freq_mean" if freq_only else "global_mean")
         x = _f32c(x)
         n, h, w, c = x.shape
-        out = torch.empty((n, w, c) if freq_only else (n, c), device=x.device, dtype=torch.float32)
+        out = _new(x, (n, w, c) if freq_only else (n, c))
         for c0 in range(0, c, 1024):
             call("tbn_spatial_mean_fwd", x.data_ptr() + 4 * c0, c, out.data_ptr() + 4 * c0, c, n, h, w, min(1024, c - c0),
                  int(freq_only), stream_ptr())
@@ -398,7 +447,7 @@ class _GlobalMeanFn(torch.autograd.Function):
     def backward(ctx, dout):
         n, h, w, c = ctx.shape
         dout = _f32c(dout)
-        dx = torch.empty(ctx.shape, device=dout.device, dtype=torch.float32)
+        dx = _new(dout, ctx.shape)
         call("tbn_spatial_mean_bwd", ptr(dout), c, ptr(dx), c, n, h, w, c, int(ctx.freq_only), stream_ptr())
         return dx, None
 
@@ -437,9 +486,9 @@ class _MaxPool3Fn(torch.autograd.Function):
         x = _f32c(x)
         n, h, w, c = x.shape
         oh, ow = pool_out_size(h, stride, pad, ceil_mode), pool_out_size(w, stride, pad, ceil_mode)
-        out = torch.empty(n, oh, ow, c, device=x.device, dtype=torch.float32)
+        out = _new(x, n, oh, ow, c)
         live = ctx.needs_input_grad[0]
-        argmax = torch.empty(n, oh, ow, c, device=x.device, dtype=torch.uint8) if live else None
+        argmax = _new(x, n, oh, ow, c, dtype=torch.uint8) if live else None
         call("tbn_maxpool3_fwd", ptr(x), c, ptr(out), c, ptr(argmax), n, h, w, c, oh, ow, stride, pad, stream_ptr())
         if live:
             ctx.geom = (n, h, w, c, oh, ow, stride, pad)
@@ -451,7 +500,7 @@ class _MaxPool3Fn(torch.autograd.Function):
         (argmax,) = ctx.saved_tensors
         n, h, w, c, oh, ow, stride, pad = ctx.geom
         dout = _f32c(dout)
-        dx = torch.empty(n, h, w, c, device=dout.device, dtype=torch.float32)
+        dx = _new(dout, n, h, w, c)
         call("tbn_maxpool3_bwd", ptr(dout), c, ptr(argmax), ptr(dx), c, n, h, w, c, oh, ow, stride, pad, 0, stream_ptr())
         return dx, None, None, None
 
@@ -484,8 +533,27 @@ def avgpool3(x_nhwc):
 
 
 # ---------------------------------------------------------------------------------------------- the stem
-_NO_INPUT_GRAD = ("{}: the gradient with respect to the input frames is not implemented (the first conv's data gradient "
-                  "is never formed); detach the input")
+def _bn_pool_fwd(y, gamma, beta, rm, rv, pooled, argmax, pad):
+    """pooled = MaxPool(3, 2, pad)(relu(bn(y))) with batch statistics, the running buffers rm / rv (may be None) updated
+    -> the (4, c) stats"""
+    n, oh, ow, c = y.shape
+    stats = _new(y, 4, c)
+    bnws = _new(y, lib().tbn_bn_workspace_floats(n * oh * ow, c))
+    call("tbn_bn_relu_maxpool_train_fwd", ptr(y), n, oh, ow, c, ptr(gamma), ptr(beta), ptr(rm), ptr(rv), MOMENTUM, EPS,
+         *_rows(stats), ptr(pooled), c, ptr(argmax), pooled.shape[1], pooled.shape[2], 2, pad, ptr(bnws), stream_ptr())
+    return stats
+
+
+def _bn_pool_bwd(dpooled, argmax, y, stats, pad):
+    """-> (dy, dgb): the gradient of the conv output and the (2, c) rows dgamma | dbeta"""
+    n, oh, ow, c = y.shape
+    dpooled = _f32c(dpooled)
+    dy = torch.empty_like(y)
+    dgb = _new(y, 2, c)
+    bnws = _new(y, lib().tbn_bn_workspace_floats(n * oh * ow, c))
+    call("tbn_bn_relu_maxpool_train_bwd", ptr(dpooled), c, ptr(argmax), ptr(y), n, oh, ow, c, argmax.shape[1],
+         argmax.shape[2], 2, pad, *_rows(stats), ptr(dy), dgb[0].data_ptr(), dgb[1].data_ptr(), ptr(bnws), stream_ptr())
+    return dy, dgb
 
 
 class _StemFn(torch.autograd.Function):
@@ -502,10 +570,10 @@ class _StemFn(torch.autograd.Function):
         st = stream_ptr()
         oh, ow = _out_size(h, w, 7, 2, 3)
         ph, pw = _out_size(oh, ow, 3, 2, 1)           # MaxPool2d(3, 2, 1), ceil_mode off
-        ws = torch.empty(lib().tbn_stem_workspace_floats(cin, h, w, 0, n, cout), device=x.device, dtype=torch.float32)
-        y = torch.empty(n, oh, ow, cout, device=x.device, dtype=torch.float32)
-        pooled = torch.empty(n, ph, pw, cout, device=x.device, dtype=torch.float32)
-        argmax = torch.empty(n, ph, pw, cout, device=x.device, dtype=torch.uint8)
+        ws = _new(x, lib().tbn_stem_workspace_floats(cin, h, w, 0, n, cout))
+        y = _new(x, n, oh, ow, cout)
+        pooled = _new(x, n, ph, pw, cout)
+        argmax = _new(x, n, ph, pw, cout, dtype=torch.uint8)
         ctx.eval_mode = not training
         ctx.live = training and any(ctx.needs_input_grad[1:4])
         ctx.who = who
@@ -516,18 +584,11 @@ class _StemFn(torch.autograd.Function):
             call("tbn_maxpool3_fwd", ptr(y), cout, ptr(pooled), cout, ptr(argmax), n, oh, ow, cout, ph, pw, 2, 1, st)
             return pooled
         # the heuristic picks the tile: statistics rows are per 128 * mt output rows, unwritten rows must read as zero
-        m = n * oh * ow
-        partial = torch.zeros((m + 127) // 128 * 2 * cout, device=x.device, dtype=torch.float32)
+        partial = torch.zeros((n * oh * ow + 127) // 128 * 2 * cout, device=x.device, dtype=torch.float32)
         call("tbn_stem_conv_fwd", ptr(x), ptr(wk), 0, ptr(y), cout, n, h, w, cin, cout, 0, 1, 0, 0, ptr(partial), 0, 0, 0,
              ptr(ws), st)
-        stats = torch.empty(4, cout, device=x.device, dtype=torch.float32)
-        bnws = torch.empty(lib().tbn_bn_workspace_floats(m, cout), device=x.device, dtype=torch.float32)
-        rm, rv = state.running_mean, state.running_var
-        call("tbn_bn_relu_maxpool_train_fwd", ptr(y), n, oh, ow, cout, ptr(gamma), ptr(beta), ptr(rm), ptr(rv), MOMENTUM,
-             EPS, stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), ptr(pooled), cout,
-             ptr(argmax), ph, pw, 2, 1, ptr(bnws), st)
-        if rm is not None:
-            torch.autograd.graph.increment_version((rm, rv))
+        stats = _bn_pool_fwd(y, gamma, beta, state.running_mean, state.running_var, pooled, argmax, 1)
+        _wrote_running(state)
         if ctx.live:
             ctx.save_for_backward(x, y, argmax, stats)
         return pooled
@@ -535,30 +596,18 @@ class _StemFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dpooled):
         need = ctx.needs_input_grad
-        if need[0]:
-            raise TbnHipError(_NO_INPUT_GRAD.format(ctx.who))
-        if not ctx.live:
-            if ctx.eval_mode and any(need[1:4]):
-                raise TbnHipError(_EVAL_BACKWARD.format(ctx.who))
-            return (None,) * 7
+        dead = _dead_backward(ctx, ctx.who, (1, 2, 3), input_grad=False)
+        if dead:
+            return dead
         x, y, argmax, stats = ctx.saved_tensors
         n, cin, h, w = x.shape
-        _, oh, ow, cout = y.shape
-        ph, pw = argmax.shape[1], argmax.shape[2]
-        st = stream_ptr()
-        dpooled = _f32c(dpooled)
-        m = n * oh * ow
-        dy = torch.empty_like(y)
-        dgb = torch.empty(2, cout, device=x.device, dtype=torch.float32)
-        bnws = torch.empty(lib().tbn_bn_workspace_floats(m, cout), device=x.device, dtype=torch.float32)
-        call("tbn_bn_relu_maxpool_train_bwd", ptr(dpooled), cout, ptr(argmax), ptr(y), n, oh, ow, cout, ph, pw, 2, 1,
-             stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), ptr(dy),
-             dgb[0].data_ptr(), dgb[1].data_ptr(), ptr(bnws), st)
+        cout = y.shape[-1]
+        dy, dgb = _bn_pool_bwd(dpooled, argmax, y, stats, 1)
         dw = None
         if need[1]:
-            ws = torch.empty(lib().tbn_stem_workspace_floats(cin, h, w, 0, n, cout), device=x.device, dtype=torch.float32)
-            dwk = torch.empty(cout, 7, 7, cin, device=x.device, dtype=torch.float32)
-            call("tbn_stem_conv_wgrad", ptr(dy), cout, ptr(x), ptr(dwk), n, h, w, cin, cout, 0, 0, 0, ptr(ws), st)
+            ws = _new(x, lib().tbn_stem_workspace_floats(cin, h, w, 0, n, cout))
+            dwk = _new(x, cout, 7, 7, cin)
+            call("tbn_stem_conv_wgrad", ptr(dy), cout, ptr(x), ptr(dwk), n, h, w, cin, cout, 0, 0, 0, ptr(ws), stream_ptr())
             dw = _oihw(dwk)
         return None, dw, dgb[0] if need[2] else None, dgb[1] if need[3] else None, None, None, None
 
@@ -593,8 +642,8 @@ class _AudioStemFn(torch.autograd.Function):
         rv = torch.cat([bns[0].running_var, bns[1].running_var]).float()
         oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
         ph, pw = pool_out_size(oh, 2, 0, True), pool_out_size(ow, 2, 0, True)      # MaxPool2d(3, 2, ceil_mode=True)
-        y = torch.empty(n, oh, ow, 64, device=x.device, dtype=torch.float32)
-        pooled = torch.empty(n, ph, pw, 64, device=x.device, dtype=torch.float32)
+        y = _new(x, n, oh, ow, 64)
+        pooled = _new(x, n, ph, pw, 64)
         ctx.eval_mode = not training
         ctx.live = training and any(ctx.needs_input_grad[1:9])
         if not training:
@@ -603,15 +652,10 @@ class _AudioStemFn(torch.autograd.Function):
             call("tbn_audio_stem_fwd", ptr(x), ptr(wk), 0, ptr(y), 64, n, h, w, 2, 0, ptr(sc), ptr(sh), 0, st)
             call("tbn_maxpool3_fwd", ptr(y), 64, ptr(pooled), 64, 0, n, oh, ow, 64, ph, pw, 2, 0, st)
             return pooled
-        argmax = torch.empty(n, ph, pw, 64, device=x.device, dtype=torch.uint8)
-        partial = torch.empty(lib().tbn_audio_stem_stat_rows(n, h, w) * 128, device=x.device, dtype=torch.float32)
+        argmax = _new(x, n, ph, pw, 64, dtype=torch.uint8)
+        partial = _new(x, lib().tbn_audio_stem_stat_rows(n, h, w) * 128)
         call("tbn_audio_stem_fwd", ptr(x), ptr(wk), 0, ptr(y), 64, n, h, w, 1, 0, 0, 0, ptr(partial), st)
-        m = n * oh * ow
-        stats = torch.empty(4, 64, device=x.device, dtype=torch.float32)
-        bnws = torch.empty(lib().tbn_bn_workspace_floats(m, 64), device=x.device, dtype=torch.float32)
-        call("tbn_bn_relu_maxpool_train_fwd", ptr(y), n, oh, ow, 64, ptr(gamma), ptr(beta), ptr(rm), ptr(rv), MOMENTUM,
-             EPS, stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), ptr(pooled), 64,
-             ptr(argmax), ph, pw, 2, 0, ptr(bnws), st)
+        stats = _bn_pool_fwd(y, gamma, beta, rm, rv, pooled, argmax, 0)
         # y is the bias-free conv output: the reference's BatchNorm sees conv + bias, its batch mean is larger by the bias
         rm += MOMENTUM * bias
         for i, bn in enumerate(bns):       # (copy_ bumps the buffers' `_version` for the caches keyed on it)
@@ -623,35 +667,21 @@ class _AudioStemFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dpooled):
-        who = "audio_stem_bn_pool"
         need = ctx.needs_input_grad
-        if need[0]:
-            raise TbnHipError(_NO_INPUT_GRAD.format(who))
-        if not ctx.live:
-            if ctx.eval_mode and any(need[1:9]):
-                raise TbnHipError(_EVAL_BACKWARD.format(who))
-            return (None,) * 11
+        dead = _dead_backward(ctx, "audio_stem_bn_pool", range(1, 9), input_grad=False)
+        if dead:
+            return dead
         x, y, argmax, stats = ctx.saved_tensors
         n, _, h, w = x.shape
-        _, oh, ow, _ = y.shape
-        ph, pw = argmax.shape[1], argmax.shape[2]
-        st = stream_ptr()
-        dpooled = _f32c(dpooled)
-        dy = torch.empty_like(y)
-        dgb = torch.empty(2, 64, device=x.device, dtype=torch.float32)
-        bnws = torch.empty(lib().tbn_bn_workspace_floats(n * oh * ow, 64), device=x.device, dtype=torch.float32)
-        call("tbn_bn_relu_maxpool_train_bwd", ptr(dpooled), 64, ptr(argmax), ptr(y), n, oh, ow, 64, ph, pw, 2, 0,
-             stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), ptr(dy),
-             dgb[0].data_ptr(), dgb[1].data_ptr(), ptr(bnws), st)
+        dy, dgb = _bn_pool_bwd(dpooled, argmax, y, stats, 0)
         dwa = dwb = None
         if need[1] or need[2]:
-            ws = torch.empty(lib().tbn_audio_stem_wgrad_workspace_floats(n, h, w), device=x.device, dtype=torch.float32)
-            dwk = torch.empty(64, 3, device=x.device, dtype=torch.float32)
-            call("tbn_audio_stem_wgrad", ptr(dy), 64, ptr(x), ptr(dwk), n, h, w, ptr(ws), st)
+            ws = _new(x, lib().tbn_audio_stem_wgrad_workspace_floats(n, h, w))
+            dwk = _new(x, 64, 3)
+            call("tbn_audio_stem_wgrad", ptr(dy), 64, ptr(x), ptr(dwk), n, h, w, ptr(ws), stream_ptr())
             dwa, dwb = dwk[:32].view(32, 1, 3, 1), dwk[32:].view(32, 1, 1, 3)
-        zeros = lambda: torch.zeros(32, device=x.device, dtype=torch.float32)   # a bias in front of a batch-statistics BN
-        return (None, dwa if need[1] else None, dwb if need[2] else None, zeros() if need[3] else None,
-                zeros() if need[4] else None, dgb[0, :32] if need[5] else None, dgb[0, 32:] if need[6] else None,
+        return (None, dwa if need[1] else None, dwb if need[2] else None, _zero_bias_grad(x, 32) if need[3] else None,
+                _zero_bias_grad(x, 32) if need[4] else None, dgb[0, :32] if need[5] else None, dgb[0, 32:] if need[6] else None,
                 dgb[1, :32] if need[7] else None, dgb[1, 32:] if need[8] else None, None, None)
 
 
@@ -678,11 +708,11 @@ def _colsum(g):
     of squares go unused) and tbn_colsum adds those few rows"""
     c = g.shape[-1]
     rows = g.numel() // c
-    out = torch.empty(c, device=g.device, dtype=torch.float32)
+    out = _new(g, c)
     if c > 1024:         # wider than the statistics kernel takes
         call("tbn_colsum", ptr(g), c, ptr(out), rows, c, stream_ptr())
         return out
-    partial = torch.empty(lib().tbn_bn_workspace_floats(rows, c), device=g.device, dtype=torch.float32)
+    partial = _new(g, lib().tbn_bn_workspace_floats(rows, c))
     nparts = C.c_int(0)
     call("tbn_bn_stats_partials", ptr(g), c, rows, c, ptr(partial), C.byref(nparts), stream_ptr())
     call("tbn_colsum", ptr(partial), 2 * c, ptr(out), nparts.value, c, stream_ptr())
@@ -698,7 +728,7 @@ class _ConvBiasActFn(torch.autograd.Function):
         x = _f32c(x)
         wk = kernel_weight(weight, state.wcache)
         _check_conv(x, wk, "conv_bias_act")
-        cb = _f32c(bias.detach()) if bias is not None else None
+        cb = _bias_f32(bias)
         z = _conv_fwd(x, wk, state.stride, state.pad, 0, bias=cb, flags=2 if relu else 0)
         if any(ctx.needs_input_grad[:3]):
             ctx.state, ctx.mask = state, relu and not relu_in_pool
@@ -724,10 +754,7 @@ def conv_bias_act(x, weight, bias, stride, pad, relu=True, relu_in_pool=False, s
     maxpool2(..., relu_gate=True), whose backward applies this unit's ReLU mask -- the backward here then skips its own mask
     pass (the pair costs one pass over the map instead of two).  A frozen weight / bias costs no gradient launch.  `state`
     (a BnState the caller keeps) carries the kernel-layout weight copy from call to call."""
-    if state is None:
-        state = BnState(stride, pad, None, None)
-    else:
-        state.stride, state.pad = stride, pad
+    state = _adopt_state(state, stride, pad)
     return _ConvBiasActFn.apply(x, weight, bias, state, bool(relu), bool(relu and relu_in_pool))
 
 
@@ -744,9 +771,9 @@ class _FirstConv3Fn(torch.autograd.Function):
                               f"weight {tuple(weight.shape)} for input {tuple(x.shape)}")
         n, cin, h, w = x.shape
         wk = kernel_weight(weight, state.wcache)
-        cb = _f32c(bias.detach()) if bias is not None else None
+        cb = _bias_f32(bias)
         st = stream_ptr()
-        y = torch.empty(n, h, w, 64, device=x.device, dtype=torch.float32)
+        y = _new(x, n, h, w, 64)
         ctx.who, ctx.bn, ctx.eval_mode = who, gamma is not None, False
         if gamma is None:
             call("tbn_conv3_first_fwd", ptr(x), ptr(wk), ptr(cb), ptr(y), 64, n, h, w, cin, 64, 0, 2 if relu else 0, 0, 0,
@@ -766,22 +793,10 @@ class _FirstConv3Fn(torch.autograd.Function):
                  ss[1].data_ptr(), 0, st)
             return y
         rows = lib().tbn_conv3_first_stat_rows(n, cin, h, w)
-        partial = torch.empty(rows * 128, device=x.device, dtype=torch.float32)
+        partial = _new(x, rows * 128)
         call("tbn_conv3_first_fwd", ptr(x), ptr(wk), 0, ptr(y), 64, n, h, w, cin, 64, 1, 0, 0, 0, ptr(partial), st)
         z = torch.empty_like(y)
-        stats = torch.empty(4, 64, device=x.device, dtype=torch.float32)
-        rm, rv = state.running_mean, state.running_var
-        d = BnFwdDesc()
-        d.y, d.y_ld, d.p, d.c = y.data_ptr(), 64, n * h * w, 64
-        d.partial, d.pld, d.nparts = partial.data_ptr(), 64, rows
-        d.gamma, d.beta, d.conv_bias = gamma.data_ptr(), beta.data_ptr(), ptr(cb)
-        d.running_mean, d.running_var = ptr(rm), ptr(rv)
-        d.save_mean, d.save_rstd, d.scale, d.shift = (stats[i].data_ptr() for i in range(4))
-        d.seg[0] = BnSeg(z.data_ptr(), 64, 0)
-        d.nseg = 1
-        call("tbn_bn_fwd_batch", C.byref(d), 1, MOMENTUM, EPS, st)
-        if rm is not None:
-            torch.autograd.graph.increment_version((rm, rv))
+        stats = _bn_fwd_batch(y, partial, rows, 64, gamma, beta, cb, state, z)
         if ctx.live:
             ctx.save_for_backward(x, y, z, stats)
         return z
@@ -789,19 +804,15 @@ class _FirstConv3Fn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dz):
         need = ctx.needs_input_grad
-        if need[0]:
-            raise TbnHipError(_NO_INPUT_GRAD.format(ctx.who))
-        if not ctx.live:
-            if ctx.eval_mode and any(need[1:5]):
-                raise TbnHipError(_EVAL_BACKWARD.format(ctx.who))
-            return (None,) * 10
+        dead = _dead_backward(ctx, ctx.who, (1, 2, 3, 4), input_grad=False)
+        if dead:
+            return dead
         dy = _f32c(dz)
         dg = dbeta = db = None
         if ctx.bn:
             x, y, z, stats = ctx.saved_tensors
             dy, dg, dbeta = _bn_bwd(dy, y, z, stats, False, True, None, need[3] or need[4])
-            # a per-channel constant in front of a batch-statistics BatchNorm has exactly zero gradient
-            db = torch.zeros(64, device=x.device, dtype=torch.float32) if need[2] else None
+            db = _zero_bias_grad(x, 64) if need[2] else None
         else:
             x, z = ctx.saved_tensors
             if ctx.mask:
@@ -810,9 +821,8 @@ class _FirstConv3Fn(torch.autograd.Function):
         dw = None
         if need[1]:
             n, cin, h, w = x.shape
-            ws = torch.empty(max(lib().tbn_conv3_first_wgrad_workspace_floats(n, cin, h, w), 1), device=x.device,
-                             dtype=torch.float32)
-            dwk = torch.empty(64, 3, 3, cin, device=x.device, dtype=torch.float32)
+            ws = _new(x, max(lib().tbn_conv3_first_wgrad_workspace_floats(n, cin, h, w), 1))
+            dwk = _new(x, 64, 3, 3, cin)
             call("tbn_conv3_first_wgrad", ptr(dy), 64, ptr(x), ptr(dwk), n, h, w, cin, 64, ptr(ws), stream_ptr())
             dw = _oihw(dwk)
         return (None, dw, db, dg if need[3] else None, dbeta if need[4] else None, None, None, None, None, None)
@@ -838,9 +848,9 @@ class _MaxPool2Fn(torch.autograd.Function):
         _check_pool(x, "maxpool2")
         x = _f32c(x)
         n, h, w, c = x.shape
-        out = torch.empty(n, h // 2, w // 2, c, device=x.device, dtype=torch.float32)
+        out = _new(x, n, h // 2, w // 2, c)
         live = ctx.needs_input_grad[0]
-        argmax = torch.empty(n, h // 2, w // 2, c, device=x.device, dtype=torch.uint8) if live else None
+        argmax = _new(x, n, h // 2, w // 2, c, dtype=torch.uint8) if live else None
         call("tbn_maxpool2_fwd", ptr(x), c, ptr(out), c, ptr(argmax), n, h, w, c, stream_ptr())
         if live:
             ctx.shape = (n, h, w, c)
@@ -852,7 +862,7 @@ class _MaxPool2Fn(torch.autograd.Function):
         argmax, z = ctx.saved_tensors
         n, h, w, c = ctx.shape
         dout = _f32c(dout)
-        dx = torch.empty(n, h, w, c, device=dout.device, dtype=torch.float32)
+        dx = _new(dout, n, h, w, c)
         call("tbn_maxpool2_bwd", ptr(dout), c, ptr(argmax), ptr(z), c, ptr(dx), c, n, h, w, c, 0, stream_ptr())
         return dx, None
 
@@ -870,7 +880,7 @@ class _AdaptiveAvgPool7Fn(torch.autograd.Function):
         _check_pool(x, "adaptive_avgpool7_flat")
         x = _f32c(x)
         n, h, w, c = x.shape
-        out = torch.empty(n, c * 49, device=x.device, dtype=torch.float32)
+        out = _new(x, n, c * 49)
         call("tbn_adaptive_avgpool7_fwd", ptr(x), c, ptr(out), n, h, w, c, stream_ptr())
         ctx.shape = (n, h, w, c)
         return out
@@ -879,7 +889,7 @@ class _AdaptiveAvgPool7Fn(torch.autograd.Function):
     def backward(ctx, dout):
         n, h, w, c = ctx.shape
         dout = _f32c(dout)
-        dx = torch.empty(n, h, w, c, device=dout.device, dtype=torch.float32)
+        dx = _new(dout, n, h, w, c)
         call("tbn_adaptive_avgpool7_bwd", ptr(dout), ptr(dx), c, n, h, w, c, 0, stream_ptr())
         return dx
 
