@@ -114,6 +114,11 @@ class MetricHead(C.Structure):
     _fields_ = [("scores", c_fp), ("scores_ld", c_i), ("classes", c_i), ("target", c_fp), ("conf_mat", c_fp)]
 
 
+class SummaryHead(C.Structure):
+    """include/tbn_hip.h tbn_summary_head"""
+    _fields_ = [("scores", c_fp), ("scores_ld", c_i), ("classes", c_i)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/tbn_hip.h
 SIGNATURES = {
     "tbn_version": (c_i, []),
@@ -258,6 +263,8 @@ SIGNATURES = {
     # reference core/utils/metric.py:50-106,137-157: a batch's hits, confusion matrices and losses in one launch
     "tbn_metric_update": (c_i, [C.POINTER(MetricHead), c_i, c_i, C.POINTER(c_i), c_i, C.POINTER(C.c_void_p), c_i, c_fp,
                                 c_fp, c_fp]),
+    # reference core/tools/vis.py:73-84,153-154: a batch's top-k classes, their softmax scores and attention entropies
+    "tbn_clip_summary": (c_i, [C.POINTER(SummaryHead), c_i, c_i, c_i, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp]),
     "tbn_frames_to_tensor": (c_i, [c_fp] + [c_i] * 16 + [c_fp, c_fp, c_i, c_i, c_fp, c_fp]),
     "tbn_frames_to_tensor_crops": (c_i, [c_fp] + [c_i] * 10 + [C.POINTER(c_i), C.POINTER(c_i)] + [c_i] * 5 +
                                    [c_fp, c_fp, c_i, c_i, c_fp, c_fp]),

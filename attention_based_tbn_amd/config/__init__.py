@@ -149,6 +149,20 @@ def load_config(overrides=None, config_dir=None):
     return _wrap(tree)
 
 
+def load_config_file(path, overrides=None):
+    """One flat YAML tree (what `cfg.pretty()` prints; the reference's `config/config_vis.yaml`, which its
+    `core/tools/vis.py:335` hands to `OmegaConf.load`) merged over the built-in defaults, then `overrides`: the same
+    node type as `load_config`, and a key the file leaves out keeps its default."""
+    with open(path) as f:
+        tree = _yload(f.read()) or {}
+    if not isinstance(tree, dict):
+        raise ValueError(f"load_config_file: {path} does not hold a mapping")
+    merged = _defaults()
+    _merge(merged, tree)
+    apply_overrides(merged, overrides)
+    return _wrap(merged)
+
+
 def get_modality(cfg):
     """reference core/utils/misc.py:7-26 -- fixed RGB, Flow, Audio order."""
     out = []

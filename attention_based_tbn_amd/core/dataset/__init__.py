@@ -8,3 +8,4 @@ from .frames import FrameReader, decode_jpegs, jpeg_geometry  # noqa: F401
 from .dataset import EpicVideoRecord, Video_Dataset, read_wav  # noqa: F401
 from .audio_file import WavInfo, load_audio, wav_info  # noqa: F401
 from .npz_file import NpzMember, load_npz_arrays, npz_chunk_index, npz_member  # noqa: F401
+from .epic_class import EpicClasses  # noqa: F401

@@ -176,7 +176,7 @@ class Video_Dataset(object):
     `transform` is the dictionary `get_transforms` returns: RGB / Flow need a
     `DevicePipeline`; the Audio entry is not called, the spectrograms are born on the device as the fp32 tensor it would
     return.
-    `action_list` (the reference's `EpicClasses` filter) is out of scope and raises."""
+    `action_list` (the reference's `EpicClasses` filter) raises here; `core.tools.vis.create_dataset` applies it."""
 
     def __init__(self, cfg, vid_list, annotation_file, modality=["RGB"], transform=None, mode="train", action_list=None,
                  *, device="cuda", threads=8, entropy="host", audio_cache_bytes=4 << 30, audio_load="host",

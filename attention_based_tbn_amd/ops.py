@@ -583,6 +583,73 @@ def attn_regularisers(w, prior=None, *, prior_kind=None, prior_reduction="batchm
     return (out[0] if kind else None, out[1] if use_contrast else None, out[2] if use_entropy else None, out[3])
 
 
+def clip_summary(scores, k, weights=None, segments=1, out=None, row=0):
+    """What the visualiser's table and figure read off a batch, in one launch and without a host round trip
+    (`tbn_clip_summary`).  scores: {head: (B, C_head) class scores}, 1..4 heads -> (idx, prob, ent):
+      idx  (B, heads, k) int32    the k best classes per head, (score descending, class index ascending); -1 when a row
+                                  runs out of classes that are not NaN
+      prob (B, heads, k) float32  softmax(scores[head][b]) at those classes
+      ent  (B,) float32 or None   with `weights` ((B * segments, T) or (B * segments, 1, T)): the mean over the clip's
+                                  `segments` rows of -sum_t w log(w + 1e-6)
+    `out=(idx_ring, prob_ring, ent_ring)` with `row`: the batch is written at rows row .. row+B-1 of the caller's rings
+    ((N, heads, k) int32 / float32 and (N,) float32 or None, contiguous) and views of those rows are returned.
+    No autograd: the inputs are detached."""
+    from ._lib import SummaryHead
+    keys = list(scores.keys())
+    if not 1 <= len(keys) <= 4:
+        raise TbnHipError(f"clip_summary: {len(keys)} heads (1..4)")
+    heads = (SummaryHead * len(keys))()
+    keep = []
+    for h, key in enumerate(keys):
+        s = scores[key]
+        _need_cuda(s, f"clip_summary scores[{key!r}]")
+        s = s.detach()
+        if s.dtype != torch.float32 or s.dim() != 2 or s.stride(1) != 1 or s.stride(0) < s.shape[1]:
+            s = s.float().reshape(s.shape[0], -1).contiguous()
+        keep.append(s)
+        heads[h] = SummaryHead(ptr(s), s.stride(0), s.shape[1])
+    B, dev = keep[0].shape[0], keep[0].device
+    if any(s.shape[0] != B for s in keep):
+        raise TbnHipError("clip_summary: the heads' scores differ in batch size")
+    k, segments, row = int(k), int(segments), int(row)
+    w, T = None, 0
+    if weights is not None:
+        _need_cuda(weights, "clip_summary weights")
+        w = weights.detach()
+        if w.dim() == 3 and w.shape[1] == 1:
+            w = w[:, 0]
+        if w.dtype != torch.float32 or w.dim() != 2 or w.stride(1) != 1 or w.stride(0) < w.shape[1]:
+            w = w.float().reshape(w.shape[0], -1).contiguous()
+        T = w.shape[1]
+        if segments < 1 or w.shape[0] != B * segments:
+            raise TbnHipError(f"clip_summary: weights of {w.shape[0]} rows for {B} clips of {segments} segments")
+    if out is None:
+        idx = torch.empty((B, len(keys), k), dtype=torch.int32, device=dev)
+        prob = torch.empty((B, len(keys), k), dtype=torch.float32, device=dev)
+        ent = torch.empty((B,), dtype=torch.float32, device=dev) if w is not None else None
+        row = 0
+    else:
+        idx, prob, ent = out
+        for name, ring, dtype in (("idx", idx, torch.int32), ("prob", prob, torch.float32)):
+            _need_cuda(ring, f"clip_summary out {name}")
+            if ring.dtype != dtype or not ring.is_contiguous() or tuple(ring.shape[1:]) != (len(keys), k):
+                raise TbnHipError(f"clip_summary: out {name} must be a contiguous (N, {len(keys)}, {k}) {dtype} tensor")
+        if (ent is None) != (w is None):
+            raise TbnHipError("clip_summary: the entropy ring and the weights go together")
+        if ent is not None:
+            _need_cuda(ent, "clip_summary out ent")
+            if ent.dtype != torch.float32 or ent.dim() != 1 or not ent.is_contiguous() or ent.shape[0] != idx.shape[0]:
+                raise TbnHipError("clip_summary: out ent must be a contiguous (N,) float32 tensor")
+        if row < 0 or row + B > idx.shape[0] or prob.shape[0] != idx.shape[0]:
+            raise TbnHipError(f"clip_summary: rows {row}..{row + B - 1} outside rings of {idx.shape[0]} rows")
+    idx_v, prob_v = idx[row:row + B], prob[row:row + B]
+    ent_v = ent[row:row + B] if ent is not None else None
+    if B > 0:
+        call("tbn_clip_summary", heads, len(keys), B, k, ptr(w), w.stride(0) if w is not None else 0, segments, T,
+             ptr(idx_v), ptr(prob_v), ptr(ent_v), stream_ptr())
+    return idx_v, prob_v, ent_v
+
+
 def dropout_mask(shape, p, training, device):
     if not training or p <= 0:
         return None

@@ -922,6 +922,26 @@ int tbn_metric_update(const tbn_metric_head* heads, int num_heads,      /* 1..4,
                       int* hits_row,    /* device, (num_heads + 1) * num_topk ints, ADDED to; group num_heads = joint */
                       float* loss_row,  /* device, num_losses floats, written */
                       void* stream);
+/* replaces: get_info's five .item() reads per clip and visualize's softmax().topk(5) (core/tools/vis.py:73-84,153-154)
+ * for a whole batch in ONE launch that the host never waits for.  Per clip b and head h:
+ *   top_idx[b][h][0..k)   the k best classes in (score descending, class index ascending) order -- the order of
+ *                         tbn_topk_correct / tbn_metric_update; NaN never ranks; -1 once the rankable classes run out
+ *   top_prob[b][h][0..k)  softmax(scores[b]) at those classes, expf(v - max) / sum; a row that holds NaN or +inf gives
+ *                         NaN throughout (as torch.softmax), a -inf entry 0, a slot with index -1 NaN
+ *   entropy[b]            mean over the rows b*segments .. b*segments+segments-1 of `weights` of
+ *                         -sum_t w * logf(w + 1e-6f); any T >= 1
+ * Every sum is taken in a fixed order, so two calls on the same inputs agree bit for bit.  batch == 0 launches nothing. */
+typedef struct {
+  const float* scores;        /* (batch, classes) fp32, pitch scores_ld >= classes */
+  int scores_ld, classes;
+} tbn_summary_head;
+int tbn_clip_summary(const tbn_summary_head* heads, int num_heads,   /* 1..4, host array, passed by value into the launch */
+                     int batch, int k,                               /* k in 1..8 and <= every head's classes */
+                     const float* weights, int weights_ld,           /* (batch*segments, T) fp32, pitch weights_ld >= T, or NULL */
+                     int segments, int T,                            /* segments >= 1 */
+                     int* top_idx, float* top_prob,                  /* device, (batch, num_heads, k) each, written */
+                     float* entropy,                                 /* device, (batch,), written; NULL iff weights is NULL */
+                     void* stream);
 
 /* ---- on-device visual input pipeline (the step right before the path) ---- */
 /* MultiScaleCrop / Rescale (cv2.resize INTER_LINEAR, 8-bit fixed point) -> CenterCrop / crop -> RandomHorizontalFlip
