@@ -32,12 +32,6 @@ int tbn_env_int(const char* name, int def, int lo, int hi) {
 }
 #endif
 
-#define TBN_TRY(expr)                \
-  do {                               \
-    int rc__ = (expr);               \
-    if (rc__ != TBN_OK) return rc__; \
-  } while (0)
-
 static void conv_geom(ConvP* p, int n, int h, int w, int cin, int cout, int k, int stride, int pad) {
   memset(p, 0, sizeof(*p));
   p->N = n;

@@ -37,11 +37,6 @@ inline bool diag_skip_fin(int bit) {
 #endif
 }
 
-inline int ew_grid(size_t items) {
-  size_t g = (items + 255) / 256;
-  return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------- forward: finalize
@@ -55,23 +50,9 @@ __global__ __launch_bounds__(256) void bn_finalize_multi_kernel(BnFwdBatch b) {
   const int c = blk * TBN_FIN_CH + tid;
   double s1, s2;
   tbn_sum_partials<TBN_FIN_CH>(L.partial, L.pld, L.nparts, blk * TBN_FIN_CH, C, red, &s1, &s2);
-  if (tid < TBN_FIN_CH && c < C) {
-    const double mean = s1 / P;
-    double var = s2 / P - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)b.eps));
-    const float sc = L.gamma[c] * rstd;
-    L.save_mean[c] = (float)mean;
-    L.save_rstd[c] = rstd;
-    L.scale[c] = sc;
-    L.shift[c] = fmaf(-(float)mean, sc, L.beta[c]);
-    if (L.running_mean != nullptr) {
-      const double unb = P > 1 ? var * ((double)P / (double)(P - 1)) : var;
-      const float mean_b = (float)mean + (L.conv_bias != nullptr ? L.conv_bias[c] : 0.f);
-      L.running_mean[c] = (1.f - b.momentum) * L.running_mean[c] + b.momentum * mean_b;
-      L.running_var[c] = (1.f - b.momentum) * L.running_var[c] + b.momentum * (float)unb;
-    }
-  }
+  if (tid < TBN_FIN_CH && c < C)
+    TBN_BN_FWD_FINALIZE(L.gamma, L.beta, L.conv_bias, L.running_mean, L.running_var, b.momentum, b.eps, L.save_mean,
+                        L.save_rstd, L.scale, L.shift);
 }
 
 // ---------------------------------------------------------------- forward: apply z = relu(y*scale+shift)
@@ -88,46 +69,11 @@ __global__ __launch_bounds__(256) void bn_apply_multi_kernel(BnFwdBatch b) {
     tbn_bn_apply_rows(L.y, L.y_ld, L.seg[0].ptr, L.seg[0].ld, L.scale, L.shift, L.C, p0, p1);
     return;
   }
-  const int G = L.C >> 2, RP = 256 / G;
-  const int cg = threadIdx.x % G, rs = threadIdx.x / G;
-  if (rs >= RP) return;
-  const int c = cg * 4;
-  const float4 sc = *reinterpret_cast<const float4*>(L.scale + c);
-  const float4 sh = *reinterpret_cast<const float4*>(L.shift + c);
-  int sg = 0;
-  if (L.nseg > 1 && c >= L.seg[1].col_begin) sg = 1;
-  if (L.nseg > 2 && c >= L.seg[2].col_begin) sg = 2;
-  const float* yp = L.y + (size_t)(p0 + rs) * L.y_ld + c;
-  float* zp = L.seg[sg].ptr + (size_t)(p0 + rs) * L.seg[sg].ld + (c - L.seg[sg].col_begin);
-  const size_t ystep = (size_t)RP * L.y_ld, zstep = (size_t)RP * L.seg[sg].ld;
-  int p = p0 + rs;
-  for (; p + 3 * RP < p1; p += 4 * RP) {
-    float4 v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const float4*>(yp + k * ystep);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float4 z;
-      z.x = fmaxf(fmaf(v[k].x, sc.x, sh.x), 0.f);
-      z.y = fmaxf(fmaf(v[k].y, sc.y, sh.y), 0.f);
-      z.z = fmaxf(fmaf(v[k].z, sc.z, sh.z), 0.f);
-      z.w = fmaxf(fmaf(v[k].w, sc.w, sh.w), 0.f);
-      *reinterpret_cast<float4*>(zp + k * zstep) = z;
-    }
-    yp += 4 * ystep;
-    zp += 4 * zstep;
-  }
-  for (; p < p1; p += RP) {
-    const float4 v = *reinterpret_cast<const float4*>(yp);
-    float4 z;
-    z.x = fmaxf(fmaf(v.x, sc.x, sh.x), 0.f);
-    z.y = fmaxf(fmaf(v.y, sc.y, sh.y), 0.f);
-    z.z = fmaxf(fmaf(v.z, sc.z, sh.z), 0.f);
-    z.w = fmaxf(fmaf(v.w, sc.w, sh.w), 0.f);
-    *reinterpret_cast<float4*>(zp) = z;
-    yp += ystep;
-    zp += zstep;
-  }
+  int c, rs, RP;   // column ranges: each thread writes its own segment, through the same row loop
+  if (!tbn_bn_lane(L.C, c, rs, RP)) return;
+  TBN_SEG_OF(sg, L.seg, L.nseg, c);
+  const Seg& z = L.seg[sg];
+  tbn_bn_apply_lane(L.y, L.y_ld, z.ptr, z.ld, c - z.col_begin, L.scale, L.shift, c, rs, RP, p0, p1);
 }
 
 // rows per workgroup of the apply kernels: 4 .. 16 passes of the row lanes, aiming at ~2048 workgroups per layer
@@ -167,8 +113,7 @@ int tbn_launch_bn_fwd_multi_defer(BnFwdBatch& b, unsigned defer_mask, RiderP* ri
     BnFwdLayer& L = b.l[i];
     TBN_REQUIRE(L.P >= 1 && L.C >= 4 && L.C % 4 == 0 && L.C <= 1024 && L.y_ld % 4 == 0 && L.y_ld >= L.C && L.pld >= L.C &&
                 L.pld % 4 == 0 && L.nparts >= 1 && L.nseg >= 1 && L.nseg <= 3, "bn_fwd_multi: bad P / C / pitch / nparts / nseg");
-    for (int s = 0; s < L.nseg; ++s)
-      TBN_REQUIRE(L.seg[s].ld % 4 == 0 && L.seg[s].col_begin % 4 == 0, "bn_fwd_multi: segment pitch/offset must be x4");
+    TBN_REQUIRE(tbn_segs_x4(L.seg, L.nseg), "bn_fwd_multi: segment pitch/offset must be x4");
     b.fin_blk0[i + 1] = b.fin_blk0[i] + cdiv(L.C, TBN_FIN_CH);
     L.app_rows = apply_rows(L.P, L.C);
     b.app_blk0[i + 1] = b.app_blk0[i] + cdiv(L.P, L.app_rows);
@@ -225,9 +170,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_multi_kernel(BnBwdBatch b) 
   const int p0 = blk * pch, p1 = min(P, p0 + pch);
   float4 s1 = make_float4(0, 0, 0, 0), s2 = s1;
   if (rs < RP) {
-    int sg = 0;
-    if (L.nseg > 1 && c >= L.dz[1].col_begin) sg = 1;
-    if (L.nseg > 2 && c >= L.dz[2].col_begin) sg = 2;
+    TBN_SEG_OF(sg, L.dz, L.nseg, c);
     const float* dzp = L.dz[sg].ptr + (c - L.dz[sg].col_begin);
     const int dld = L.dz[sg].ld;
     const float4 sc = *reinterpret_cast<const float4*>(L.scale + c);
@@ -239,29 +182,12 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_multi_kernel(BnBwdBatch b) 
     for (int p = p0 + rs; p < p1; p += RP) {
       const float4 v = *reinterpret_cast<const float4*>(y + (size_t)p * yld + c);
       const float4 d = *reinterpret_cast<const float4*>(dzp + (size_t)p * dld);
-      const float gx = fmaf(v.x, sc.x, sh.x) > 0.f ? d.x : 0.f;
-      const float gy = fmaf(v.y, sc.y, sh.y) > 0.f ? d.y : 0.f;
-      const float gz = fmaf(v.z, sc.z, sh.z) > 0.f ? d.z : 0.f;
-      const float gw = fmaf(v.w, sc.w, sh.w) > 0.f ? d.w : 0.f;
-      s1.x += gx; s1.y += gy; s1.z += gz; s1.w += gw;
-      s2.x = fmaf(gx, (v.x - mu.x) * rs4.x, s2.x);
-      s2.y = fmaf(gy, (v.y - mu.y) * rs4.y, s2.y);
-      s2.z = fmaf(gz, (v.z - mu.z) * rs4.z, s2.z);
-      s2.w = fmaf(gw, (v.w - mu.w) * rs4.w, s2.w);
+      tbn_bn_sums4(s1, s2, tbn_bn_gate4(v, sc, sh, d), v, mu, rs4);
     }
-    *reinterpret_cast<float4*>(&red[(rs * G + cg) * 4]) = s1;
-    *reinterpret_cast<float4*>(&red[2048 + (rs * G + cg) * 4]) = s2;
+    tbn_bn_red_put(red, rs, G, cg, s1, s2);
   }
   __syncthreads();
-  for (int cc = tid; cc < C; cc += 256) {
-    float a = 0.f, s = 0.f;
-    for (int r = 0; r < RP; ++r) {
-      a += red[r * C + cc];
-      s += red[2048 + r * C + cc];
-    }
-    L.partial[((size_t)blk * 2 + 0) * C + cc] = a;
-    L.partial[((size_t)blk * 2 + 1) * C + cc] = s;
-  }
+  TBN_BN_RED_FOLD(red, RP, C, L.partial, blk, C, 0)
 }
 
 // coef[0][c]=a, coef[1][c]=b, coef[2][c]=cst with dy = a*g + b*y + cst
@@ -275,16 +201,7 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_multi_kernel(BnBwdBatch b
   const int c = blk * TBN_FIN_CH + tid;
   double s1, s2;
   tbn_sum_partials<TBN_FIN_CH>(L.partial, C, L.nparts, blk * TBN_FIN_CH, C, red, &s1, &s2);
-  if (tid < TBN_FIN_CH && c < C) {
-    const double sc = L.scale[c], rs = L.rstd[c], mu = L.mean[c];
-    const double bb = -sc * rs * (s2 / P);
-    L.coef[c] = (float)sc;
-    L.coef[C + c] = (float)bb;
-    L.coef[2 * C + c] = (float)(-sc * (s1 / P) - bb * mu);
-    if (L.dgamma) L.dgamma[c] = (float)s2;
-    if (L.dbeta) L.dbeta[c] = (float)s1;
-    if (L.dbias) L.dbias[c] = 0.f;   // a per-channel constant added before a batch-stat BN has exactly zero gradient
-  }
+  if (tid < TBN_FIN_CH && c < C) TBN_BN_BWD_FINALIZE(L.scale, L.mean, L.rstd, L.coef, L.dgamma, L.dbeta, L.dbias);
 }
 
 // y and dy alias (the engine converts y to dy in place).  Same thread mapping as bn_apply_multi_kernel: per-channel
@@ -298,50 +215,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_multi_kernel(BnBwdBatch b) {
     tbn_bn_bwd_apply_rows(L.dz[0].ptr, L.dz[0].ld, L.y, L.y_ld, L.dy, L.scale, L.shift, L.coef, L.C, p0, p1);
     return;
   }
-  const int C = L.C, G = C >> 2, RP = 256 / G;
-  const int cg = threadIdx.x % G, rs = threadIdx.x / G;
-  if (rs >= RP) return;
-  const int c = cg * 4;
-  int sg = 0;
-  if (L.nseg > 1 && c >= L.dz[1].col_begin) sg = 1;
-  if (L.nseg > 2 && c >= L.dz[2].col_begin) sg = 2;
-  const float4 sc = *reinterpret_cast<const float4*>(L.scale + c);
-  const float4 sh = *reinterpret_cast<const float4*>(L.shift + c);
-  const float4 ca = *reinterpret_cast<const float4*>(L.coef + c);
-  const float4 cb = *reinterpret_cast<const float4*>(L.coef + C + c);
-  const float4 cc = *reinterpret_cast<const float4*>(L.coef + 2 * C + c);
-  const float* dp = L.dz[sg].ptr + (size_t)(p0 + rs) * L.dz[sg].ld + (c - L.dz[sg].col_begin);
-  const float* yp = L.y + (size_t)(p0 + rs) * L.y_ld + c;
-  float* op = L.dy + (size_t)(p0 + rs) * L.y_ld + c;
-  const size_t dstep = (size_t)RP * L.dz[sg].ld, ystep = (size_t)RP * L.y_ld;
-  auto one = [&](const float4 d, const float4 v) {
-    float4 o;
-    o.x = fmaf(ca.x, fmaf(v.x, sc.x, sh.x) > 0.f ? d.x : 0.f, fmaf(cb.x, v.x, cc.x));
-    o.y = fmaf(ca.y, fmaf(v.y, sc.y, sh.y) > 0.f ? d.y : 0.f, fmaf(cb.y, v.y, cc.y));
-    o.z = fmaf(ca.z, fmaf(v.z, sc.z, sh.z) > 0.f ? d.z : 0.f, fmaf(cb.z, v.z, cc.z));
-    o.w = fmaf(ca.w, fmaf(v.w, sc.w, sh.w) > 0.f ? d.w : 0.f, fmaf(cb.w, v.w, cc.w));
-    return o;
-  };
-  int p = p0 + rs;
-  for (; p + 3 * RP < p1; p += 4 * RP) {
-    float4 d[4], v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      d[k] = *reinterpret_cast<const float4*>(dp + k * dstep);
-      v[k] = *reinterpret_cast<const float4*>(yp + k * ystep);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) *reinterpret_cast<float4*>(op + k * ystep) = one(d[k], v[k]);
-    dp += 4 * dstep;
-    yp += 4 * ystep;
-    op += 4 * ystep;
-  }
-  for (; p < p1; p += RP) {
-    *reinterpret_cast<float4*>(op) = one(*reinterpret_cast<const float4*>(dp), *reinterpret_cast<const float4*>(yp));
-    dp += dstep;
-    yp += ystep;
-    op += ystep;
-  }
+  int c, rs, RP;   // column ranges: each thread reads its own segment, through the same row loop
+  if (!tbn_bn_lane(L.C, c, rs, RP)) return;
+  TBN_SEG_OF(sg, L.dz, L.nseg, c);
+  const CSeg& dz = L.dz[sg];
+  tbn_bn_bwd_apply_lane(dz.ptr, dz.ld, c - dz.col_begin, L.y, L.y_ld, L.dy, L.scale, L.shift, L.coef, L.C, c, rs, RP, p0, p1);
 }
 
 int tbn_launch_bn_bwd_multi(BnBwdBatch& b, hipStream_t st) { return tbn_launch_bn_bwd_multi_defer(b, 0u, nullptr, st); }
@@ -354,15 +232,9 @@ int tbn_launch_bn_bwd_multi_defer(BnBwdBatch& b, unsigned defer_mask, RiderP* ri
     BnBwdLayer& L = b.l[i];
     TBN_REQUIRE(L.P >= 1 && L.C >= 4 && L.C % 4 == 0 && L.C <= 1024 && L.y_ld % 4 == 0 && L.y_ld >= L.C && L.ext_parts >= 0 &&
                 L.nseg >= 1 && L.nseg <= 3, "bn_bwd_multi: bad P / C / pitch / ext_parts / nseg");
-    for (int s = 0; s < L.nseg; ++s)
-      TBN_REQUIRE(L.dz[s].ld % 4 == 0 && L.dz[s].col_begin % 4 == 0, "bn_bwd_multi: segment pitch/offset must be x4");
-    {  // same chunking as bn.hip's single-layer launch: rows per workgroup rounded to the row-lane count
-      const int rp = 256 / (L.C / 4);
-      int pch = cdiv(L.P, 512);
-      if (pch < 64) pch = 64;
-      L.pch = cdiv(pch, rp) * rp;
-      L.nparts = cdiv(L.P, L.pch);
-    }
+    TBN_REQUIRE(tbn_segs_x4(L.dz, L.nseg), "bn_bwd_multi: segment pitch/offset must be x4");
+    L.pch = tbn_bn_reduce_chunk(L.P, L.C);
+    L.nparts = cdiv(L.P, L.pch);
     int red_blocks = L.nparts;
     if (L.ext_parts > 0) {   // partials came from the data-gradient epilogue that finished dz: nothing to reduce
       L.nparts = L.ext_parts;

@@ -19,17 +19,12 @@
 #include "tbn_bn_dev.h"
 #include "../../include/tbn_hip.h"
 
-#define TBN_TRY(expr)                \
-  do {                               \
-    int rc__ = (expr);               \
-    if (rc__ != TBN_OK) return rc__; \
-  } while (0)
-
 namespace {
 
 constexpr int kSlice = 1024;   // channels per workgroup of the reduce: red[] below holds 2 x 2048 floats as in bn.hip
 
-// rows per reduce workgroup: the same for every column slice, so that all slices write the same partial rows
+// rows per reduce workgroup: NOT tbn_bn_reduce_chunk -- not rounded to the row lanes, whose count differs between column
+// slices of unequal width, so that all slices write the same partial rows
 inline int res_chunk(int P) {
   const int pch = cdiv(P, 512);
   return pch < 64 ? 64 : pch;
@@ -38,11 +33,6 @@ inline int res_parts(int P) { return cdiv(P, res_chunk(P)); }
 // column slices of at most kSlice channels, balanced in float4 quads
 inline int res_slices(int C) { return cdiv(C, kSlice); }
 inline int res_slice_width(int C) { return cdiv(C / 4, res_slices(C)) * 4; }
-
-inline int ew_grid(size_t items) {
-  const size_t g = (items + 255) / 256;
-  return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
-}
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
@@ -60,22 +50,9 @@ __global__ __launch_bounds__(256) void bn_res_finalize_kernel(const float* __res
   const int c = blockIdx.x * TBN_FIN_CH + tid;
   double s1, s2;
   tbn_sum_partials<TBN_FIN_CH>(partial, pld, nparts, blockIdx.x * TBN_FIN_CH, C, red, &s1, &s2);
-  if (tid < TBN_FIN_CH && c < C) {
-    const double mean = s1 / P;
-    double var = s2 / P - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float sc = gamma[c] * rstd;
-    save_mean[c] = (float)mean;
-    save_rstd[c] = rstd;
-    scale[c] = sc;
-    shift[c] = fmaf(-(float)mean, sc, beta[c]);
-    if (running_mean != nullptr) {
-      const double unb = P > 1 ? var * ((double)P / (double)(P - 1)) : var;
-      running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-      running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unb;
-    }
-  }
+  if (tid < TBN_FIN_CH && c < C)
+    TBN_BN_FWD_FINALIZE(gamma, beta, (const float*)nullptr, running_mean, running_var, momentum, eps, save_mean,
+                        save_rstd, scale, shift);
 }
 
 // ---------------------------------------------------------------- apply: z = act(y*scale + shift + res)
@@ -131,32 +108,13 @@ __global__ __launch_bounds__(256) void bn_res_bwd_reduce_kernel(const float* __r
     for (int p = p0 + rs; p < p1; p += RP) {
       const float4 v = *reinterpret_cast<const float4*>(y + (size_t)p * y_ld + c);
       float4 g = *reinterpret_cast<const float4*>(dz + (size_t)p * dz_ld + c);
-      if (RELU) {
-        const float4 o = *reinterpret_cast<const float4*>(z + (size_t)p * z_ld + c);
-        g.x = o.x > 0.f ? g.x : 0.f;
-        g.y = o.y > 0.f ? g.y : 0.f;
-        g.z = o.z > 0.f ? g.z : 0.f;
-        g.w = o.w > 0.f ? g.w : 0.f;
-      }
-      s1.x += g.x; s1.y += g.y; s1.z += g.z; s1.w += g.w;
-      s2.x = fmaf(g.x, (v.x - mu.x) * rs4.x, s2.x);
-      s2.y = fmaf(g.y, (v.y - mu.y) * rs4.y, s2.y);
-      s2.z = fmaf(g.z, (v.z - mu.z) * rs4.z, s2.z);
-      s2.w = fmaf(g.w, (v.w - mu.w) * rs4.w, s2.w);
+      if (RELU) g = tbn_pos_gate4(*reinterpret_cast<const float4*>(z + (size_t)p * z_ld + c), g);
+      tbn_bn_sums4(s1, s2, g, v, mu, rs4);
     }
-    *reinterpret_cast<float4*>(&red[(rs * G + cg) * 4]) = s1;
-    *reinterpret_cast<float4*>(&red[2048 + (rs * G + cg) * 4]) = s2;
+    tbn_bn_red_put(red, rs, G, cg, s1, s2);
   }
   __syncthreads();
-  for (int cc = tid; cc < Cs; cc += 256) {
-    float a = 0.f, b = 0.f;
-    for (int r = 0; r < RP; ++r) {
-      a += red[r * Cs + cc];
-      b += red[2048 + r * Cs + cc];
-    }
-    partial[((size_t)blockIdx.x * 2 + 0) * C + c0 + cc] = a;
-    partial[((size_t)blockIdx.x * 2 + 1) * C + c0 + cc] = b;
-  }
+  TBN_BN_RED_FOLD(red, RP, Cs, partial, blockIdx.x, C, c0)
 }
 
 // dy = a*g + b*y + cst (coef rows a | b | cst of bn_bwd_finalize_kernel);  dres (+)= g.
@@ -173,13 +131,7 @@ __global__ __launch_bounds__(256) void bn_res_bwd_apply_kernel(const float* dz, 
     const int c = (int)(i - p * (uint32_t)G) * 4;
     float4 g = tbn_ld4<(TBN_BN_NT & 2) != 0>(dz + (size_t)p * dz_ld + c);
     const float4 v = tbn_ld4<(TBN_BN_NT & 2) != 0>(y + (size_t)p * y_ld + c);
-    if (RELU) {
-      const float4 o = tbn_ld4<(TBN_BN_NT & 2) != 0>(z + (size_t)p * z_ld + c);
-      g.x = o.x > 0.f ? g.x : 0.f;
-      g.y = o.y > 0.f ? g.y : 0.f;
-      g.z = o.z > 0.f ? g.z : 0.f;
-      g.w = o.w > 0.f ? g.w : 0.f;
-    }
+    if (RELU) g = tbn_pos_gate4(tbn_ld4<(TBN_BN_NT & 2) != 0>(z + (size_t)p * z_ld + c), g);
     const float4 ca = *reinterpret_cast<const float4*>(coef + c);
     const float4 cb = *reinterpret_cast<const float4*>(coef + C + c);
     const float4 cc = *reinterpret_cast<const float4*>(coef + 2 * C + c);
@@ -192,12 +144,7 @@ __global__ __launch_bounds__(256) void bn_res_bwd_apply_kernel(const float* dz, 
       }
       *reinterpret_cast<float4*>(dr) = r;
     }
-    float4 o;
-    o.x = fmaf(ca.x, g.x, fmaf(cb.x, v.x, cc.x));
-    o.y = fmaf(ca.y, g.y, fmaf(cb.y, v.y, cc.y));
-    o.z = fmaf(ca.z, g.z, fmaf(cb.z, v.z, cc.z));
-    o.w = fmaf(ca.w, g.w, fmaf(cb.w, v.w, cc.w));
-    *reinterpret_cast<float4*>(dy + (size_t)p * dy_ld + c) = o;
+    *reinterpret_cast<float4*>(dy + (size_t)p * dy_ld + c) = tbn_bn_dy4(ca, cb, cc, g, v);
   }
 }
 
@@ -223,7 +170,7 @@ int tbn_bn_res_apply(const float* y, int y_ld, int p, int c, const float* scale,
   if (res != nullptr) TBN_TRY(check_tensor(who, "res", res, res_ld, c));
   TBN_REQUIRE(scale && shift && aligned16(scale) && aligned16(shift), "%s: scale / shift must be 16-byte aligned device pointers", who);
   TBN_REQUIRE(relu == 0 || relu == 1, "%s: relu is 0 or 1", who);
-  const dim3 grid(ew_grid((size_t)p * c / 4)), block(256);
+  const dim3 grid(ew_grid((size_t)p * c / 4, 4096)), block(256);
   const FastDiv dg = make_fastdiv((uint32_t)(c / 4));
   tbn_prof_begin(res ? (relu ? "bn_res_apply_kernel<res,relu>" : "bn_res_apply_kernel<res>")
                      : (relu ? "bn_res_apply_kernel<relu>" : "bn_res_apply_kernel<>"),
@@ -290,7 +237,7 @@ int tbn_bn_res_bwd(const float* dz, int dz_ld, const float* z, int z_ld, const f
   tbn_prof_end(st);
   TBN_CHECK_LAUNCH("bn_res_bwd_reduce");
   TBN_TRY(tbn_launch_bn_bwd_finalize(workspace, parts, p, c, scale, save_mean, save_rstd, coef, dgamma, dbeta, nullptr, st));
-  const dim3 grid(ew_grid((size_t)p * c / 4)), block(256);
+  const dim3 grid(ew_grid((size_t)p * c / 4, 4096)), block(256);
   const FastDiv dg = make_fastdiv((uint32_t)(c / 4));
   const int mode = (relu ? 4 : 0) | (dres != nullptr ? 2 : 0) | (dres != nullptr && accumulate ? 1 : 0);
   tbn_prof_begin(relu ? (dres ? "bn_res_bwd_apply_kernel<relu,dres>" : "bn_res_bwd_apply_kernel<relu>")

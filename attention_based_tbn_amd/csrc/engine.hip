@@ -1020,12 +1020,6 @@ int tbn_backbone_out_shape(const tbn_backbone_plan* P, int* h, int* w, int* c) {
   return TBN_OK;
 }
 
-#define TBN_TRY(expr)            \
-  do {                           \
-    int rc__ = (expr);           \
-    if (rc__ != TBN_OK) return rc__; \
-  } while (0)
-
 }  // extern "C"
 
 namespace {

@@ -11,11 +11,6 @@
 #include "tbn_common.h"
 #include "../../include/tbn_hip.h"
 
-static inline int ew_grid(size_t items) {
-  size_t g = (items + 255) / 256;
-  return (int)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
-}
-
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -840,7 +835,7 @@ extern "C" {
 
 int tbn_dropout_fwd(const float* x, const float* rnd, float p, float* y, float* mask, size_t count, void* stream) {
   TBN_REQUIRE(x && rnd && y && mask && p >= 0.f && p < 1.f, "dropout_fwd: bad argument (p = %g)", (double)p);
-  TBN_KLAUNCH(dropout_fwd_kernel, dim3(ew_grid(count)), dim3(256), 0, (hipStream_t)stream, x, rnd, p, 1.f / (1.f - p), y,
+  TBN_KLAUNCH(dropout_fwd_kernel, dim3(ew_grid(count, 4096)), dim3(256), 0, (hipStream_t)stream, x, rnd, p, 1.f / (1.f - p), y,
               mask, count);
   TBN_CHECK_LAUNCH("dropout_fwd");
   return TBN_OK;
@@ -888,7 +883,7 @@ int tbn_ce_heads_bwd(const float* dscores, int ld, int batch, int num_heads, con
 int tbn_pe_concat_fwd(const float* feat, int feat_ld, const float* pe, float* out, int out_ld, int r, int t, int c,
                       int pe_dim, void* stream) {
   TBN_REQUIRE(out_ld >= c + pe_dim, "pe_concat: out_ld too small");
-  TBN_KLAUNCH(pe_concat_kernel, dim3(ew_grid((size_t)r * t * out_ld)), dim3(256), 0, (hipStream_t)stream, feat,
+  TBN_KLAUNCH(pe_concat_kernel, dim3(ew_grid((size_t)r * t * out_ld, 4096)), dim3(256), 0, (hipStream_t)stream, feat,
                      feat_ld, pe, out, out_ld, r, t, c, pe_dim);
   TBN_CHECK_LAUNCH("pe_concat");
   return TBN_OK;
@@ -979,7 +974,7 @@ int tbn_mha_fwd(const float* q, int q_ld, const float* k, int k_ld, const float*
   TBN_KLAUNCH(mha_fwd_kernel, dim3(r * heads * l), dim3(64), 0, st, q, q_ld, k, k_ld, v, v_ld, drop_mask, ctx, ctx_ld,
               probs, pdrop, l, t, r, e, heads, scale);
   TBN_CHECK_LAUNCH("mha_fwd");
-  TBN_KLAUNCH(mha_head_mean_kernel, dim3(ew_grid((size_t)r * l * t)), dim3(256), 0, st, pdrop, avg_w, r, l * t, heads);
+  TBN_KLAUNCH(mha_head_mean_kernel, dim3(ew_grid((size_t)r * l * t, 4096)), dim3(256), 0, st, pdrop, avg_w, r, l * t, heads);
   TBN_CHECK_LAUNCH("mha_head_mean");
   return TBN_OK;
 }
@@ -1094,37 +1089,37 @@ int tbn_attn_reg_bwd(const float* up, const float* w, int w_ld, const float* pri
 }
 
 int tbn_weighted_sum_fwd(const float* feat, const float* w, float* out, int out_ld, int r, int t, int c, void* stream) {
-  TBN_KLAUNCH(weighted_sum_fwd_kernel, dim3(ew_grid((size_t)r * c)), dim3(256), 0, (hipStream_t)stream, feat, w,
+  TBN_KLAUNCH(weighted_sum_fwd_kernel, dim3(ew_grid((size_t)r * c, 4096)), dim3(256), 0, (hipStream_t)stream, feat, w,
                      out, out_ld, r, t, c);
   TBN_CHECK_LAUNCH("weighted_sum_fwd");
   return TBN_OK;
 }
 int tbn_weighted_sum_bwd(const float* dout, int dout_ld, const float* w, float* dfeat, int r, int t, int c,
                          void* stream) {
-  TBN_KLAUNCH(weighted_sum_bwd_kernel, dim3(ew_grid((size_t)r * t * c)), dim3(256), 0, (hipStream_t)stream,
+  TBN_KLAUNCH(weighted_sum_bwd_kernel, dim3(ew_grid((size_t)r * t * c, 4096)), dim3(256), 0, (hipStream_t)stream,
                      dout, dout_ld, w, dfeat, r, t, c);
   TBN_CHECK_LAUNCH("weighted_sum_bwd");
   return TBN_OK;
 }
 int tbn_segment_mean_fwd(const float* x, float* out, int b, int n, int c, void* stream) {
-  TBN_KLAUNCH(segment_mean_fwd_kernel, dim3(ew_grid((size_t)b * c)), dim3(256), 0, (hipStream_t)stream, x, out,
+  TBN_KLAUNCH(segment_mean_fwd_kernel, dim3(ew_grid((size_t)b * c, 4096)), dim3(256), 0, (hipStream_t)stream, x, out,
                      b, n, c);
   TBN_CHECK_LAUNCH("segment_mean_fwd");
   return TBN_OK;
 }
 int tbn_segment_mean_bwd(const float* dout, float* dx, int b, int n, int c, void* stream) {
-  TBN_KLAUNCH(segment_mean_bwd_kernel, dim3(ew_grid((size_t)b * n * c)), dim3(256), 0, (hipStream_t)stream,
+  TBN_KLAUNCH(segment_mean_bwd_kernel, dim3(ew_grid((size_t)b * n * c, 4096)), dim3(256), 0, (hipStream_t)stream,
                      dout, dx, b, n, c);
   TBN_CHECK_LAUNCH("segment_mean_bwd");
   return TBN_OK;
 }
 int tbn_mul_mask(const float* x, const float* mask, float* y, size_t count, void* stream) {
-  TBN_KLAUNCH(mul_mask_kernel, dim3(ew_grid(count)), dim3(256), 0, (hipStream_t)stream, x, mask, y, count);
+  TBN_KLAUNCH(mul_mask_kernel, dim3(ew_grid(count, 4096)), dim3(256), 0, (hipStream_t)stream, x, mask, y, count);
   TBN_CHECK_LAUNCH("mul_mask");
   return TBN_OK;
 }
 int tbn_relu_mask_bwd(const float* dy, const float* y, const float* mask, float* dx, size_t count, void* stream) {
-  TBN_KLAUNCH(relu_mask_bwd_kernel, dim3(ew_grid(count)), dim3(256), 0, (hipStream_t)stream, dy, y, mask, dx,
+  TBN_KLAUNCH(relu_mask_bwd_kernel, dim3(ew_grid(count, 4096)), dim3(256), 0, (hipStream_t)stream, dy, y, mask, dx,
                      count);
   TBN_CHECK_LAUNCH("relu_mask_bwd");
   return TBN_OK;

@@ -12,54 +12,22 @@
 #include "tbn_kernels.h"
 #include "tbn_pool_dev.h"
 
-static inline int ew_grid(size_t items) {
-  size_t g = (items + 255) / 256;
-  return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
-}
-
-// Stencil kernels re-read their neighbours' rows: workgroups b, b+8, ... share an XCD (and its L2), so the
-// bijective remap hands every XCD a CONTIGUOUS run of workgroup ids -- a row is then fetched into one L2, not
-// into all eight (measured: 3x the algorithmic HBM reads without it).
-__device__ __forceinline__ unsigned xcd_block_id() {
-  const unsigned nb = gridDim.x, bid = blockIdx.x;
-  const unsigned q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7, idx = bid >> 3;
-  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
-}
-
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* __restrict__ in, int in_ld,
                                                           float* __restrict__ out, int out_ld,
                                                           uint8_t* __restrict__ argmax, int N, int H, int W, int C,
                                                           int OH, int OW, int stride, int pad, PixDecode dec) {
   const int G = C >> 2;
   const uint32_t total = (uint32_t)N * OH * OW * G;
-  for (uint32_t i = xcd_block_id() * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+  for (uint32_t i = tbn_xcd_block_id() * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
     int g, ox, oy, n;
     uint32_t opix;
     pix_decode(dec, i, g, ox, oy, n, opix);
     const int y0 = oy * stride - pad, x0 = ox * stride - pad;
-    float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
     // where nothing compares greater than -inf ATen keeps its start index, the first IN-BOUNDS tap: in a padded
     // border window that is not tap 0, and the gather backward finds no owner for a tap outside the map
-    const int k0 = max(-y0, 0) * 3 + max(-x0, 0);
-    int bx = k0, by = k0, bz = k0, bw = k0;
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int s = 0; s < 3; ++s) {
-        const int iy = y0 + r, ix = x0 + s;
-        if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) {
-          const float4 v = *reinterpret_cast<const float4*>(in + ((size_t)(n * H + iy) * W + ix) * in_ld + g * 4);
-          const int k = r * 3 + s;
-          if (v.x > best.x || v.x != v.x) { best.x = v.x; bx = k; }
-          if (v.y > best.y || v.y != v.y) { best.y = v.y; by = k; }
-          if (v.z > best.z || v.z != v.z) { best.z = v.z; bz = k; }
-          if (v.w > best.w || v.w != v.w) { best.w = v.w; bw = k; }
-        }
-      }
+    TBN_MAX3X3(best, b, in, in_ld, n, H, W, y0, x0, g * 4, max(-y0, 0) * 3 + max(-x0, 0), v, );
     *reinterpret_cast<float4*>(out + (size_t)opix * out_ld + g * 4) = best;
-    if (argmax != nullptr)
-      *reinterpret_cast<uint32_t*>(argmax + (size_t)opix * C + g * 4) =
-          (uint32_t)bx | ((uint32_t)by << 8) | ((uint32_t)bz << 16) | ((uint32_t)bw << 24);
+    if (argmax != nullptr) *reinterpret_cast<uint32_t*>(argmax + (size_t)opix * C + g * 4) = tbn_argmax_word(bx, by, bz, bw);
   }
 }
 
@@ -67,7 +35,7 @@ int tbn_launch_maxpool_fwd(const float* in, int in_ld, float* out, int out_ld, u
                            int C, int OH, int OW, int stride, int pad, hipStream_t st) {
   TBN_REQUIRE(C % 4 == 0 && in_ld % 4 == 0 && out_ld % 4 == 0, "maxpool: C / pitches must be multiples of 4");
   TBN_REQUIRE((size_t)N * H * W * (C / 4) < (1ull << 31), "maxpool: too many elements per call");
-  TBN_KLAUNCH(maxpool_fwd_kernel, dim3(ew_grid((size_t)N * OH * OW * C / 4)), dim3(256), 0, st, in, in_ld, out,
+  TBN_KLAUNCH(maxpool_fwd_kernel, dim3(ew_grid((size_t)N * OH * OW * C / 4, 8192)), dim3(256), 0, st, in, in_ld, out,
                      out_ld, argmax, N, H, W, C, OH, OW, stride, pad, make_pixdecode(C / 4, OW, OH));
   TBN_CHECK_LAUNCH("maxpool_fwd");
   return TBN_OK;
@@ -81,66 +49,17 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restric
                                                           PixDecode dec) {
   const int G = C >> 2;
   const uint32_t total = (uint32_t)N * H * W * G;
-  for (uint32_t i = xcd_block_id() * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+  for (uint32_t i = tbn_xcd_block_id() * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
     int g, ix, iy, n;
     uint32_t ipix;
     pix_decode(dec, i, g, ix, iy, n, ipix);
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (stride == 2 && pad == 0) {
-      // the pass-through pools of inception_3c / 4e: branch-free form of the loops below (window i >> 1 with tap
-      // i & 1 and, for even i, window (i >> 1) - 1 with tap 2); all loads are issued together, same summation order
-      const int oyA = iy >> 1, ryA = iy & 1, oxA = ix >> 1, rxA = ix & 1;
-      const bool vy[2] = {oyA < OH, (ryA == 0) && (oyA >= 1)}, vx[2] = {oxA < OW, (rxA == 0) && (oxA >= 1)};
-      const int oy[2] = {vy[0] ? oyA : 0, vy[1] ? oyA - 1 : 0}, ry[2] = {ryA, 2};
-      const int ox[2] = {vx[0] ? oxA : 0, vx[1] ? oxA - 1 : 0}, rx[2] = {rxA, 2};
-      uint32_t am[4];
-      float4 d[4];
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-          const size_t opix = (size_t)(n * OH + oy[a]) * OW + ox[b];
-          am[a * 2 + b] = *reinterpret_cast<const uint32_t*>(argmax + opix * C + g * 4);
-          d[a * 2 + b] = *reinterpret_cast<const float4*>(dout + opix * dout_ld + g * 4);
-        }
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-          const uint32_t k = (uint32_t)(ry[a] * 3 + rx[b]), m = am[a * 2 + b];
-          const bool v = vy[a] && vx[b];
-          if (v && (m & 0xff) == k) acc.x += d[a * 2 + b].x;
-          if (v && ((m >> 8) & 0xff) == k) acc.y += d[a * 2 + b].y;
-          if (v && ((m >> 16) & 0xff) == k) acc.z += d[a * 2 + b].z;
-          if (v && (m >> 24) == k) acc.w += d[a * 2 + b].w;
-        }
+    if (stride == 2 && pad == 0) {   // the pass-through pools of inception_3c / 4e
+      TBN_POOL_GATHER_S2(acc, dout, dout_ld, argmax, C, OH, OW, n, iy, ix, g * 4);
     } else {
-    // windows oy with oy*stride - pad <= iy <= oy*stride - pad + 2
-    const int oy_hi = min(OH - 1, (iy + pad) / stride);
-    const int ox_hi = min(OW - 1, (ix + pad) / stride);
-    for (int oy = oy_hi; oy >= 0; --oy) {
-      const int r = iy - (oy * stride - pad);
-      if (r > 2) break;
-      for (int ox = ox_hi; ox >= 0; --ox) {
-        const int s = ix - (ox * stride - pad);
-        if (s > 2) break;
-        const uint32_t k = (uint32_t)(r * 3 + s);
-        const size_t opix = (size_t)(n * OH + oy) * OW + ox;
-        const uint32_t am = *reinterpret_cast<const uint32_t*>(argmax + opix * C + g * 4);
-        const float4 d = *reinterpret_cast<const float4*>(dout + opix * dout_ld + g * 4);
-        if ((am & 0xff) == k) acc.x += d.x;
-        if (((am >> 8) & 0xff) == k) acc.y += d.y;
-        if (((am >> 16) & 0xff) == k) acc.z += d.z;
-        if ((am >> 24) == k) acc.w += d.w;
-      }
+      TBN_POOL_GATHER_LOOPS(acc, dout, dout_ld, argmax, C, OH, OW, stride, pad, n, iy, ix, g * 4);
     }
-    }
-    float4* o = reinterpret_cast<float4*>(din + (size_t)ipix * din_ld + g * 4);
-    if (accumulate) {
-      const float4 prev = *o;
-      acc.x += prev.x; acc.y += prev.y; acc.z += prev.z; acc.w += prev.w;
-    }
-    *o = acc;
+    TBN_ST4_ACC(din + (size_t)ipix * din_ld + g * 4, acc, accumulate);
   }
 }
 
@@ -150,27 +69,17 @@ __global__ __launch_bounds__(256) void maxpool_bwd2x2_kernel(PoolBlk pb, float* 
                                                              int C, int accumulate, FastDiv divg) {
   const int G = C >> 2;
   const uint32_t total = (uint32_t)NQ * G;
-  for (uint32_t i = xcd_block_id() * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+  for (uint32_t i = tbn_xcd_block_id() * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
     const uint32_t q = fdiv(i, divg);
     const int c = (int)(i - q * (uint32_t)G) * 4;
-    const uint32_t row = fdiv(q, pb.div_bw);
-    const int bx = (int)q - (int)row * pb.BW;
-    const uint32_t n = fdiv(row, pb.div_bh);
-    const int by = (int)row - (int)n * pb.BH;
+    TBN_BLK_DECODE(pb, q, n, by, bx);
     float4 g[4];
-    pooled_grad_2x2(pb, (int)n, by, bx, c, g);
+    pooled_grad_2x2(pb, n, by, bx, c, g);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int iy = 2 * by + (k >> 1), ix = 2 * bx + (k & 1);
-      if (iy < pb.H && ix < pb.W) {
-        float4* o = reinterpret_cast<float4*>(din + ((size_t)((int)n * pb.H + iy) * pb.W + ix) * din_ld + c);
-        float4 acc = g[k];
-        if (accumulate) {
-          const float4 prev = *o;
-          acc.x += prev.x; acc.y += prev.y; acc.z += prev.z; acc.w += prev.w;
-        }
-        *o = acc;
-      }
+      if (iy < pb.H && ix < pb.W)
+        TBN_ST4_ACC(din + ((size_t)(n * pb.H + iy) * pb.W + ix) * din_ld + c, g[k], accumulate);
     }
   }
 }
@@ -181,13 +90,13 @@ int tbn_launch_maxpool_bwd(const float* dout, int dout_ld, const uint8_t* argmax
   TBN_REQUIRE((size_t)N * H * W * (C / 4) < (1ull << 31), "maxpool_bwd: too many elements per call");
   if (stride == 2 && pad == 0) {
     const int NQ = N * ((H + 1) / 2) * ((W + 1) / 2);
-    TBN_KLAUNCH(maxpool_bwd2x2_kernel, dim3(ew_grid((size_t)NQ * C / 4)), dim3(256), 0, st,
+    TBN_KLAUNCH(maxpool_bwd2x2_kernel, dim3(ew_grid((size_t)NQ * C / 4, 8192)), dim3(256), 0, st,
                        make_poolblk(dout, dout_ld, argmax, H, W, OH, OW, C), din, din_ld, NQ, C, accumulate,
                        make_fastdiv((uint32_t)(C / 4)));
     TBN_CHECK_LAUNCH("maxpool_bwd2x2");
     return TBN_OK;
   }
-  TBN_KLAUNCH(maxpool_bwd_kernel, dim3(ew_grid((size_t)N * H * W * C / 4)), dim3(256), 0, st, dout, dout_ld,
+  TBN_KLAUNCH(maxpool_bwd_kernel, dim3(ew_grid((size_t)N * H * W * C / 4, 8192)), dim3(256), 0, st, dout, dout_ld,
                      argmax, din, din_ld, N, H, W, C, OH, OW, stride, pad, accumulate, make_pixdecode(C / 4, W, H));
   TBN_CHECK_LAUNCH("maxpool_bwd");
   return TBN_OK;
@@ -199,7 +108,7 @@ __global__ __launch_bounds__(256) void avgpool3_kernel(const float* __restrict__
                                                        int accumulate, PixDecode dec) {
   const int G = C >> 2;
   const uint32_t total = (uint32_t)N * H * W * G;
-  for (uint32_t i = xcd_block_id() * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+  for (uint32_t i = tbn_xcd_block_id() * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
     int g, x, y, n;
     uint32_t opix;
     pix_decode(dec, i, g, x, y, n, opix);
@@ -216,12 +125,7 @@ __global__ __launch_bounds__(256) void avgpool3_kernel(const float* __restrict__
       }
     const float k = 1.f / 9.f;
     acc.x *= k; acc.y *= k; acc.z *= k; acc.w *= k;
-    float4* o = reinterpret_cast<float4*>(out + (size_t)opix * out_ld + g * 4);
-    if (accumulate) {
-      const float4 prev = *o;
-      acc.x += prev.x; acc.y += prev.y; acc.z += prev.z; acc.w += prev.w;
-    }
-    *o = acc;
+    TBN_ST4_ACC(out + (size_t)opix * out_ld + g * 4, acc, accumulate);
   }
 }
 
@@ -229,7 +133,7 @@ int tbn_launch_avgpool3_fwd(const float* in, int in_ld, float* out, int out_ld, 
                             int accumulate, hipStream_t st) {
   TBN_REQUIRE(C % 4 == 0 && in_ld % 4 == 0 && out_ld % 4 == 0, "avgpool: C / pitches must be multiples of 4");
   TBN_REQUIRE((size_t)N * H * W * (C / 4) < (1ull << 31), "avgpool: too many elements per call");
-  TBN_KLAUNCH(avgpool3_kernel, dim3(ew_grid((size_t)N * H * W * C / 4)), dim3(256), 0, st, in, in_ld, out,
+  TBN_KLAUNCH(avgpool3_kernel, dim3(ew_grid((size_t)N * H * W * C / 4, 8192)), dim3(256), 0, st, in, in_ld, out,
                      out_ld, N, H, W, C, accumulate, make_pixdecode(C / 4, W, H));
   TBN_CHECK_LAUNCH("avgpool3");
   return TBN_OK;
@@ -304,7 +208,7 @@ __global__ __launch_bounds__(256) void spatial_mean_bwd_kernel(const float* __re
 int tbn_launch_spatial_mean_bwd(const float* dout, int dout_ld, float* din, int din_ld, int N, int H, int W, int C,
                                 int freq_only, hipStream_t st) {
   TBN_REQUIRE(C % 4 == 0 && din_ld % 4 == 0 && dout_ld % 4 == 0, "spatial_mean_bwd: bad C / pitches");
-  TBN_KLAUNCH(spatial_mean_bwd_kernel, dim3(ew_grid((size_t)N * H * W * C / 4)), dim3(256), 0, st, dout,
+  TBN_KLAUNCH(spatial_mean_bwd_kernel, dim3(ew_grid((size_t)N * H * W * C / 4, 8192)), dim3(256), 0, st, dout,
                      dout_ld, din, din_ld, N, H, W, C, freq_only);
   TBN_CHECK_LAUNCH("spatial_mean_bwd");
   return TBN_OK;
@@ -359,7 +263,7 @@ __global__ __launch_bounds__(256) void nchw_to_s2d_pad_kernel(const float* __res
 int tbn_launch_nchw_to_s2d_pad(const float* in, float* out, int N, int C, int H, int W, hipStream_t st) {
   TBN_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0, "nchw_to_s2d_pad: empty input");
   const int HP = (H + 1) / 2 + 3, WP = (W + 1) / 2 + 3;
-  const dim3 grid(ew_grid((size_t)N * HP * WP));
+  const dim3 grid(ew_grid((size_t)N * HP * WP, 8192));
   switch (C) {
     case 1: TBN_KLAUNCH(nchw_to_s2d_pad_kernel<1>, grid, dim3(256), 0, st, in, out, N, C, H, W, HP, WP); break;
     case 3: TBN_KLAUNCH(nchw_to_s2d_pad_kernel<3>, grid, dim3(256), 0, st, in, out, N, C, H, W, HP, WP); break;
@@ -426,7 +330,7 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_pad_kernel(const float* __re
 
 int tbn_launch_nchw_to_nhwc_pad(const float* in, float* out, int N, int C, int H, int W, int HP, int WP, hipStream_t st) {
   TBN_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && HP >= H + 3 && WP >= W + 3, "nchw_to_nhwc_pad: bad extents");
-  const dim3 grid(ew_grid((size_t)N * HP * WP));
+  const dim3 grid(ew_grid((size_t)N * HP * WP, 8192));
   if (C == 10)
     TBN_KLAUNCH(nchw_to_nhwc_pad_kernel<10>, grid, dim3(256), 0, st, in, out, N, C, H, W, HP, WP);
   else

@@ -23,6 +23,13 @@ void tbn_set_error(const char* fmt, ...);
   } while (0)
 #define TBN_REQUIRE(cond, ...) TBN_REQUIRE_OR(TBN_ERR_ARG, cond, __VA_ARGS__)
 
+// passes a failed call's status on to the caller
+#define TBN_TRY(expr)                \
+  do {                               \
+    int rc__ = (expr);               \
+    if (rc__ != TBN_OK) return rc__; \
+  } while (0)
+
 #define TBN_CHECK_LAUNCH(what)                                                     \
   do {                                                                             \
     hipError_t e__ = hipGetLastError();                                            \
@@ -68,6 +75,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// workgroups of a grid-stride elementwise launch: one per 256 items, at least 1 and at most `cap` (each site's own)
+static inline int ew_grid(size_t items, size_t cap) {
+  const size_t g = (items + 255) / 256;
+  return (int)(g > cap ? cap : (g < 1 ? 1 : g));
+}
 
 // exact unsigned division by a runtime constant for dividends < 2^31:
 //   q = (m * mul) >> (31 + sh), sh = ceil(log2 d), mul = ceil(2^(31+sh) / d)  (fits 32 bits)

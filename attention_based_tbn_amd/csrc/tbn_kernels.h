@@ -309,6 +309,24 @@ struct FlipTab {
 };
 int tbn_launch_weight_flip_transpose_all(const float* w, float* wt, const FlipTab& tab, hipStream_t st);
 
+// Rows per workgroup of the BN reduce passes (forward statistics, backward sums): about 512 workgroups, at least 64
+// rows each, rounded up to the row-lane count 256 / (C / 4) so that every row lane walks the same number of rows.
+// bn.hip, bn_multi.hip and whoever sizes a partial buffer (tbn_bn_stats_parts, tbn_bn_bwd_pooled_parts) use this one rule.
+static inline int tbn_bn_reduce_chunk(int P, int C) {
+  const int rp = 256 / (C / 4);
+  int pch = cdiv(P, 512);
+  if (pch < 64) pch = 64;
+  return cdiv(pch, rp) * rp;
+}
+static inline int tbn_bn_reduce_parts(int P, int C) { return cdiv(P, tbn_bn_reduce_chunk(P, C)); }
+// pitch and first column of every segment (Seg or CSeg) are multiples of 4: the kernels move float4
+template <class S>
+static inline bool tbn_segs_x4(const S* s, int n) {
+  for (int i = 0; i < n; ++i)
+    if (s[i].ld % 4 != 0 || s[i].col_begin % 4 != 0) return false;
+  return true;
+}
+
 // bn.hip
 int tbn_launch_bn_stats(const float* y, int ld, int P, int C, float* partial, int* nparts, hipStream_t st);
 int tbn_bn_stats_parts(int P, int C);

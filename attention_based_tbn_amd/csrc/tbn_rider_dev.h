@@ -5,19 +5,26 @@
 #pragma once
 #include "tbn_common.h"
 #include "tbn_kernels.h"
+#include "tbn_bn_dev.h"
 
-// z = relu(y * scale + shift) for rows [p0, p1) of a (P, C) column range; z_col0 = channel offset of `z` already applied
-__device__ __forceinline__ void tbn_bn_apply_rows(const float* __restrict__ y, int y_ld, float* __restrict__ z, int z_ld,
-                                                  const float* __restrict__ scale, const float* __restrict__ shift, int C,
-                                                  int p0, int p1) {
-  const int G = C >> 2, RP = 256 / G;
-  const int cg = threadIdx.x % G, rs = threadIdx.x / G;
-  if (rs >= RP) return;
-  const int c = cg * 4;
+// the thread's channel quad c and row lane rs of RP; false for the threads beyond the last whole row lane
+__device__ __forceinline__ bool tbn_bn_lane(int C, int& c, int& rs, int& RP) {
+  const int G = C >> 2;
+  RP = 256 / G;
+  c = (threadIdx.x % G) * 4;
+  rs = threadIdx.x / G;
+  return rs < RP;
+}
+
+// The row loops of ONE row lane: channel quad c of y (and of dy), read from / written to column zc of z (dz).  z, its
+// pitch and zc may differ from thread to thread: the multi-segment tails of bn_multi.hip pass their segment's.
+__device__ __forceinline__ void tbn_bn_apply_lane(const float* __restrict__ y, int y_ld, float* __restrict__ z, int z_ld,
+                                                  int zc, const float* __restrict__ scale,
+                                                  const float* __restrict__ shift, int c, int rs, int RP, int p0, int p1) {
   const float4 sc = *reinterpret_cast<const float4*>(scale + c);
   const float4 sh = *reinterpret_cast<const float4*>(shift + c);
   const float* yp = y + (size_t)(p0 + rs) * y_ld + c;
-  float* zp = z + (size_t)(p0 + rs) * z_ld + c;
+  float* zp = z + (size_t)(p0 + rs) * z_ld + zc;
   const size_t ystep = (size_t)RP * y_ld, zstep = (size_t)RP * z_ld;
   int p = p0 + rs;
   for (; p + 3 * RP < p1; p += 4 * RP) {
@@ -25,56 +32,30 @@ __device__ __forceinline__ void tbn_bn_apply_rows(const float* __restrict__ y, i
 #pragma unroll
     for (int k = 0; k < 4; ++k) v[k] = tbn_ld4<(TBN_BN_NT & 1) != 0>(yp + k * ystep);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float4 o;
-      o.x = fmaxf(fmaf(v[k].x, sc.x, sh.x), 0.f);
-      o.y = fmaxf(fmaf(v[k].y, sc.y, sh.y), 0.f);
-      o.z = fmaxf(fmaf(v[k].z, sc.z, sh.z), 0.f);
-      o.w = fmaxf(fmaf(v[k].w, sc.w, sh.w), 0.f);
-      tbn_st4<(TBN_BN_NT & 4) != 0>(zp + k * zstep, o);
-    }
+    for (int k = 0; k < 4; ++k) tbn_st4<(TBN_BN_NT & 4) != 0>(zp + k * zstep, tbn_bn_relu4(v[k], sc, sh));
     yp += 4 * ystep;
     zp += 4 * zstep;
   }
   for (; p < p1; p += RP) {
-    const float4 v = tbn_ld4<(TBN_BN_NT & 1) != 0>(yp);
-    float4 o;
-    o.x = fmaxf(fmaf(v.x, sc.x, sh.x), 0.f);
-    o.y = fmaxf(fmaf(v.y, sc.y, sh.y), 0.f);
-    o.z = fmaxf(fmaf(v.z, sc.z, sh.z), 0.f);
-    o.w = fmaxf(fmaf(v.w, sc.w, sh.w), 0.f);
-    tbn_st4<(TBN_BN_NT & 4) != 0>(zp, o);
+    tbn_st4<(TBN_BN_NT & 4) != 0>(zp, tbn_bn_relu4(tbn_ld4<(TBN_BN_NT & 1) != 0>(yp), sc, sh));
     yp += ystep;
     zp += zstep;
   }
 }
-
-// dy = a * [y*scale+shift > 0] dz + b * y + c  (coef = a | b | c rows of C floats); dy may alias y
-__device__ __forceinline__ void tbn_bn_bwd_apply_rows(const float* __restrict__ dz, int dz_ld, const float* y, int y_ld,
-                                                      float* dy, const float* __restrict__ scale,
-                                                      const float* __restrict__ shift, const float* __restrict__ coef, int C,
-                                                      int p0, int p1) {
-  const int G = C >> 2, RP = 256 / G;
-  const int cg = threadIdx.x % G, rs = threadIdx.x / G;
-  if (rs >= RP) return;
-  const int c = cg * 4;
+__device__ __forceinline__ void tbn_bn_bwd_apply_lane(const float* __restrict__ dz, int dz_ld, int dc, const float* y,
+                                                      int y_ld, float* dy, const float* __restrict__ scale,
+                                                      const float* __restrict__ shift, const float* __restrict__ coef,
+                                                      int C, int c, int rs, int RP, int p0, int p1) {
   const float4 sc = *reinterpret_cast<const float4*>(scale + c);
   const float4 sh = *reinterpret_cast<const float4*>(shift + c);
   const float4 ca = *reinterpret_cast<const float4*>(coef + c);
   const float4 cb = *reinterpret_cast<const float4*>(coef + C + c);
   const float4 cc = *reinterpret_cast<const float4*>(coef + 2 * C + c);
-  const float* dp = dz + (size_t)(p0 + rs) * dz_ld + c;
+  const float* dp = dz + (size_t)(p0 + rs) * dz_ld + dc;
   const float* yp = y + (size_t)(p0 + rs) * y_ld + c;
   float* op = dy + (size_t)(p0 + rs) * y_ld + c;
   const size_t dstep = (size_t)RP * dz_ld, ystep = (size_t)RP * y_ld;
-  auto one = [&](const float4 d, const float4 v) {
-    float4 o;
-    o.x = fmaf(ca.x, fmaf(v.x, sc.x, sh.x) > 0.f ? d.x : 0.f, fmaf(cb.x, v.x, cc.x));
-    o.y = fmaf(ca.y, fmaf(v.y, sc.y, sh.y) > 0.f ? d.y : 0.f, fmaf(cb.y, v.y, cc.y));
-    o.z = fmaf(ca.z, fmaf(v.z, sc.z, sh.z) > 0.f ? d.z : 0.f, fmaf(cb.z, v.z, cc.z));
-    o.w = fmaf(ca.w, fmaf(v.w, sc.w, sh.w) > 0.f ? d.w : 0.f, fmaf(cb.w, v.w, cc.w));
-    return o;
-  };
+  auto one = [&](const float4 d, const float4 v) { return tbn_bn_gated_dy4(ca, cb, cc, v, sc, sh, d); };
   int p = p0 + rs;
   for (; p + 3 * RP < p1; p += 4 * RP) {
     float4 d[4], v[4];
@@ -95,6 +76,23 @@ __device__ __forceinline__ void tbn_bn_bwd_apply_rows(const float* __restrict__ 
     yp += ystep;
     op += ystep;
   }
+}
+
+// z = relu(y * scale + shift) for rows [p0, p1) of a (P, C) column range; z_col0 = channel offset of `z` already applied
+__device__ __forceinline__ void tbn_bn_apply_rows(const float* __restrict__ y, int y_ld, float* __restrict__ z, int z_ld,
+                                                  const float* __restrict__ scale, const float* __restrict__ shift, int C,
+                                                  int p0, int p1) {
+  int c, rs, RP;
+  if (tbn_bn_lane(C, c, rs, RP)) tbn_bn_apply_lane(y, y_ld, z, z_ld, c, scale, shift, c, rs, RP, p0, p1);
+}
+
+// dy = a * [y*scale+shift > 0] dz + b * y + c  (coef = a | b | c rows of C floats); dy may alias y
+__device__ __forceinline__ void tbn_bn_bwd_apply_rows(const float* __restrict__ dz, int dz_ld, const float* y, int y_ld,
+                                                      float* dy, const float* __restrict__ scale,
+                                                      const float* __restrict__ shift, const float* __restrict__ coef, int C,
+                                                      int p0, int p1) {
+  int c, rs, RP;
+  if (tbn_bn_lane(C, c, rs, RP)) tbn_bn_bwd_apply_lane(dz, dz_ld, c, y, y_ld, dy, scale, shift, coef, C, c, rs, RP, p0, p1);
 }
 
 // one rider workgroup (rb = its index inside the rider's part of the grid)

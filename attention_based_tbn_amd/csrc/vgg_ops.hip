@@ -336,11 +336,6 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const float* __restri
   }
 }
 
-static inline int vgg_ew_grid(size_t items) {
-  const size_t g = (items + 255) / 256;
-  return (int)(g > 8192 ? 8192 : (g < 1 ? 1 : g));
-}
-
 // ---------------------------------------------------------------------------------------------- AdaptiveAvgPool2d((7, 7))
 // PyTorch's windows: bin i of an axis of length L covers [floor(i L / 7), ceil((i + 1) L / 7))
 __device__ __forceinline__ int ap_start(int i, int L) { return (i * L) / 7; }
@@ -499,7 +494,7 @@ int tbn_maxpool2_fwd(const float* in, int in_ld, float* out, int out_ld, uint8_t
               "maxpool2_fwd: in / out must be 16-B aligned, argmax 4-B aligned");
   const int oh = h / 2, ow = w / 2;
   const size_t total = (size_t)n * oh * ow * (c / 4);
-  TBN_KLAUNCH(maxpool2_fwd_kernel, dim3(vgg_ew_grid(total)), dim3(256), 0, (hipStream_t)stream, in, in_ld, out, out_ld,
+  TBN_KLAUNCH(maxpool2_fwd_kernel, dim3(ew_grid(total, 8192)), dim3(256), 0, (hipStream_t)stream, in, in_ld, out, out_ld,
               argmax, h, w, c, oh, ow, (uint32_t)total);
   TBN_CHECK_LAUNCH("maxpool2_fwd");
   return TBN_OK;
@@ -518,7 +513,7 @@ int tbn_maxpool2_bwd(const float* dout, int dout_ld, const uint8_t* argmax, cons
   TBN_REQUIRE((((uintptr_t)dout | (uintptr_t)din | (uintptr_t)z) & 15) == 0 && ((uintptr_t)argmax & 3) == 0,
               "maxpool2_bwd: dout / din / z must be 16-B aligned, argmax 4-B aligned");
   const size_t total = (size_t)n * h * w * (c / 4);
-  TBN_KLAUNCH(maxpool2_bwd_kernel, dim3(vgg_ew_grid(total)), dim3(256), 0, (hipStream_t)stream, dout, dout_ld, argmax, z,
+  TBN_KLAUNCH(maxpool2_bwd_kernel, dim3(ew_grid(total, 8192)), dim3(256), 0, (hipStream_t)stream, dout, dout_ld, argmax, z,
               z_ld, din, din_ld, h, w, c, h / 2, w / 2, accumulate ? 1 : 0, (uint32_t)total);
   TBN_CHECK_LAUNCH("maxpool2_bwd");
   return TBN_OK;

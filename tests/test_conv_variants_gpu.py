@@ -373,3 +373,37 @@ def test_bn_relu_maxpool_fused_fwd_bwd(case):
     call("tbn_bn_relu_maxpool_train_bwd", ptr(dpd), c, ptr(am), ptr(y2), n, h, w, c, oh, ow, s, p, ptr(mean), ptr(rstd),
          ptr(scale), ptr(shift), ptr(y2), ptr(dg), ptr(db), ptr(ws), st())
     assert torch.equal(y2, dy)
+
+
+@pytest.mark.parametrize("c", [8, 64])
+def test_bn_relu_maxpool_bwd_looped_gather_is_the_unfused_pair(c):
+    """the looped gather arms of the fused backward (bn_bwd_reduce_kernel<true> / bn_bwd_apply_kernel<true>, any pool but
+    3x3 / 2 / 0; here 3x3 / 1 / 1 on n = 2, 5 x 5) against the unfused pair on the same arg-max: tbn_maxpool3_bwd into a
+    buffer, then tbn_bn_relu_train_bwd.  Same gather, same chunking of the rows and same summation order, so dy, dgamma
+    and dbeta are bit-equal (the relation the library showed before the gather became one text, and shows after)."""
+    n, h, w, s, p = 2, 5, 5, 1, 1
+    oh, ow, P = h, w, n * h * w
+    y = (torch.randn(n, h, w, c, generator=g(31)) * 2 + 0.5).to(DEV)
+    gamma, beta = (torch.rand(c, generator=g(32)) + 0.5).to(DEV), (torch.randn(c, generator=g(33)) * 0.1).to(DEV)
+    rm, rv = torch.zeros(c, device=DEV), torch.ones(c, device=DEV)
+    dpool = torch.randn(n, oh, ow, c, generator=g(34)).to(DEV)
+    ws = torch.empty(lib().tbn_bn_workspace_floats(P, c), device=DEV)
+    mean, rstd, scale, shift = (torch.empty(c, device=DEV) for _ in range(4))
+    pooled = torch.empty(n, oh, ow, c, device=DEV)
+    am = torch.full((n, oh, ow, c), 255, dtype=torch.uint8, device=DEV)
+    call("tbn_bn_relu_maxpool_train_fwd", ptr(y), n, h, w, c, ptr(gamma), ptr(beta), ptr(rm), ptr(rv), 0.1, 1e-5, ptr(mean),
+         ptr(rstd), ptr(scale), ptr(shift), ptr(pooled), c, ptr(am), oh, ow, s, p, ptr(ws), st())
+    assert int(am.max()) < 9
+    nan = float("nan")
+    dy, dg, db = torch.full((n, h, w, c), nan, device=DEV), torch.full((c,), nan, device=DEV), torch.full((c,), nan, device=DEV)
+    call("tbn_bn_relu_maxpool_train_bwd", ptr(dpool), c, ptr(am), ptr(y), n, h, w, c, oh, ow, s, p, ptr(mean), ptr(rstd),
+         ptr(scale), ptr(shift), ptr(dy), ptr(dg), ptr(db), ptr(ws), st())
+    dz = torch.full((n, h, w, c), nan, device=DEV)
+    call("tbn_maxpool3_bwd", ptr(dpool), c, ptr(am), ptr(dz), c, n, h, w, c, oh, ow, s, p, 0, st())
+    dy2, dg2, db2 = torch.full_like(dy, nan), torch.full_like(dg, nan), torch.full_like(db, nan)
+    call("tbn_bn_relu_train_bwd", ptr(dz), c, ptr(y), P, c, ptr(mean), ptr(rstd), ptr(scale), ptr(shift), ptr(dy2), ptr(dg2),
+         ptr(db2), ptr(ws), st())
+    for name, a, b in (("dy", dy, dy2), ("dgamma", dg, dg2), ("dbeta", db, db2)):
+        assert bool(torch.isfinite(a).all()) and float(a.abs().max()) > 0, name
+        print(name, "max |fused - unfused| =", float((a - b).abs().max()), "of", float(b.abs().max()))
+        assert torch.equal(a, b), name
