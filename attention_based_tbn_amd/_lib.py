@@ -245,6 +245,10 @@ SIGNATURES = {
     "tbn_stft_logpower": (c_i, [c_fp, c_i, c_i, c_fp, c_fp, c_f, c_fp]),
     # reference core/dataset/dataset.py:421-459 (window cut) + :461-510 (stft / logms) in one entry
     "tbn_stft_windows": (c_i, [c_fp, c_fp, c_i, c_i, c_fp, c_fp, c_f, c_i, c_fp, c_fp, c_fp]),
+    # reference core/dataset/dataset.py:461-510 at any data.audio.sampling_rate: window and hop from the rate (:483-484)
+    "tbn_stft_rate_twiddle_floats": (c_sz, [c_i]),
+    "tbn_stft_rate_make_twiddle": (c_i, [c_i, c_fp]),
+    "tbn_stft_rate_windows": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_f, c_i, c_fp, c_fp, c_fp]),
     # reference core/dataset/dataset.py:534-575 (prior_type "loud")
     "tbn_attn_prior_loud": (c_i, [c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp]),
     # reference core/dataset/dataset.py:401-414, preprocessing/create_audio_pickle.py:47-49 (librosa.load): host bank, one launch

@@ -64,18 +64,39 @@ def mel_filterbank(sr=24000, n_fft=511, n_mels=128):
     return (w * (2.0 / (mel_f[2:] - mel_f[:-2]))[:, None]).astype(np.float32)
 
 
+N_FFT = 511
+
+
+def stft_geometry(sampling_rate, window_ms=10, step_ms=5):
+    """(win, hop) in samples as the reference derives them from the rate (dataset.py:483-484): Python 3's
+    `int(round(...))`, ties to even -- 22 050 Hz -> (220, 110), 44 100 Hz -> (441, 220), 24 000 Hz -> (240, 120)."""
+    return int(round(window_ms * sampling_rate / 1e3)), int(round(step_ms * sampling_rate / 1e3))
+
+
 class Spectrogram:
-    """`spec = Spectrogram()(wave)`: wave (nseg, L) float32 on the GPU -> (nseg, 256, 1+(L-1)//120) log-power STFT
+    """`spec = Spectrogram()(wave)`: wave (nseg, L) float32 on the GPU -> (nseg, 256, 1+(L-1)//hop) log-power STFT
     (`spec_type="stft"`, the reference default) or (nseg, 128, T) log-mel dB (`spec_type="logms"`,
     dataset.py:496-506: librosa melspectrogram + power_to_db(ref=max) of each segment; two HIP launches, no torch op).
-    `AudioSegments` (audio.py) runs the same code on windows of untrimmed clips through `windows()`."""
+    `AudioSegments` (audio.py) runs the same code on windows of untrimmed clips through `windows()`.
+    Window and hop follow `sampling_rate` (`stft_geometry`; n_fft stays 511, 256 bins): (240, 120) at 24 kHz runs the
+    kernel written for it, every other geometry with 8 <= win <= 511 and 1 <= hop <= win the general one
+    (`tbn_stft_rate_windows`)."""
 
-    def __init__(self, eps=1e-6, spec_type="stft", sampling_rate=24000):
+    _force_general = False    # tests / scripts/stft_rates_profile.py: send (240, 120) through the general kernel too
+
+    def __init__(self, eps=1e-6, spec_type="stft", sampling_rate=24000, window_ms=10, step_ms=5):
         if spec_type not in ("stft", "logms"):
             raise Exception("Unknown spectrogram representation")
         self.eps = eps
         self.spec_type = spec_type
         self.sampling_rate = sampling_rate
+        self.win_length, self.hop_length = stft_geometry(sampling_rate, window_ms, step_ms)
+        if self.win_length > N_FFT:     # librosa (reference dataset.py:487-495) refuses win_length > n_fft
+            raise ValueError(f"Spectrogram: sampling rate {sampling_rate} Hz gives a window of {self.win_length} samples "
+                             f"({window_ms} ms), longer than n_fft = {N_FFT}")
+        if self.win_length < 8 or not 1 <= self.hop_length <= self.win_length:
+            raise ValueError(f"Spectrogram: sampling rate {sampling_rate} Hz gives window {self.win_length} / hop "
+                             f"{self.hop_length} samples; the STFT kernel takes 8 <= window <= {N_FFT}, 1 <= hop <= window")
         self._tw = {}
         self._mel = {}
 
@@ -84,13 +105,18 @@ class Spectrogram:
             self._mel[device] = torch.from_numpy(mel_filterbank(self.sampling_rate)).to(device)
         return self._mel[device]
 
-    def _twiddle(self, device):
-        if device not in self._tw:
-            n = lib().tbn_stft_twiddle_floats()
-            host = np.empty(n, dtype=np.float32)
-            call("tbn_stft_make_twiddle", host.ctypes.data)
-            self._tw[device] = torch.from_numpy(host).to(device)
-        return self._tw[device]
+    def _twiddle(self, device, general=False):
+        """one table per (device, win); the general kernel's table of win = 240 has the same bits as the other one"""
+        key = (device, self.win_length)
+        if key not in self._tw:
+            if general:
+                host = np.empty(lib().tbn_stft_rate_twiddle_floats(self.win_length), dtype=np.float32)
+                call("tbn_stft_rate_make_twiddle", self.win_length, host.ctypes.data)
+            else:
+                host = np.empty(lib().tbn_stft_twiddle_floats(), dtype=np.float32)
+                call("tbn_stft_make_twiddle", host.ctypes.data)
+            self._tw[key] = torch.from_numpy(host).to(device)
+        return self._tw[key]
 
     def windows(self, window_ptrs, wave, nseg, L, device):
         """The one code path of both representations: nseg windows of L samples, either `window_ptrs` (a device int64
@@ -98,7 +124,9 @@ class Spectrogram:
         (nseg, L) batch -- the special case "window s starts at wave + s * L"."""
         if L < 1:       # librosa 0.7.2 (reference dataset.py:487-495) rejects it too: "Input is too short" (util.frame)
             raise ValueError("Spectrogram: empty audio sample (a clip shorter than audio_length, reference dataset.py:441-451)")
-        W = 1 + (L - 1) // 120
+        W = 1 + (L - 1) // self.hop_length
+        if self._force_general or (self.win_length, self.hop_length) != (240, 120):
+            return self._windows_general(window_ptrs, wave, nseg, L, W, device)
         tw = self._twiddle(device)
         if self.spec_type == "stft":
             spec = torch.empty(nseg, 256, W, device=device, dtype=torch.float32)
@@ -115,6 +143,17 @@ class Spectrogram:
         spec = torch.empty(nseg, 128, W, device=device, dtype=torch.float32)
         call("tbn_stft_windows", ptr(window_ptrs), ptr(wave), nseg, L, ptr(tw), ptr(spec), 0.0, STFT_LOGMEL,
              ptr(self._melbasis(device)), ptr(power), stream_ptr())
+        return spec
+
+    def _windows_general(self, window_ptrs, wave, nseg, L, W, device):
+        """`windows` for any (win, hop): one entry for both representations and both ways to name the windows"""
+        tw = self._twiddle(device, general=True)
+        stft = self.spec_type == "stft"
+        spec = torch.empty(nseg, 256 if stft else 128, W, device=device, dtype=torch.float32)
+        power = None if stft else torch.empty(nseg, 256, W, device=device, dtype=torch.float32)
+        call("tbn_stft_rate_windows", ptr(window_ptrs), ptr(wave), nseg, L, self.win_length, self.hop_length, ptr(tw),
+             ptr(spec), float(self.eps) if stft else 0.0, STFT_LOGPOWER if stft else STFT_LOGMEL,
+             0 if stft else ptr(self._melbasis(device)), ptr(power), stream_ptr())
         return spec
 
     def __call__(self, wave):

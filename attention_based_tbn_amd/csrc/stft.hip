@@ -28,6 +28,11 @@
 // The rest of the audio data layer lives here too (reference dataset.py:421-575): the audio window cut inside the launch
 // (tbn_stft_windows: a table of window addresses instead of a staged batch), the log-mel representation (the same kernel
 // writing |X|^2 + mel_db_kernel) and the "loud" attention prior (attn_prior_loud_kernel).
+//
+// Everything above is the geometry of data.audio.sampling_rate = 24000: window 240, hop 120.  The reference derives both from
+// the rate (dataset.py:483-484: 10 ms and 5 ms, rounded); at any other rate stft_rate_kernel below does the same contraction
+// with window, hop and tap-group count at run time (tbn_stft_rate_windows), feeding the same epilogue, mel and prior kernels.
+// The 24 kHz kernel is untouched and stays the path of (240, 120).
 #include <cmath>
 #include <cstring>
 
@@ -210,6 +215,132 @@ __global__ __launch_bounds__(256) void stft_logpower_kernel(const float* __restr
   stft_store<POWER>(spec + (size_t)seg * STFT_BINS * W, W, b0, t0, lrow, lhalf, eps, a);
 }
 
+// ---- the STFT at any sampling rate (reference dataset.py:483-495: win = round(10 ms * rate), hop = round(5 ms * rate)) ----
+// The same contraction, [256 bins x 8 * KG taps] . [taps x frames], with the geometry at run time: tap j of frame t reads
+// sample t * hop - win / 2 + j, KG = ceil(win / 8) tap groups (up to 64; the table's taps from `win` to 8 * KG are exact
+// zeros), the same workgroup (64 frames x 128 bins, 4 waves), twiddle layout, k permutation and epilogue as above.  What
+// the 24 kHz kernel takes from its constants is decided here per launch:
+//   * the staged span, (64 - 1) * hop + 8 * KG samples from s0 = t0 * hop - win / 2 (up to 128 KB: dynamic LDS), is loaded
+//     in 16-B groups that start at multiples of 4 SAMPLES, whatever s0 is: a group is then wholly in front of sample 0
+//     (out of range as a whole: zeros, which is right) or wholly behind it -- one that straddled sample 0 would lose its
+//     real samples.  Sample s goes to LDS position x = s - s0, so frame f starts at f * hop whatever s0 mod 4 is: one
+//     ds_write_b128 per group when s0 is a multiple of 4 and hop % 4 == 0, four ds_write_b32 otherwise.  Every position
+//     of the span is written (zeros in front of the first and behind the last sample), so no fragment read meets a word
+//     that was never staged (0 * NaN);
+//   * ALIGNED (hop % 4 == 0: 8, 16, 24, 32, 44.1, 48 kHz): a lane's 4 taps are one 16-B aligned ds_read_b128.  Each hop
+//     row gets `pad` = 4 floats behind it when hop / 4 is even -- position x lives at x + pad * (x / hop) -- so the lane
+//     stride hop + pad is an odd number of 16-B slots (16 distinct slots per 16-lane group; hop 120 -> the 124 above);
+//   * any other hop (22.05 kHz: 110, 11.025 kHz: 55): frames start off the 16-B grid, where a ds_read_b128 is replayed
+//     at 64 cycles per instruction -- four ds_read_b32 per fragment instead, on the unpadded span (8 per tap group and
+//     wave against its 16 MFMAs = 1024 MFMA cycles);
+//   * a 3-slot twiddle ring like the one above, with the prefetch index clamped to the last group instead of wrapping,
+//     whole trips of 3 groups without a branch and the 0 .. 2 groups left over behind them.
+#define STFT_RATE_D 3
+
+template <bool ALIGNED>
+__device__ __forceinline__ int stft_rate_pos(int x, int pad, unsigned rcp) {   // rcp = floor(2^32 / hop) + 1: x / hop is
+  return ALIGNED ? x + pad * (int)__umulhi((unsigned)x, rcp) : x;              // exact for x * hop < 2^32
+}
+
+template <bool ALIGNED>
+__device__ __forceinline__ float4 stft_rate_taps(const float* __restrict__ fr, int i) {
+  if (ALIGNED) return *reinterpret_cast<const float4*>(&fr[i]);
+  return make_float4(fr[i], fr[i + 1], fr[i + 2], fr[i + 3]);
+}
+
+template <bool POWER, bool ALIGNED>
+__global__ __launch_bounds__(256) void stft_rate_kernel(const float* __restrict__ wave, const float* const* __restrict__ windows,
+                                                        int len, int W, int half, int hop, int KG, int pad, unsigned rcp,
+                                                        const float* __restrict__ tw, float* __restrict__ spec, float eps) {
+  extern __shared__ __attribute__((aligned(16))) float fr_dyn[];
+  constexpr int D = STFT_RATE_D;
+  constexpr unsigned kGroupBytes = STFT_BINS * 8 * 4;
+  const int seg = blockIdx.y, t0 = blockIdx.x * STFT_FR;
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lrow = lane & 31, lhalf = lane >> 5;
+  const int b0 = blockIdx.z * 128 + wv * 32;
+  const unsigned lane_byte = (unsigned)((b0 + lrow) * 2 + lhalf) * 16u;   // [part][kg][b0 + lrow][4 * lhalf]
+  const unsigned part_bytes = (unsigned)KG * kGroupBytes;
+  StftRing<D> tr;
+#pragma unroll
+  for (int d = 0; d + 1 < D; ++d) {
+    const unsigned kn = (unsigned)min(d, KG - 1) * kGroupBytes;
+    tr.c[d] = stft_tw_load(tw, kn, lane_byte);
+    tr.s[d] = stft_tw_load(tw, kn + part_bytes, lane_byte);
+  }
+  const int span = (STFT_FR - 1) * hop + 8 * KG;
+  {
+    const stft_i32x4 rs = stft_segment_buffer(wave, windows, seg, len);
+    const int s0 = t0 * hop - half;        // first staged sample; a0 <= s0: the multiple of 4 its 16-B group starts at
+    const int a0 = s0 & ~3, d0 = s0 - a0;
+    const int ngroups = (d0 + span + 3) >> 2;
+    const bool whole = ALIGNED && d0 == 0; // then span % 4 == 0 too, and no group straddles a hop row
+    // four loads in flight per thread; a group behind the span is loaded (the range check makes that safe) and dropped
+#pragma unroll 1
+    for (int i0 = tid; i0 < ngroups; i0 += 4 * 256) {
+      f32x4 v[4];
+      // unsigned byte offset: in front of sample 0 it is >= 2^31, out of range like everything behind sample len - 1
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = stft_buffer_load_f32x4(rs, (int)((unsigned)(a0 + 4 * (i0 + 256 * q)) * 4u), 0, 0);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int x = 4 * (i0 + 256 * q) - d0;
+        if (whole) {
+          if (x < span)
+            *reinterpret_cast<float4*>(&fr_dyn[stft_rate_pos<ALIGNED>(x, pad, rcp)]) = make_float4(v[q].x, v[q].y, v[q].z, v[q].w);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (x + e >= 0 && x + e < span) fr_dyn[stft_rate_pos<ALIGNED>(x + e, pad, rcp)] = v[q][e];
+        }
+      }
+    }
+  }
+  StftAcc a;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) a.re0[e] = a.im0[e] = a.re1[e] = a.im1[e] = 0.f;
+  __syncthreads();
+  // frame lrow (and lrow + 32), tap j at position lrow * hop + j: base + j + pad * (j / hop)
+  const int base = lrow * (hop + pad), second = 32 * (hop + pad), j0 = 4 * lhalf;
+  float4 fa[D], fb[D];
+  fa[0] = stft_rate_taps<ALIGNED>(fr_dyn, base + j0);
+  fb[0] = stft_rate_taps<ALIGNED>(fr_dyn, base + second + j0);
+  // group k from ring slot j = k % D: prefetch the twiddles of group k + D - 1 and the taps of group k + 1 (both clamped to
+  // the last group: a re-read, no branch), then the 16 MFMAs
+#define STFT_RATE_GROUP(j, k)                                                                \
+  {                                                                                          \
+    const unsigned kn = (unsigned)min((k) + D - 1, KG - 1) * kGroupBytes;                     \
+    tr.c[((j) + D - 1) % D] = stft_tw_load(tw, kn, lane_byte);                                \
+    tr.s[((j) + D - 1) % D] = stft_tw_load(tw, kn + part_bytes, lane_byte);                   \
+    const int jn = 8 * min((k) + 1, KG - 1) + j0;                                             \
+    const int fo = base + stft_rate_pos<ALIGNED>(jn, pad, rcp);                               \
+    fa[((j) + 1) % D] = stft_rate_taps<ALIGNED>(fr_dyn, fo);                                  \
+    fb[((j) + 1) % D] = stft_rate_taps<ALIGNED>(fr_dyn, fo + second);                         \
+    __builtin_amdgcn_sched_barrier(0);                                                       \
+    const float4 c = tr.c[j], s = tr.s[j], f0 = fa[j], f1 = fb[j];                            \
+    STFT_RATE_STEP(x) STFT_RATE_STEP(y) STFT_RATE_STEP(z) STFT_RATE_STEP(w)                   \
+    __builtin_amdgcn_sched_barrier(0);                                                       \
+  }
+#define STFT_RATE_STEP(q)                                                     \
+  a.re0 = __builtin_amdgcn_mfma_f32_32x32x2f32(c.q, f0.q, a.re0, 0, 0, 0);     \
+  a.im0 = __builtin_amdgcn_mfma_f32_32x32x2f32(s.q, f0.q, a.im0, 0, 0, 0);     \
+  a.re1 = __builtin_amdgcn_mfma_f32_32x32x2f32(c.q, f1.q, a.re1, 0, 0, 0);     \
+  a.im1 = __builtin_amdgcn_mfma_f32_32x32x2f32(s.q, f1.q, a.im1, 0, 0, 0);
+  int kg = 0;
+#pragma unroll 1
+  for (; kg + D <= KG; kg += D) {
+    STFT_RATE_GROUP(0, kg)
+    STFT_RATE_GROUP(1, kg + 1)
+    STFT_RATE_GROUP(2, kg + 2)
+  }
+  if (kg < KG) STFT_RATE_GROUP(0, kg)
+  if (kg + 1 < KG) STFT_RATE_GROUP(1, kg + 1)
+#undef STFT_RATE_STEP
+#undef STFT_RATE_GROUP
+  static_assert(D == 3, "the trips above are written out for a ring of 3");
+  stft_store<POWER>(spec + (size_t)seg * STFT_BINS * W, W, b0, t0, lrow, lhalf, eps, a);
+}
+
 // ---- log-mel (spec_type "logms", reference dataset.py:496-506: librosa melspectrogram + power_to_db(ref = np.max)) ----
 // One workgroup per segment: mel = basis (128 x 256) . power (256 x W), then 10 log10(max(amin, mel)) - 10 log10(max(amin,
 // max mel)), floored at -80 dB.  A Slaney mel filter is a triangle over a handful of neighbouring bins (about 500 non-zeros
@@ -358,7 +489,88 @@ static int stft_launch(const char* what, const float* wave, const float* const* 
   return TBN_OK;
 }
 
+// the accepted geometry of the rate kernel (librosa refuses win_length > n_fft = 511; tap groups of 8 need win >= 8)
+static inline bool stft_rate_geometry_ok(int win, int hop) { return win >= 8 && win <= 511 && hop >= 1 && hop <= win; }
+
+template <bool POWER, bool ALIGNED>
+static int stft_rate_launch_as(const float* wave, const float* const* windows, int nseg, int len, int W, int win, int hop,
+                               const float* twiddle, float* spec, float eps, hipStream_t st) {
+  const int KG = cdiv(win, 8), pad = ALIGNED && (hop / 4) % 2 == 0 ? 4 : 0;
+  const unsigned rcp = ALIGNED ? (unsigned)((1ull << 32) / (unsigned)hop) + 1u : 0u;
+  // LDS floats: the last position of the span + 1 (stft_rate_pos), whole 16-B groups
+  const int span = (STFT_FR - 1) * hop + 8 * KG;
+  const size_t lds = (size_t)((span + pad * ((span - 1) / hop) + 3) & ~3) * sizeof(float);
+  TBN_REQUIRE(lds <= TBN_DYN_LDS_MAX, "stft_rate_windows: window %d / hop %d needs %zu bytes of LDS", win, hop, lds);
+  static size_t allowed = TBN_DYN_LDS_DEFAULT;
+  const int rc = tbn_raise_dyn_lds((const void*)stft_rate_kernel<POWER, ALIGNED>, lds, allowed, "stft_rate_windows");
+  if (rc != TBN_OK) return rc;
+  const dim3 grid(cdiv(W, STFT_FR), nseg, 2);
+  tbn_prof_begin(POWER ? "stft_rate_kernel<power>" : "stft_rate_kernel<log>", 4.0 * STFT_BINS * win * (double)W * nseg, st);
+  TBN_LAUNCH((stft_rate_kernel<POWER, ALIGNED>), grid, dim3(256), lds, st, wave, windows, len, W, win / 2, hop, KG, pad, rcp,
+             twiddle, spec, eps);
+  tbn_prof_end(st);
+  TBN_CHECK_LAUNCH("stft_rate_windows");
+  return TBN_OK;
+}
+
+template <bool POWER>
+static int stft_rate_launch(const float* wave, const float* const* windows, int nseg, int len, int win, int hop,
+                            const float* twiddle, float* spec, float eps, hipStream_t st) {
+  const int W = 1 + (len - 1) / hop;
+  // 32-bit byte offsets inside a segment's samples and inside its 256 x W spectrogram
+  TBN_REQUIRE(nseg <= 65535 && (size_t)len * 4 < (1ull << 31) && (size_t)STFT_BINS * W * 4 < (1ull << 31),
+              "stft_rate_windows: too many segments / too long a waveform per call");
+  return hop % 4 == 0 ? stft_rate_launch_as<POWER, true>(wave, windows, nseg, len, W, win, hop, twiddle, spec, eps, st)
+                      : stft_rate_launch_as<POWER, false>(wave, windows, nseg, len, W, win, hop, twiddle, spec, eps, st);
+}
+
 extern "C" {
+
+size_t tbn_stft_rate_twiddle_floats(int win) {
+  return win >= 8 && win <= 511 ? (size_t)2 * cdiv(win, 8) * STFT_BINS * 8 : 0;
+}
+
+int tbn_stft_rate_make_twiddle(int win, float* host) {
+  TBN_REQUIRE(host != nullptr, "stft_rate_make_twiddle: null buffer");
+  TBN_REQUIRE(win >= 8 && win <= 511, "stft_rate_make_twiddle: window %d outside 8 .. 511 (n_fft = 511)", win);
+  const double pi = 3.14159265358979323846;
+  const int lpad = (511 - win) / 2;
+  const size_t part = (size_t)cdiv(win, 8) * STFT_BINS * 8;
+  memset(host, 0, 2 * part * sizeof(float));     // the taps win .. 8 * ceil(win / 8) - 1
+  for (int j = 0; j < win; ++j) {
+    const double h = 0.5 - 0.5 * cos(2.0 * pi * j / (double)win);
+    for (int k = 0; k < STFT_BINS; ++k) {
+      const long m = ((long)(j + lpad) * k) % 511;  // exact phase reduction
+      const double a = 2.0 * pi * (double)m / 511.0;
+      const size_t idx = ((size_t)(j / 8) * STFT_BINS + k) * 8 + (j % 8);
+      host[idx] = (float)(h * cos(a));
+      host[part + idx] = (float)(-h * sin(a));
+    }
+  }
+  return TBN_OK;
+}
+
+int tbn_stft_rate_windows(const float* const* window_ptrs, const float* wave, int nseg, int len, int win, int hop,
+                          const float* twiddle, float* out, float eps, int mode, const float* mel_basis, float* power,
+                          void* stream) {
+  TBN_REQUIRE((window_ptrs != nullptr) != (wave != nullptr),
+              "stft_rate_windows: give a window table or a contiguous batch, not both");
+  TBN_REQUIRE(twiddle && out && nseg > 0 && len > 0, "stft_rate_windows: bad argument");
+  TBN_REQUIRE(stft_rate_geometry_ok(win, hop), "stft_rate_windows: window %d / hop %d outside 8 <= window <= 511, 1 <= hop <= window",
+              win, hop);
+  TBN_REQUIRE(mode == TBN_STFT_LOGPOWER || mode == TBN_STFT_LOGMEL, "stft_rate_windows: unknown mode %d", mode);
+  hipStream_t st = (hipStream_t)stream;
+  if (mode == TBN_STFT_LOGPOWER) return stft_rate_launch<false>(wave, window_ptrs, nseg, len, win, hop, twiddle, out, eps, st);
+  TBN_REQUIRE(mel_basis && power && power != out, "stft_rate_windows: the log-mel mode needs the mel basis and a power workspace");
+  const int W = 1 + (len - 1) / hop;
+  const int rc = stft_rate_launch<true>(wave, window_ptrs, nseg, len, win, hop, twiddle, power, 0.f, st);
+  if (rc != TBN_OK) return rc;
+  tbn_prof_begin("mel_db_kernel", 0.0, st);
+  TBN_LAUNCH(mel_db_kernel, dim3(nseg), dim3(MEL_THREADS), 0, st, (const float*)power, mel_basis, W, out);
+  tbn_prof_end(st);
+  TBN_CHECK_LAUNCH("stft_rate_windows (mel)");
+  return TBN_OK;
+}
 
 size_t tbn_stft_twiddle_floats(void) { return (size_t)2 * STFT_KG * STFT_BINS * 8; }
 

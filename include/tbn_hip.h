@@ -808,6 +808,24 @@ int tbn_stft_logpower(const float* wave, int nseg, int len, const float* twiddle
 #define TBN_STFT_LOGMEL 1
 int tbn_stft_windows(const float* const* window_ptrs, const float* wave, int nseg, int len, const float* twiddle,
                      float* out, float eps, int mode, const float* mel_basis, float* power, void* stream);
+/* The STFT at any sampling rate (reference core/dataset/dataset.py:461-510: window = int(round(10 ms * rate)), hop =
+ * int(round(5 ms * rate)), n_fft = 511 at every rate): periodic Hann(win) centred in the 511 taps (lpad = (511 - win) / 2),
+ * the signal zero-padded by 255 on both sides, so tap j of frame t reads sample t * hop - win / 2 + j, and
+ * W = 1 + (len - 1) / hop.  8 <= win <= 511 (librosa refuses win_length > n_fft), 1 <= hop <= win; anything else is
+ * TBN_ERR_ARG before any launch.  A kernel of its own: tbn_stft_logpower / tbn_stft_windows stay the (240, 120) path.
+ *   tbn_stft_rate_twiddle_floats(win)  2 * ceil(win / 8) * 256 * 8 floats (0 outside the domain);
+ *   tbn_stft_rate_make_twiddle(win, host_buffer)  host, fp64 -> fp32, phase ((j + lpad) * k) mod 511 reduced in integers,
+ *     layout [cos | -sin][tap / 8][bin][tap % 8] with the taps rounded up to whole groups of 8, the padding taps exact
+ *     zeros; win = 240 gives tbn_stft_make_twiddle's table bit for bit;
+ *   tbn_stft_rate_windows  the contract of tbn_stft_windows (a window table or a contiguous batch, both modes, the same
+ *     mel / dB kernel) with `twiddle` = the table of `win` on the device.  The profiler counts stft_rate_kernel<log|power>
+ *     (4 * 256 * win * W * nseg FLOP) and mel_db_kernel.  Samples that are not finite propagate into a frame from up to 7
+ *     taps behind its window (the tap groups are whole groups of 8; their twiddles are zero). */
+size_t tbn_stft_rate_twiddle_floats(int win);
+int tbn_stft_rate_make_twiddle(int win, float* host_buffer);
+int tbn_stft_rate_windows(const float* const* window_ptrs, const float* wave, int nseg, int len, int win, int hop,
+                          const float* twiddle, float* out, float eps, int mode, const float* mel_basis, float* power,
+                          void* stream);
 /* prior_type "loud" of reference core/dataset/dataset.py:534-575 (`_get_attn_weights`) for nseg spectrograms (nseg, F, W) on
  * the device, one launch, one wave per segment: the maxima of the W / T full blocks of T frames over all F rows (a partial
  * last block is ignored), their arg-max `loc` (ties: the highest block index), then out (nseg, T) = the Gaussian `gauss`
