@@ -109,6 +109,17 @@ class DeflateMember(C.Structure):
                 ("skip", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class PngGeometry(C.Structure):
+    """include/tbn_hip.h tbn_png_geometry"""
+    _fields_ = [("width", c_i), ("height", c_i), ("colour_type", c_i), ("bpp", c_i), ("palette_entries", c_i),
+                ("reserved", c_i), ("raw_bytes", c_sz), ("idat_bytes", c_sz)]
+
+
+class PngImage(C.Structure):
+    """include/tbn_hip.h tbn_png_image: one row of the image table of tbn_png_decode / tbn_png_decode_host"""
+    _fields_ = [("in_off", C.c_uint64), ("palette_off", C.c_uint64), ("in_len", C.c_uint32), ("adler", C.c_uint32)]
+
+
 class MetricHead(C.Structure):
     """include/tbn_hip.h tbn_metric_head"""
     _fields_ = [("scores", c_fp), ("scores_ld", c_i), ("classes", c_i), ("target", c_fp), ("conf_mat", c_fp)]
@@ -301,6 +312,19 @@ SIGNATURES = {
     "tbn_deflate_host": (c_i, [c_fp, c_sz, c_fp, c_i, c_fp, c_sz, c_fp, c_fp, c_fp]),
     "tbn_deflate_batch_indexed": (c_i, [c_fp, c_sz, c_fp, c_i, c_fp, c_sz, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]),
     "tbn_deflate_host_indexed": (c_i, [c_fp, c_sz, c_fp, c_i, c_fp, c_sz, c_fp, c_fp, c_fp, c_fp]),
+    # reference core/dataset/dataset.py:305, :360, :365 (cv2.imread of a PNG frame): host container walk, inflate on the host
+    # or the device, one unfilter + conversion kernel
+    "tbn_png_parse": (c_i, [C.c_char_p, c_sz, C.POINTER(PngGeometry)]),
+    "tbn_png_parse_header": (c_i, [C.c_char_p, c_sz, C.POINTER(PngGeometry)]),
+    "tbn_png_gather_bytes": (c_sz, [c_sz]),
+    "tbn_png_gather": (c_i, [C.c_char_p, c_sz, C.POINTER(PngGeometry), c_fp, c_fp, C.POINTER(C.c_uint32),
+                             C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "tbn_png_limits": (c_i, [C.POINTER(c_i), C.POINTER(c_i), C.POINTER(c_i)]),
+    "tbn_png_unfilter": (c_i, [c_fp, c_fp, c_i, C.POINTER(PngGeometry), c_i, c_fp, c_fp, c_fp]),
+    "tbn_png_workspace_bytes": (c_sz, [C.POINTER(PngGeometry), c_i]),
+    "tbn_png_decode": (c_i, [c_fp, c_sz, c_fp, c_i, C.POINTER(PngGeometry), c_i, c_fp, c_fp, c_fp, c_fp, c_fp]),
+    "tbn_png_unfilter_host": (c_i, [c_fp, c_fp, c_i, C.POINTER(PngGeometry), c_i, c_fp, c_fp]),
+    "tbn_png_decode_host": (c_i, [c_fp, c_sz, c_fp, c_i, C.POINTER(PngGeometry), c_i, c_fp, c_fp, c_fp, c_fp]),
 }
 
 _lib = None

@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtbn_hip.so")
-SOURCES = ["api.hip", "conv_igemm.hip", "conv_bf16x.hip", "bn.hip", "bn_multi.hip", "bn_res.hip", "pool.hip", "heads.hip", "stft.hip", "engine.hip", "train_ops.hip", "frames.hip", "jpeg.hip", "jpeg_entropy.hip", "audio_load.hip", "inflate.hip", "deflate.hip", "audio_stem.hip", "vgg_ops.hip", "vis_ops.hip"]
+SOURCES = ["api.hip", "conv_igemm.hip", "conv_bf16x.hip", "bn.hip", "bn_multi.hip", "bn_res.hip", "pool.hip", "heads.hip", "stft.hip", "engine.hip", "train_ops.hip", "frames.hip", "jpeg.hip", "jpeg_entropy.hip", "audio_load.hip", "inflate.hip", "deflate.hip", "audio_stem.hip", "vgg_ops.hip", "vis_ops.hip", "png.hip"]
 # -amdgpu-mfma-vgpr-form: the MFMA accumulators live in VGPRs instead of AGPRs.  With AGPR accumulators the compiler
 # copied every accumulator register AGPR -> VGPR -> AGPR once per K-loop iteration around some loop shapes (the split-K
 # tile kernel: 32 copies per 16 MFMAs; the LDS-DMA and LDS-halo kernels likewise) -- VALU instructions on the port the

@@ -26,7 +26,8 @@ import torch
 from ..._lib import TbnHipError
 from .audio import AudioSegments
 from .audio_file import load_audio
-from .frames import FrameReader, decode_jpegs, geometry_key, jpeg_geometry
+from .frames import (PNG_HEADER_BYTES, FrameReader, decode_jpegs, decode_pngs, geometry_key, is_png, jpeg_geometry,
+                     png_frame_size, png_geometry)
 from .npz_file import load_npz_arrays, npz_member
 from .sampler import frame_span, get_offsets
 from .transform import DevicePipeline
@@ -165,7 +166,8 @@ class _Clip(object):
 
 class Video_Dataset(object):
     """The reference's constructor `(cfg, vid_list, annotation_file, modality, transform, mode, action_list=None)` plus
-    keyword-only `device`, `threads` / `entropy` (handed to `decode_jpegs`), `audio_cache_bytes` (cap of the device
+    keyword-only `device`, `threads` / `entropy` (handed to `decode_jpegs`), `inflate` (handed to `decode_pngs`: frames
+    are JPEG or PNG by content, as cv2.imread reads them), `audio_cache_bytes` (cap of the device
     waveform cache) and `audio_load`: "host" (the default) reads a raw audio file with `read_wav` -- 16-bit PCM at
     data.audio.sampling_rate, anything else raises; "device" sends the file through `audio_file.load_audio`, which decodes
     any PCM width or float32, downmixes and resamples on the device like the reference's librosa.load (.wav files only;
@@ -180,7 +182,7 @@ class Video_Dataset(object):
 
     def __init__(self, cfg, vid_list, annotation_file, modality=["RGB"], transform=None, mode="train", action_list=None,
                  *, device="cuda", threads=8, entropy="host", audio_cache_bytes=4 << 30, audio_load="host",
-                 flow_load="host"):
+                 flow_load="host", inflate="host"):
         import pandas as pd
         if action_list is not None and len(action_list) > 0:
             raise NotImplementedError("Video_Dataset: action_list needs the reference's EpicClasses verb / noun tables, "
@@ -224,7 +226,9 @@ class Video_Dataset(object):
         self.device = torch.device(device)
         if entropy not in ("host", "device"):
             raise ValueError(f"Video_Dataset: entropy={entropy!r} is not 'host' or 'device'")
-        self.threads, self.entropy = threads, entropy
+        if inflate not in ("host", "device"):
+            raise ValueError(f"Video_Dataset: inflate={inflate!r} is not 'host' or 'device'")
+        self.threads, self.entropy, self.inflate = threads, entropy, inflate
         if audio_load == "device" and "Audio" in self.modality and not self.read_audio_pickle \
                 and str(self.aud_file_ext).lower() != "wav":
             raise ValueError(f"Video_Dataset: audio_load='device' reads .wav files, data.audio.file_ext is "
@@ -323,7 +327,7 @@ class Video_Dataset(object):
             hw = (int(arrays.shape[1]), int(arrays.shape[2]))
             return _Visual(paths, None, arrays, ("npz",) + hw, hw, None, None)
         blobs = [FrameReader._read(p) for p in paths]
-        keys = [geometry_key(jpeg_geometry(b)) for b in blobs]
+        keys = [geometry_key(png_geometry(b) if is_png(b) else jpeg_geometry(b)) for b in blobs]
         for p, k in zip(paths, keys):
             if k[:2] != keys[0][:2]:
                 raise TbnHipError(f"Video_Dataset: the frames of one clip differ in size: {paths[0]} is "
@@ -345,6 +349,14 @@ class Video_Dataset(object):
                 planes = self._read_flow_pickle(path)
                 return (int(planes.shape[1]), int(planes.shape[2]))
             return tuple(int(v) for v in record.shape[:2])
+        if str(self.vis_file_ext).lower() == "png":          # a PNG needs only its first 33 bytes; anything else in a
+            try:                                             # .png file is a JPEG's business, as cv2.imread reads by content
+                with open(path, "rb") as f:
+                    head = f.read(PNG_HEADER_BYTES)
+            except OSError:
+                raise Exception(f"Problem reading file {path}")
+            if is_png(head):
+                return png_frame_size(head)
         return jpeg_frame_size(path)
 
     def plan(self, indices, rng=None, keep=None):
@@ -408,16 +420,22 @@ class Video_Dataset(object):
 
     def _decode(self, blobs, keys, gray):
         """files of one frame size -> uint8 (n, H, W, C): ONE `decode_jpegs` call when they share components and
-        sampling (a dataset written by one encoder does); otherwise one call per kind, scattered into place"""
+        sampling (a dataset written by one encoder does); otherwise one call per kind, scattered into place.  A kind of
+        PNG files (`geometry_key`: "png" in third place) goes through `decode_pngs` instead."""
         kinds = OrderedDict()
         for i, k in enumerate(keys):
             kinds.setdefault(k, []).append(i)
         kw = dict(gray=gray, device=self.device, threads=self.threads, entropy=self.entropy)
+        png_kw = dict(gray=gray, device=self.device, threads=self.threads, inflate=self.inflate)
+
+        def decode(kind, part):
+            return decode_pngs(part, **png_kw) if kind[2] == "png" else decode_jpegs(part, **kw)
+
         if len(kinds) == 1:
-            return decode_jpegs(blobs, **kw)
+            return decode(keys[0], blobs)
         frames = None
-        for where in kinds.values():
-            part = decode_jpegs([blobs[i] for i in where], **kw)
+        for kind, where in kinds.items():
+            part = decode(kind, [blobs[i] for i in where])
             if frames is None:
                 frames = torch.empty((len(blobs),) + tuple(part.shape[1:]), dtype=torch.uint8, device=self.device)
             frames.index_copy_(0, torch.tensor(where, device=self.device), part)

@@ -16,7 +16,7 @@ from ... import ops
 from ...config import get_modality, load_config_file
 from ..dataset.dataset import Video_Dataset
 from ..dataset.epic_class import EpicClasses
-from ..dataset.frames import decode_jpegs
+from ..dataset.frames import decode_frames
 from ..dataset.transform import get_transforms
 from ..models import build_model
 from ..utils import ClipLoader
@@ -159,7 +159,7 @@ def visualize(cfg, model, criterion, dataset, index, epic_classes, device, *, ou
         name = "img_{:010d}.{}".format(int(i), cfg.data.rgb.file_ext)
         with open(os.path.join(cfg.data_dir, cfg.data.rgb.dir_prefix, vid_id, name), "rb") as f:
             blobs.append(f.read())
-    frames = decode_jpegs(blobs, device=device).flip(-1).cpu().numpy()      # BGR -> RGB
+    frames = decode_frames(blobs, device=device).flip(-1).cpu().numpy()      # BGR -> RGB
     times = [str(datetime.timedelta(seconds=int(i) / cfg.data.vid_fps))[0:-3] for i in rgb_indices[:n_seg]]
 
     fig = Figure(figsize=(16, 16))

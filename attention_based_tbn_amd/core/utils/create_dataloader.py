@@ -356,12 +356,13 @@ class ClipLoader(object):
 
 
 def create_dataloader(cfg, logger, modality, mode="test", device="cuda", *, prefetch=0, audio_load="host",
-                      flow_load="host", shard=None):
+                      flow_load="host", shard=None, inflate="host"):
     """`shard=(rank, world)`: handed to `ClipLoader`; the mode's batch size stays the global batch.  The annotation file, video list and batch size per mode follow the reference (:86-120); val reads the TRAIN
     annotation file filtered by the val video list, as there.  A relative `vid_list` path is taken from the directory
     above the `core` package, like the reference's; an empty one keeps every video.  `prefetch` is handed to `ClipLoader`,
     `audio_load` ("host" / "device": who reads raw audio files) and `flow_load` ("host" / "device": who inflates the flow
-    pickles of data.flow.read_flow_pickle) to `Video_Dataset`."""
+    pickles of data.flow.read_flow_pickle) and `inflate` ("host" / "device": who inflates PNG frames, data.rgb.file_ext "png")
+    to `Video_Dataset`."""
     logger.info(f"Creating {mode} Dataloader...")
     if mode == "train":
         vid_file, annotation_file, batch_size = cfg.train.vid_list, cfg.train.annotation_file, cfg.train.batch_size
@@ -381,7 +382,7 @@ def create_dataloader(cfg, logger, modality, mode="test", device="cuda", *, pref
             vid_list = [x.strip() for x in f.readlines() if len(x.strip()) > 0]
     transforms = get_transforms(cfg, modality, mode, device=device, flow_length=2 * cfg.data.flow.win_length)
     dataset = Video_Dataset(cfg, vid_list, annotation_file, modality, transform=transforms, mode=mode, device=device,
-                            audio_load=audio_load, flow_load=flow_load)
+                            audio_load=audio_load, flow_load=flow_load, inflate=inflate)
     loader = ClipLoader(dataset, batch_size, shuffle=(mode == "train"), prefetch=prefetch, shard=shard, logger=logger)
     logger.info("Done.")
     logger.info("----------------------------------------------------------")

@@ -104,7 +104,7 @@ def save_images_to_pickle(record, root_dir, out_dir, win_len, file_format, njobs
     """one annotation row -> (written paths, kept paths)"""
     import torch
 
-    from ..core.dataset.frames import decode_jpegs
+    from ..core.dataset.frames import decode_frames
     from ..core.dataset.npz_file import write_npz_files
     vid_id = record["video_id"]
     vid_path = os.path.join(root_dir, record["participant_id"], vid_id)
@@ -129,7 +129,7 @@ def save_images_to_pickle(record, root_dir, out_dir, win_len, file_format, njobs
     # every frame the missing stacks need, decoded once: u frames, then v frames, in one batch
     frames = sorted(set(indices[k] + i for k in todo for i in range(win_len)))
     blobs = [_read(os.path.join(vid_path, uv, file_format.format(f))) for uv in ("u", "v") for f in frames]
-    planes = decode_jpegs(blobs, gray=True, device=device, threads=max(1, min(16, njobs)))       # (2 F, H, W, 1)
+    planes = decode_frames(blobs, gray=True, device=device, threads=max(1, min(16, njobs)))       # (2 F, H, W, 1)
     F = len(frames)
     pairs = torch.cat((planes[:F], planes[F:]), dim=3)                                            # (F, H, W, 2): u_f, v_f
     slot = {f: j for j, f in enumerate(frames)}

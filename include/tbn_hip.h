@@ -1243,6 +1243,96 @@ int tbn_deflate_batch_indexed(const void* raw_dev, size_t raw_bytes, const tbn_d
 int tbn_deflate_host_indexed(const void* raw, size_t raw_bytes, const tbn_deflate_member* members, int n_members, void* out,
                              size_t out_bytes, uint32_t* out_len, uint32_t* crc, int* status, uint32_t* chunk_end);
 
+/* ---- PNG frames into device frames (data.rgb.file_ext / data.flow.file_ext: "png") ---------- */
+/* Replaces cv2.imread of reference core/dataset/dataset.py:305 (RGB: 3 channels B, G, R) and :360, :365 (Flow:
+ * cv2.imread(path, 0), gray) for frames extracted as PNG -- lossless, so every byte is exact.  The container is host code
+ * (csrc/tbn_png_host.h) and needs no GPU; the zlib stream is inflated on host threads or, opt-in, on the device with the
+ * decoder core of tbn_inflate_batch (csrc/tbn_inflate.h); scanline unfiltering and the conversion to frame bytes are one
+ * kernel.  Supported: bit depth 8, non-interlaced, colour types 0 (gray), 2 (RGB), 3 (palette), 4 (gray + alpha), 6 (RGBA);
+ * alpha is dropped and ancillary chunks (tRNS, gAMA, ...) are skipped unread, as cv2.imread does at its defaults.  Refused
+ * with a message naming the reason (TBN_ERR_UNSUPPORTED: bit depths 1, 2, 4, 16, Adam7 interlace, a scanline of more than
+ * 16384 bytes = 4096 RGBA pixels, 2^31 or more scanline bytes; TBN_ERR_ARG: anything malformed or truncated).  There is no
+ * capability bit: callers detect the feature by the symbol. */
+#ifndef TBN_PNG_GEOMETRY_DEFINED
+#define TBN_PNG_GEOMETRY_DEFINED
+typedef struct tbn_png_geometry {
+  int width, height;        /* image size in pixels */
+  int colour_type;          /* 0 gray, 2 RGB, 3 palette, 4 gray + alpha, 6 RGBA */
+  int bpp;                  /* bytes per pixel in the scanlines: 1, 3, 1, 2, 4 */
+  int palette_entries;      /* entries of PLTE (colour type 3; else 0).  Per file: not compared */
+  int reserved;
+  size_t raw_bytes;         /* the inflated scanlines: height * (1 + width * bpp) */
+  size_t idat_bytes;        /* sum of the IDAT payloads: the zlib stream.  Per file: not compared */
+} tbn_png_geometry;
+#endif
+/* HOST, thread-safe.  Walks `size` untrusted bytes: the signature; IHDR first and 13 bytes long; chunk lengths inside the
+ * file; CRC-32 of IHDR, PLTE, IDAT and IEND (ancillary chunks are skipped unread); PLTE present with 3 * (1..256) bytes
+ * for colour type 3; consecutive IDAT chunks; IEND present.  Fills `out`.
+ * replaces: the header half of cv2.imread, core/dataset/dataset.py:305, :360, :365 */
+int tbn_png_parse(const unsigned char* data, size_t size, tbn_png_geometry* out);
+/* HOST, thread-safe.  The same IHDR checks on the first 33 bytes alone (signature, IHDR and its CRC): width, height,
+ * colour_type, bpp and raw_bytes of a frame whose file is not read further.
+ * replaces: frame.shape of a cv2.imread result where only the size is used, core/dataset/dataset.py:305 */
+int tbn_png_parse_header(const unsigned char* data, size_t size, tbn_png_geometry* out);
+/* bytes tbn_png_gather writes for a zlib stream of idat_bytes: 2 + idat_bytes rounded up to 4, plus 4 */
+size_t tbn_png_gather_bytes(size_t idat_bytes);
+/* HOST, thread-safe.  Concatenates the IDAT payloads -- the zlib stream, split anywhere, inside its header and into empty
+ * chunks too -- into zstream[2, 2 + expect->idat_bytes) (4-byte aligned, tbn_png_gather_bytes() long, pinned if it is to
+ * be copied asynchronously; the rest is zeroed), so that the raw deflate data behind the 2-byte zlib header starts at
+ * byte 4, a multiple of 4 as tbn_inflate_member.in_off and tbn_png_image.in_off require.  Checks the zlib header (CM 8,
+ * window <= 32 K, no preset dictionary, FCHECK).  [*deflate_begin, *deflate_end) of zstream is the deflate data, *adler
+ * the stream's trailing Adler-32.  palette_bgr (1024 bytes; may be NULL): 256 x 3 bytes B, G, R with unused entries
+ * zero, the entry count as a little-endian uint32 at byte 768, zeros behind it.  Refuses a file whose size, colour type
+ * or IDAT byte count differs from `expect`.
+ * replaces: the chunk-reading half of cv2.imread, core/dataset/dataset.py:305, :360, :365 */
+int tbn_png_gather(const unsigned char* data, size_t size, const tbn_png_geometry* expect, unsigned char* zstream,
+                   unsigned char* palette_bgr, uint32_t* deflate_begin, uint32_t* deflate_end, uint32_t* adler);
+/* the sizes at which the unfilter kernel changes its path, for tests: rows of a band (64), pixel steps between two staging
+ * passes (64), the longest scanline in bytes (16384).  cv2.imread of core/dataset/dataset.py:305 has no such seams. */
+int tbn_png_limits(int* band_rows, int* step_tile, int* max_row_bytes);
+/* DEVICE.  n_img images of ONE geometry: raw_dev (n_img, raw_bytes), 4-byte aligned, are the inflated scanlines, each with
+ * its filter byte; palette_dev (n_img, 1024) in tbn_png_gather's layout (colour type 3 only; else ignored);
+ * frames_dev (n_img, height, width, out_channels) uint8.  Filters None, Sub, Up, Average (9-bit sum, floor) and Paeth
+ * (ties in the order a, b, c), prior row of the first row = 0, a = c = 0 at the first pixel, arithmetic mod 256.
+ * out_channels 3: gray replicated, RGB as B, G, R, alpha dropped, palette looked up.  out_channels 1: colour types 0 and 4
+ * only (cv2.imread(path, 0) of a colour file goes through a conversion formula that is not reproduced: TBN_ERR_ARG).
+ * status_dev[n_img]: 0 ok; 21 a filter byte above 4 (that row is taken as filter 0); 22 a palette index at or beyond the
+ * entry count (that pixel is 0, 0, 0).  One wavefront per image, rows of a 64-row band on the lanes, skewed by one pixel
+ * (csrc/png.hip).  Corrupt bytes cost a status or garbage pixels, never a fault: every address depends on the geometry
+ * alone.  replaces: the row-reconstruction half of cv2.imread, core/dataset/dataset.py:305, :360, :365 */
+int tbn_png_unfilter(const unsigned char* raw_dev, const unsigned char* palette_dev, int n_img, const tbn_png_geometry* geometry,
+                     int out_channels, unsigned char* frames_dev, int* status_dev, void* stream);
+/* One row of the image table of tbn_png_decode (24 bytes):
+ *   in_off, in_len   the image's raw deflate data inside `in` (tbn_png_gather: zstream + *deflate_begin, of
+ *                    *deflate_end - *deflate_begin bytes); in_off is a multiple of 4
+ *   palette_off      its 1024-byte palette slot inside `in` (colour type 3; else ignored)
+ *   adler            the stream's trailing Adler-32 */
+typedef struct tbn_png_image {
+  uint64_t in_off, palette_off;
+  uint32_t in_len, adler;
+} tbn_png_image;
+/* bytes of workspace tbn_png_decode needs for n_img images of this geometry (their inflated scanlines); 0 for a geometry
+ * it would refuse.  cv2.imread of core/dataset/dataset.py:305 allocates the like inside libpng. */
+size_t tbn_png_workspace_bytes(const tbn_png_geometry* geometry, int n_img);
+/* DEVICE (opt-in; the default inflates on host threads).  Three launches on `stream`: one wavefront per image inflates its
+ * deflate data into the workspace with the decoder core of tbn_inflate_batch; one workgroup per image checks the Adler-32
+ * of the inflated bytes; tbn_png_unfilter's kernel then skips every image whose status is not 0.  in_dev[0, in_bytes) and
+ * the workspace: 4-byte aligned; images_dev[n_img]: device memory, 8-byte aligned.  status_dev[n_img]: 0 ok; 1..12 the
+ * statuses of tbn_inflate_batch, raw_bytes being the required output length (12: the row is inconsistent); 20 Adler-32
+ * mismatch; 21, 22 as above.  With a non-zero status the image's frame is unspecified -- it is for the host stage.
+ * info_dev[n_img]: bytes inflated.  A damaged stream costs a status, never a fault or a hang.
+ * replaces: the zlib and row-reconstruction halves of cv2.imread, core/dataset/dataset.py:305, :360, :365 */
+int tbn_png_decode(const void* in_dev, size_t in_bytes, const tbn_png_image* images_dev, int n_img,
+                   const tbn_png_geometry* geometry, int out_channels, unsigned char* frames_dev, void* workspace,
+                   int* status_dev, int* info_dev, void* stream);
+/* HOST, thread-safe, no GPU call: the same predictors, conversion, decoder core and Adler pieces run serially, all pointers
+ * host memory, the same statuses and the same bytes.  The test aids of tbn_png_unfilter and tbn_png_decode (cv2.imread of
+ * core/dataset/dataset.py:305 is their common reference). */
+int tbn_png_unfilter_host(const unsigned char* raw, const unsigned char* palette, int n_img, const tbn_png_geometry* geometry,
+                          int out_channels, unsigned char* frames, int* status);
+int tbn_png_decode_host(const void* in, size_t in_bytes, const tbn_png_image* images, int n_img, const tbn_png_geometry* geometry,
+                        int out_channels, unsigned char* frames, void* workspace, int* status, int* info);
+
 #ifdef __cplusplus
 }
 #endif
